@@ -11,6 +11,9 @@ One step = the whole hot path on one batch of synthetic input already resident i
 Nothing is skipped inside the timed region.  `value` counts the 90 TRAINED images per GPU per step
 (BASELINE.json configs[1]); `value_train_only` times the same step without the mining forward.
 
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) to DIR/<name>.npy: the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
 Weak scaling: every rank trains its own 90-image batch (per-replica BatchNorm, local mining); gradients are summed
 by RCCL all-reduce in backward-ordered buckets overlapped with backward.
 """
@@ -363,6 +366,44 @@ def embedding_l2_err(dev):
     return out
 
 
+DUMP_SAMPLE = 1 << 20          # entries of the seeded sample taken from each model-sized state vector (--dump-outputs)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(trainer, miner, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, as the arrays its caller receives, one DIR/<name>.npy each.
+    Mining: the pool's unit embeddings, their distance matrix and the selected (a, p, n) pool indices.  Training: the loss, the
+    trained batch's unit embeddings, the moving BatchNorm statistics, and of the parameters, gradients and Adam moments (Keras
+    variables in Keras layout and order, flattened and concatenated: too large to write whole) a fixed seeded sample of
+    DUMP_SAMPLE entries whose positions are `state_sample_index`.  Float arrays are float32, indices float64."""
+    net = trainer.net
+    torch.cuda.synchronize()
+    params = net.export_keras_params()
+    grads = net.export_keras_grads(trainer.G)                        # keyed by the trainable variables, in order
+    flat = lambda d: torch.cat([d[k].reshape(-1) for k in grads]).numpy()
+    state = {"params": flat(params), "grads": flat(grads),
+             "adam_m": flat(net.export_keras_grads(trainer.M)), "adam_v": flat(net.export_keras_grads(trainer.V))}
+    n = state["params"].size
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    out = {
+        "mining_embeddings": miner.embn.cpu().numpy(),
+        "mining_distances": miner.dist.cpu().numpy(),
+        "triplets": miner.triplets.cpu().numpy().astype(np.float64),
+        "loss": trainer.loss[:1].cpu().numpy(),
+        "embeddings": trainer.embn.cpu().numpy(),
+        "moving_mean": torch.cat([v.reshape(-1) for k, v in params.items() if k.endswith("/moving_mean")]).numpy(),
+        "moving_variance": torch.cat([v.reshape(-1) for k, v in params.items() if k.endswith("/moving_variance")]).numpy(),
+        "state_sample_index": idx.astype(np.float64),
+        **{f"{k}_sample": v[idx] for k, v in state.items()},
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process (one rank per GPU, RCCL), let
@@ -425,10 +466,14 @@ def main():
                          "FACENET_DIST_BACKEND (default nccl = RCCL): the exchange is the identity, the backend calls, the "
                          "communication stream and its ordering against the captured segments are the real ones")
     ap.add_argument("--dump-ops", default=None, help="write per-launch HIP-event timings (eager) to this JSON file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; float32 / float64, at most 64 MB)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / reporting path only: no HIP work (CPU test of --gpus N)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.streams > 2 and not args.no_graph:
         raise SystemExit("--streams > 2 needs --no-graph: captured schedules span at most 2 streams (DESIGN.md section 5)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -444,9 +489,17 @@ def main():
 
     # the tile choices of the committed profiles (profiles/rNN_tile_cache.json of the latest round: one autotune run on an MI355X) are reused when
     # present: the run then launches the kernel variants the rocprofv3 passes under profiles/ measured (roofline.traffic), starts
-    # faster and is reproducible.  FACENET_TUNE_CACHE= (empty) re-tunes from scratch.
+    # faster and is reproducible.  FACENET_TUNE_CACHE= (empty) re-tunes from scratch.  The run reads a private copy: shapes the
+    # profile lacks (other --batch / --pool) are tuned into the copy, never into the committed file.
     if "FACENET_TUNE_CACHE" not in os.environ and os.path.exists(latest_profile("tile_cache.json")):
-        os.environ["FACENET_TUNE_CACHE"] = latest_profile("tile_cache.json")
+        import atexit
+        import shutil
+        import tempfile
+        fd, cache = tempfile.mkstemp(prefix="facenet_tiles_", suffix=".json")
+        os.close(fd)
+        shutil.copyfile(latest_profile("tile_cache.json"), cache)
+        atexit.register(lambda: os.path.exists(cache) and os.remove(cache))
+        os.environ["FACENET_TUNE_CACHE"] = cache
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # one process per GPU; FACENET_DIST_BACKEND=gloo lets the whole data-parallel path be rehearsed with several ranks on
@@ -535,6 +588,8 @@ def main():
     loss_warm = trainer.loss_value()
     elapsed = timed(args.steps, True)
     loss = trainer.loss_value()            # last mined step (the train-only replays below re-fit one batch: not a loss to report)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, miner, args.dump_outputs)
     n2 = max(5, args.steps // 2)
     elapsed_train = timed(n2, False)
 
@@ -588,7 +643,13 @@ def main():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     if rank == 0:
-        print(json.dumps(out))
+        print(json.dumps(out), flush=True)      # on stdout before any teardown: a pipe would otherwise hold it until exit
+    # Captured graphs, streams and device buffers are released here, while the HIP runtime is up.  The trainer and the miner sit
+    # in reference cycles (their ops close over them), so without this they would be collected during interpreter shutdown.
+    trainer = miner = net = mine_graph = pools = step = timed = None
+    import gc
+    gc.collect()
+    torch.cuda.synchronize()
 
 
 if __name__ == "__main__":

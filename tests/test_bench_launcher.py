@@ -61,3 +61,24 @@ def test_real_step_through_the_launcher_two_gloo_ranks_on_one_gpu():
     xp = out["gradient_exchange"]
     assert xp["n_buckets"] == len(xp["buckets"]) >= 3 and xp["allreduce_ms"] > 0 and 0.0 <= xp["overlapped_frac"] <= 1.0
     assert abs(sum(b["elements"] for b in xp["buckets"]) * 4e-6 - sum(b["mbytes"] for b in xp["buckets"])) < 0.1
+
+
+@pytest.mark.gpu
+def test_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files, at most 64 MB; two runs with the same
+    arguments write the same bits (seeded inputs, reproducible training step)."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                            "--dump-outputs", str(tmp_path / name)], env=_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert _last_json(r.stdout)["steps"] == 3
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / name).iterdir())})
+    a, b = runs
+    assert {"loss.npy", "triplets.npy", "embeddings.npy", "params_sample.npy", "grads_sample.npy"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert float(a["loss.npy"][0]) > 0 and np.abs(a["grads_sample.npy"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
