@@ -82,6 +82,10 @@ _SIGNATURES = {
     "fn_nms_greedy": [_p, _i, _p, _i, C.c_double, _i, _p, C.c_long, _p, _p, _p],
     "fn_avgpool_fwd": [_p, _p, _i, _i, _i, _i, _p],
     "fn_avgpool_bwd": [_p, _p, _i, _i, _i, _i, _p],
+    "fn_avgpool3x3s1_fwd": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "fn_avgpool3x3s1_bwd": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "fn_dropout_fwd": [_p, _p, _i, _i, _f, _u, _i, _p, _i, _p],
+    "fn_dropout_bwd": [_p, _p, _i, _i, _f, _u, _i, _p, _i, _p],
     "fn_residual_bwd": [_p, _p, _p, _p, _p, _i, _i, _f, _i, _i, _i, _p],
     "fn_acc_to_float": [_p, _p, _l, _i, _p],
     "fn_head_bn_fwd": [_p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _f, _f, _p],

@@ -38,8 +38,19 @@ class FaceNet:
         model_cfg = dict(default_config)
         if config.embedding_size:
             model_cfg["output"] = {"size": int(config.embedding_size)}
-        self._model = InceptionResnetV1(inputs(image), ImageProcessing(image), Config(model_cfg),
-                                        device=config.device if config.device else "cuda")
+        from .engine_v2 import NetworkV2, network_class
+        device = config.device if config.device else "cuda"
+        if network_class(config.model.module if config.model else None) is NetworkV2:     # model.module selects the family
+            from .models.inception_resnet_v2 import InceptionResnetV2
+            from .models.inception_resnet_v2 import default_config as v2_default
+            v2_cfg = dict(v2_default.as_dict)
+            if config.model.config:
+                v2_cfg.update(config.model.config.as_dict)
+            if config.embedding_size:
+                v2_cfg["embedding_size"] = int(config.embedding_size)
+            self._model = InceptionResnetV2(inputs(image), ImageProcessing(image), Config(v2_cfg), device=device)
+        else:
+            self._model = InceptionResnetV1(inputs(image), ImageProcessing(image), Config(model_cfg), device=device)
         if config.path:
             path = Path(config.path).expanduser()
             if path.is_dir():

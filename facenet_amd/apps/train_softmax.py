@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from facenet_amd import config as config_mod
-from facenet_amd.engine import Network
+from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
 from facenet_amd.train import Trainer
 
@@ -60,8 +60,9 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     if cfg.batch_size % world_size:
         raise ValueError(f"batch_size {cfg.batch_size} is not divisible by the {world_size} replicas")
     local_batch = cfg.batch_size // world_size
-    net = Network(embedding_size=embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
-                  nrof_classes=nrof_classes, device=device, seed=cfg.seed)
+    # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
+    net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
+                        nrof_classes=nrof_classes, device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group)
     first_epoch = 0

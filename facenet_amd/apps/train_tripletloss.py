@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from facenet_amd import config as config_mod
-from facenet_amd.engine import Network
+from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
 from facenet_amd.train import GraphRunner, Trainer, TripletMiner
 from facenet_amd.schedule import make_events
@@ -25,7 +25,9 @@ from facenet_amd.schedule import make_events
 def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 4, nrof_triplets: int = 30, embedding_size: int = 128,
                       pools=None, device: str = "cuda", use_graph: bool = True, world_size: int = 1, process_group=None, log=print):
     alpha = cfg.loss.alpha if cfg.loss.alpha else 0.2
-    net = Network(embedding_size=embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization, device=device, seed=cfg.seed)
+    # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
+    net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
+                        device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=3 * nrof_triplets, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size,
                       process_group=process_group)

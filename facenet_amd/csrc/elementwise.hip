@@ -26,9 +26,13 @@ __global__ __launch_bounds__(256) void img_stats_kernel(const SRC* __restrict__ 
     const SRC* p = img + (long)n * count;
     float mx = -3e38f, mn = 3e38f, s = 0.f, q = 0.f;
     constexpr int PER = 16 / sizeof(SRC);
-    const int nvec = count / PER;
+    // images whose byte size is not a multiple of 16 (e.g. 299x299x3 u8) start unaligned: scalar head up to the first 16-B
+    // boundary, 16-B vectors, scalar tail (head = 0 for aligned images: the same loads and order as before)
+    const int head = min(count, (int)(((16 - ((uintptr_t)p & 15)) & 15) / sizeof(SRC)));
+    const int nvec = (count - head) / PER;
+    const SRC* pv = p + head;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(p + (long)i * PER);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(pv + (long)i * PER);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             if constexpr (sizeof(SRC) == 1) {
@@ -43,11 +47,16 @@ __global__ __launch_bounds__(256) void img_stats_kernel(const SRC* __restrict__ 
             }
         }
     }
-    if (blockIdx.x == 0)
-        for (int i = nvec * PER + threadIdx.x; i < count; i += 256) {
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < head; i += 256) {
             const float x = (float)p[i];
             mx = fmaxf(mx, x); mn = fminf(mn, x); s += x; q += x * x;
         }
+        for (int i = head + nvec * PER + threadIdx.x; i < count; i += 256) {
+            const float x = (float)p[i];
+            mx = fmaxf(mx, x); mn = fminf(mn, x); s += x; q += x * x;
+        }
+    }
     mx = wave_max(mx); mn = -wave_max(-mn); s = wave_sum(s); q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) {
         atomicMax(&work[8 * n + 0], f2ord(mx));
@@ -556,6 +565,103 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const unsigned short* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Inception-ResNet-v2 Mixed_5a Branch_3: AvgPool 3x3, stride 1, SAME (TF semantics: divide by the number of IN-MAP taps,
+// 4 / 6 / 9).  One thread per (pixel, 8-channel group); the backward is the gather form (no atomics, bit-reproducible).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int avg3_taps(int i, int n) { return (i > 0) + 1 + (i + 1 < n); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool3s1_fwd_kernel(const unsigned short* __restrict__ x, int ld_x, unsigned short* __restrict__ y,
+                                                             int ld_y, int N, int H, int W, int C) {
+    const int CG = C >> 3;
+    const long total = (long)N * H * W * CG;
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+        const int cg = (int)(t % CG);
+        long pix = t / CG;
+        const int ox = (int)(pix % W); pix /= W;
+        const int oy = (int)(pix % H);
+        const int n = (int)(pix / H);
+        float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int iy = max(0, oy - 1); iy <= min(H - 1, oy + 1); ++iy)
+            for (int ix = max(0, ox - 1); ix <= min(W - 1, ox + 1); ++ix) {
+                float v[8];
+                unpack8<T>(*reinterpret_cast<const u32x4*>(x + ((long)(n * H + iy) * W + ix) * ld_x + cg * 8), v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s[e] += v[e];
+            }
+        const float inv = 1.f / (float)(avg3_taps(oy, H) * avg3_taps(ox, W));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] *= inv;
+        *reinterpret_cast<u32x4*>(y + ((long)(n * H + oy) * W + ox) * ld_y + cg * 8) = pack8<T>(s);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool3s1_bwd_kernel(const unsigned short* __restrict__ dy, int ld_dy, unsigned short* __restrict__ dx,
+                                                             int ld_dx, int N, int H, int W, int C, int accumulate) {
+    const int CG = C >> 3;
+    const long total = (long)N * H * W * CG;
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+        const int cg = (int)(t % CG);
+        long pix = t / CG;
+        const int ix = (int)(pix % W); pix /= W;
+        const int iy = (int)(pix % H);
+        const int n = (int)(pix / H);
+        float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int oy = max(0, iy - 1); oy <= min(H - 1, iy + 1); ++oy)
+            for (int ox = max(0, ix - 1); ox <= min(W - 1, ix + 1); ++ox) {
+                float d[8];
+                unpack8<T>(*reinterpret_cast<const u32x4*>(dy + ((long)(n * H + oy) * W + ox) * ld_dy + cg * 8), d);
+                const float inv = 1.f / (float)(avg3_taps(oy, H) * avg3_taps(ox, W));
+#pragma unroll
+                for (int e = 0; e < 8; ++e) g[e] += d[e] * inv;
+            }
+        unsigned short* o = dx + ((long)(n * H + iy) * W + ix) * ld_dx + cg * 8;
+        if (accumulate) {
+            float pv[8];
+            unpack8<T>(*reinterpret_cast<const u32x4*>(o), pv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] += pv[e];
+        }
+        *reinterpret_cast<u32x4*>(o) = pack8<T>(g);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dropout on the pooled [N,C] features (Inception-ResNet-v2 Logits/Dropout).  The keep bit of (n, c) is
+// dropout_hash(seed, rank, t, n, c) < keep_threshold with t read from device memory (graph replays advance it); the
+// backward recomputes the same bits, so there is no mask buffer.  Kept values are scaled by 1/keep.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned dropout_mix(unsigned h, unsigned v) {      // lowbias32 fold, as loss.hip:hash_mix
+    h ^= v;
+    h ^= h >> 16; h *= 0x7FEB352Du;
+    h ^= h >> 15; h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ unsigned dropout_hash(unsigned seed, unsigned rank, unsigned t, unsigned n, unsigned c) {
+    return dropout_mix(dropout_mix(dropout_mix(dropout_mix(dropout_mix(0x9E3779B9u, seed), rank), t), n), c);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, int N, int C,
+                                                      unsigned thresh, float inv_keep, unsigned seed, unsigned rank,
+                                                      const int* __restrict__ step) {
+    const unsigned t = (unsigned)*step;
+    const int CG = C >> 3;
+    const long total = (long)N * CG;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int n = (int)(i / CG), c0 = (int)(i % CG) * 8;
+        float v[8];
+        unpack8<T>(*reinterpret_cast<const u32x4*>(x + (long)n * C + c0), v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            v[e] = dropout_hash(seed, rank, t, (unsigned)n, (unsigned)(c0 + e)) < thresh ? v[e] * inv_keep : 0.f;
+        *reinterpret_cast<u32x4*>(y + (long)n * C + c0) = pack8<T>(v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // residual backward:  out = act(trunk + scale*(up + bias))
 // ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -727,7 +833,7 @@ static int image_normalize_impl(const SRC* img, void* out, float* work, int N, i
     DT_CHECK(dtype);
     FN_REQUIRE(img && out && work && N > 0 && HW > 0, "image_normalize: bad arguments");
     FN_REQUIRE(mode == 0 || mode == 1, "Invalid image normalization algorithm");  // facenet.py:82
-    FN_REQUIRE(((uintptr_t)img & 15) == 0 && ((long)HW * 3 * sizeof(SRC)) % 16 == 0, "image_normalize: images must be 16-B aligned");
+    FN_REQUIRE(((uintptr_t)img % sizeof(SRC)) == 0, "image_normalize: misaligned images");
     hipStream_t st = (hipStream_t)stream;
     fill_words(work, 0u, 0u, 8 * N, st);
     hipLaunchKernelGGL(img_stats_kernel<SRC>, dim3(8, N), dim3(256), 0, st, img, (unsigned*)work, HW * 3);
@@ -888,6 +994,40 @@ extern "C" int fn_avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, in
     FN_REQUIRE(dy && dx && N > 0 && HW > 0 && C % 8 == 0, "avgpool_bwd: bad arguments");
     LAUNCH_T(dtype, avgpool_bwd_kernel, dim3(grid_for((long)N * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)dy, (unsigned short*)dx, N, HW, C);
     return check_launch("avgpool_bwd");
+}
+
+extern "C" int fn_avgpool3x3s1_fwd(const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, int dtype, void* stream) {
+    DT_CHECK(dtype);
+    FN_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && ld_x % 8 == 0 && ld_y % 8 == 0 && ld_x >= C && ld_y >= C,
+               "avgpool3x3s1_fwd: bad arguments");
+    LAUNCH_T(dtype, avgpool3s1_fwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+             (const unsigned short*)x, ld_x, (unsigned short*)y, ld_y, N, H, W, C);
+    return check_launch("avgpool3x3s1_fwd");
+}
+extern "C" int fn_avgpool3x3s1_bwd(const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C, int accumulate, int dtype,
+                                   void* stream) {
+    DT_CHECK(dtype);
+    FN_REQUIRE(dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && ld_dy % 8 == 0 && ld_dx % 8 == 0 && ld_dy >= C && ld_dx >= C,
+               "avgpool3x3s1_bwd: bad arguments");
+    LAUNCH_T(dtype, avgpool3s1_bwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+             (const unsigned short*)dy, ld_dy, (unsigned short*)dx, ld_dx, N, H, W, C, accumulate);
+    return check_launch("avgpool3x3s1_bwd");
+}
+static int dropout_launch(const void* x, void* y, int N, int C, float keep, unsigned seed, int rank, const int* step, int dtype, void* stream,
+                          const char* what) {
+    DT_CHECK(dtype);
+    FN_REQUIRE(x && y && step && N > 0 && C > 0 && C % 8 == 0 && keep > 0.f && keep < 1.f && rank >= 0, "%s: bad arguments", what);
+    const double th = std::nearbyint((double)keep * 4294967296.0);
+    const unsigned thresh = th >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)th;
+    LAUNCH_T(dtype, dropout_kernel, dim3(grid_for((long)N * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
+             (unsigned short*)y, N, C, thresh, 1.f / keep, seed, (unsigned)rank, step);
+    return check_launch(what);
+}
+extern "C" int fn_dropout_fwd(const void* x, void* y, int N, int C, float keep, unsigned seed, int rank, const int* step, int dtype, void* stream) {
+    return dropout_launch(x, y, N, C, keep, seed, rank, step, dtype, stream, "dropout_fwd");
+}
+extern "C" int fn_dropout_bwd(const void* dy, void* dx, int N, int C, float keep, unsigned seed, int rank, const int* step, int dtype, void* stream) {
+    return dropout_launch(dy, dx, N, C, keep, seed, rank, step, dtype, stream, "dropout_bwd");   // same bits, same scale
 }
 
 extern "C" int fn_residual_bwd(const void* dout, const void* out, void* dtrunk, void* dup, fn_acc_t* dbias_, int M, int C, float scale, int relu,

@@ -159,11 +159,15 @@ def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
 class Network:
     """Parameters + topology of Inception-ResNet-v1; ``plan()`` lowers it for one batch size."""
 
+    default_config = DEFAULT_CONFIG
+    bn_momentum = BN_MOMENTUM     # moving-statistics decay of every BatchNorm of the family (v2: 0.995, engine_v2.py)
+    l2_weight = L2_WEIGHT         # the Trainer's default coupled L2 factor (g += 2 * l2 * w on the kernels)
+
     def __init__(self, embedding_size: int = 512, config: Optional[dict] = None, image_size: int = 160,
                  normalization: int = 0, nrof_classes: Optional[int] = None, device: str = "cuda",
                  train_dtype: torch.dtype = torch.bfloat16, infer_dtype: torch.dtype = torch.float16, seed: int = 0,
                  allocate: bool = True):
-        self.cfg = {k: (dict(v) if isinstance(v, dict) else v) for k, v in DEFAULT_CONFIG.items()}
+        self.cfg = {k: (dict(v) if isinstance(v, dict) else v) for k, v in type(self).default_config.items()}
         if config:
             for k, v in config.items():
                 self.cfg[k] = v
@@ -173,6 +177,7 @@ class Network:
         self.nrof_classes = nrof_classes
         self.device = torch.device(device)
         self.train_dtype, self.infer_dtype = train_dtype, infer_dtype
+        self.seed = int(seed)
         # allocate=False: host-side description only (layer table, flat layout, variable counts) -- nothing is computed
         if allocate and self.device.type != "cuda":
             raise _lib.FacenetHipError("facenet_amd runs on a HIP device only (no CPU fallback)")
@@ -336,6 +341,11 @@ class Network:
         from . import keras_names
         return keras_names.from_keras(params, self.layers, int(self.cfg["block8_1"]["repeat"]))
 
+    def variable_table(self) -> List[Tuple[str, str]]:
+        """[(file variable name, engine key)] in save order: what checkpoints (and their optimiser slots) are keyed by."""
+        from . import keras_names
+        return keras_names.keras_variable_table(self.layers, int(self.cfg["block8_1"]["repeat"]))
+
     def keras_variables(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
         """``model.weights`` of the reference model: Keras variable names, Keras layouts, Keras order (keras_names.py)."""
         from . import keras_names
@@ -434,8 +444,11 @@ class Network:
             tot += k + (L.cout_real if L.has_bias else 0) + (3 * L.cout if L.has_bn else 0)
         return tot, tr
 
-    def plan(self, N: int, training: bool, loss: Optional[str] = None) -> "Lowering":
-        g = Lowering(self, N=N, training=training, declare=False, loss=loss)
+    def plan(self, N: int, training: bool, loss: Optional[str] = None, step_word: Optional[torch.Tensor] = None,
+             rank: int = 0) -> "Lowering":
+        """``step_word``: device int32 the dropout masks read their step from (the Trainer passes Keras' ``iterations``); a plan
+        given none owns a counter of its own (``Lowering.step_word``).  ``rank``: data-parallel replica (masks differ per rank)."""
+        g = Lowering(self, N=N, training=training, declare=False, loss=loss, step_word=step_word, rank=rank)
         g.embedding = self._topology(g)
         g.finish()
         return g
@@ -476,8 +489,10 @@ class BlockNetwork(Network):
 # lowering: topology -> buffers + forward records -> launch lists
 # ------------------------------------------------------------------------------------------------
 class Lowering:
-    def __init__(self, net: Network, N: int, training: bool, declare: bool, loss: Optional[str] = None):
+    def __init__(self, net: Network, N: int, training: bool, declare: bool, loss: Optional[str] = None,
+                 step_word: Optional[torch.Tensor] = None, rank: int = 0):
         self.net, self.N, self.training, self.declare, self.loss = net, N, training, declare, loss
+        self.step_word, self.rank = step_word, int(rank)     # dropout: where the step count lives, data-parallel replica
         self.fuse_bn_bwd = True     # BN-backward reduction inside the producing dgrad's epilogue where it is the sole producer
         # Optional: BN+ReLU outputs that only convolutions read are never written; the consumers (forward and weight
         # gradient) normalise the raw tensor while staging their operand tile (fn_conv_desc.nrm_*) and fn_bn_finalize
@@ -521,6 +536,7 @@ class Lowering:
         self.bn_ranges: Dict[str, List[Tuple[int, int, bool]]] = {}
         self.bn_reduced: Dict[Tuple[str, int, int], int] = {}   # BN slices whose backward reduction a dgrad epilogue performs
         self.embedding = None
+        self.head_out = "features/bn"
 
     # ---- buffers -------------------------------------------------------------------------------
     def buf(self, name: str, H: int, W: int, Cc: int, bn_channels: int = 0, need_raw: bool = False, f32: bool = False) -> Buf:
@@ -600,6 +616,13 @@ class Lowering:
         self.recs.append(Rec("maxpool", None, x, out))
         return out
 
+    def avgpool3(self, name: str, x: Slice) -> Slice:
+        """AvgPool 3x3 / stride 1 / SAME (TF: divisor = in-map taps) into a buffer of its own."""
+        out = self.buf(name, x.buf.H, x.buf.W, x.C).full()
+        self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
+        self.recs.append(Rec("avgpool3", None, x, out))
+        return out
+
     def _tower(self, prefix: str, x: Slice, tower, last_out: Slice) -> None:
         for j, spec in enumerate(tower):
             nm, cout, k = spec[0], spec[1], spec[2]
@@ -611,7 +634,8 @@ class Lowering:
             else:
                 x = self.cbr(name, x, cout, k, stride, padding)
 
-    def block(self, prefix: str, trunk: Slice, towers, up: int, scale: float, relu: bool) -> Slice:
+    def block(self, prefix: str, trunk: Slice, towers, up: int, scale: float, relu: bool, branch: str = "tower_conv{}",
+              up_name: str = "up") -> Slice:
         """Block35/17/8 (:83-259): towers -> concat -> up 1x1 (+bias) -> act(trunk + scale*up)."""
         H, W = trunk.buf.H, trunk.buf.W
         cm = sum(t[-1][1] for t in towers)
@@ -630,15 +654,15 @@ class Lowering:
         mixed = self.buf(prefix + "/mixed", H, W, cm, bn_channels=cm, need_raw=True)
         c0 = 0
         for i, t in enumerate(towers):
-            self._tower(f"{prefix}/tower_conv{i}", trunk, t, mixed.sl(c0, t[-1][1]))
+            self._tower(f"{prefix}/{branch.format(i)}", trunk, t, mixed.sl(c0, t[-1][1]))
             c0 += t[-1][1]
         self.bn_apply(mixed, 0, cm)                      # one pass over the whole concat buffer
         out = self.buf(prefix + "/out", H, W, up)
-        self.conv(prefix + "/up", mixed.full(), up, (1, 1), 1, "same", out=out.full(), has_bn=False, has_bias=True,
+        self.conv(f"{prefix}/{up_name}", mixed.full(), up, (1, 1), 1, "same", out=out.full(), has_bn=False, has_bias=True,
                   kind="resid", trunk=trunk, scale=float(scale), relu=bool(relu))
         return out.full()
 
-    def reduction(self, prefix: str, trunk: Slice, towers) -> Slice:
+    def reduction(self, prefix: str, trunk: Slice, towers, branch: str = "tower_conv{}") -> Slice:
         """ReductionA/B (:262-377): strided towers + MaxPool, concatenated."""
         H, W = trunk.buf.H, trunk.buf.W
         OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
@@ -646,29 +670,58 @@ class Lowering:
         out = self.buf(prefix + "/out", OH, OW, cbn + trunk.C, bn_channels=cbn, need_raw=True)
         c0 = 0
         for i, t in enumerate(towers):
-            self._tower(f"{prefix}/tower_conv{i}", trunk, t, out.sl(c0, t[-1][1]))
+            self._tower(f"{prefix}/{branch.format(i)}", trunk, t, out.sl(c0, t[-1][1]))
             c0 += t[-1][1]
         self.bn_apply(out, 0, cbn)
         self.maxpool(prefix + "/MaxPool_1a_3x3", trunk, out=out.sl(cbn, trunk.C))
         return out.full()
 
-    def head(self, x: Slice, E: int) -> Slice:
-        """features (:459-468): AvgPool2D([3,3]) valid (stride = pool) -> Flatten -> Dense(no bias) -> BN."""
+    def mixed(self, prefix: str, trunk: Slice, towers, branch: str = "Branch_{}") -> Slice:
+        """Stride-1 concat block (Inception-ResNet-v2 Mixed_5a): every tower ends in a convolution + BN + ReLU and writes its
+        channel slice of one buffer; a tower may open with ("AvgPool_...",), a 3x3 / stride 1 / SAME average pool of the trunk."""
+        H, W = trunk.buf.H, trunk.buf.W
+        cm = sum(t[-1][1] for t in towers)
+        out = self.buf(prefix + "/out", H, W, cm, bn_channels=cm, need_raw=True)
+        c0 = 0
+        for i, t in enumerate(towers):
+            x = trunk
+            if len(t[0]) == 1:
+                x = self.avgpool3(f"{prefix}/{branch.format(i)}/{t[0][0]}", trunk)
+                t = t[1:]
+            self._tower(f"{prefix}/{branch.format(i)}", x, t, out.sl(c0, t[-1][1]))
+            c0 += t[-1][1]
+        self.bn_apply(out, 0, cm)
+        return out.full()
+
+    def head(self, x: Slice, E: int, dense: str = "features/logits", pool: str = "features/avgpool", out: str = "features/bn",
+             whole_map: bool = False, keep: float = 1.0) -> Slice:
+        """features (:459-468): AvgPool2D([3,3]) valid (stride = pool) -> Flatten -> Dense(no bias) -> BN.
+        ``whole_map``: pool any map size (Inception-ResNet-v2's AvgPool_1a, kernel = map); ``keep`` < 1: dropout on the pooled
+        features in training plans (the mask is a hash of seed, rank, step, image, channel: fn_dropout_fwd)."""
         H, W = x.buf.H, x.buf.W
-        if (H, W) != (3, 3):
+        if not whole_map and (H, W) != (3, 3):
             # AvgPool2D([3,3], 'valid') pools the top-left 3x3 window only and Flatten of a larger pooled map has a layout of
             # its own (hazard 11): the whole-map average of fn_avgpool_* is the reference's result for 3x3 maps exactly
             raise ValueError(f"head expects a 3x3 final map (image sizes 139..170; the reference uses 160), got {H}x{W}")
-        pooled = self.buf("features/avgpool", 1, 1, x.C)
+        pooled = self.buf(pool, 1, 1, x.C)
         self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
         self.recs.append(Rec("avgpool", None, x, pooled.full()))
-        yh = self.buf("features/logits", 1, 1, E, bn_channels=E, f32=True)
-        L = self.net._declare_layer("features/logits", x.C, x.C, E, 1, 1, 1, 0, 0, True, False, dense=True) \
-            if self.declare else self.net.layers["features/logits"]
+        if self.training and keep < 1.0:
+            dropped = self.buf(pool + "/Dropout", 1, 1, x.C)
+            self.readers[pooled.name] = self.readers.get(pooled.name, 0) + 1
+            if self.step_word is None:       # no Trainer: the plan owns its step counter (bumped by the caller after each step)
+                self.step_word = torch.zeros(1, dtype=torch.int32, device=self.net.device)
+            self.recs.append(Rec("dropout", None, pooled.full(), dropped.full(), dict(keep=float(keep))))
+            pooled = dropped
+        self.pre_logits = pooled
+        yh = self.buf(dense, 1, 1, E, bn_channels=E, f32=True)
+        L = self.net._declare_layer(dense, x.C, x.C, E, 1, 1, 1, 0, 0, True, False, dense=True) \
+            if self.declare else self.net.layers[dense]
         if self.declare:
             L.bn_off = yh.bn_off
         self.recs.append(Rec("conv", L, pooled.full(), yh.full(), dict(kind="f32")))
-        emb = self.buf("features/bn", 1, 1, E, f32=True)
+        self.head_out = out
+        emb = self.buf(out, 1, 1, E, f32=True)
         self.recs.append(Rec("head_bn", L, yh.full(), emb.full()))
         return emb.full()
 
@@ -747,7 +800,7 @@ class Lowering:
             self.fin_reps, self.fin_count = self.fin_reps.to(dev), self.fin_count.to(dev)
             self._emit(self.fwd, "bn_finalize", lib.fn_bn_finalize, _ptr(self.ws), CB, 2 * CB, _ptr(self.fin_reps), _ptr(self.fin_count),
                        _ptr(net.P, net.beta_base), _ptr(self.save_scale), _ptr(self.save_shift), _ptr(net.S_mean), _ptr(net.S_var),
-                       BN_MOMENTUM, BN_EPS, CB,
+                       net.bn_momentum, BN_EPS, CB,
                        r=[(self.ws.data_ptr() + 1, 0, CB), region(net.P, net.beta_base, net.beta_base + CB)],
                        w=[region(self.save_scale), region(self.save_shift), region(net.S_mean), region(net.S_var)])
 
@@ -864,7 +917,7 @@ class Lowering:
         elif kind == "f32":
             tgt = r.y.buf
             if L.has_bn and not self.training:       # inference: BN folded, write the embedding buffer directly
-                tgt = self.bufs["features/bn"]
+                tgt = self.bufs[self.head_out]
                 d.bias = _ptr(net.fold_bias, L.bn_off)
                 reads.append(region(net.fold_bias, L.bn_off, L.bn_off + L.cout))
             d.y = _ptr(tgt.act, r.y.c0)
@@ -934,7 +987,7 @@ class Lowering:
             return
         self._emit(self.fwd, "bn_relu_fwd:" + b.name, lib.fn_bn_relu_train_fwd, _ptr(b.raw, c0), b.C, _ptr(b.act, c0), b.C, b.M, Cc,
                    _ptr(self.ws, o), net.CB, self._replicas(b.M), 2 * net.CB, _ptr(net.P, net.beta_base + o), _ptr(self.save_scale, o),
-                   _ptr(self.save_shift, o), _ptr(net.S_mean, o), _ptr(net.S_var, o), BN_MOMENTUM, BN_EPS, 1 if r.extra["relu"] else 0, self.dt,
+                   _ptr(self.save_shift, o), _ptr(net.S_mean, o), _ptr(net.S_var, o), net.bn_momentum, BN_EPS, 1 if r.extra["relu"] else 0, self.dt,
                    r=[self._rr(r.y), (self.ws.data_ptr() + 1, o, o + Cc), region(net.P, net.beta_base + o, net.beta_base + o + Cc)],
                    w=[self._ra(r.y), region(self.save_scale, o, o + Cc), region(self.save_shift, o, o + Cc),
                       region(net.S_mean, o, o + Cc), region(net.S_var, o, o + Cc)])
@@ -954,6 +1007,19 @@ class Lowering:
         self._emit(self.fwd, "avgpool_fwd", self.net.lib.fn_avgpool_fwd, _ptr(x.buf.act), _ptr(y.buf.act), self.N, x.buf.H * x.buf.W, x.C, self.dt,
                    r=[self._ra(x)], w=[self._ra(y)])
 
+    def _fwd_avgpool3(self, r: Rec):
+        x, y = r.x, r.y
+        self._emit(self.fwd, "avgpool3x3s1_fwd", self.net.lib.fn_avgpool3x3s1_fwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.act, y.c0),
+                   y.buf.C, self.N, x.buf.H, x.buf.W, x.C, self.dt, r=[self._ra(x)], w=[self._ra(y)])
+
+    def _dropout_args(self, r: Rec):
+        return (self.N, r.x.C, r.extra["keep"], self.net.seed & 0xFFFFFFFF, self.rank, _ptr(self.step_word), self.dt)
+
+    def _fwd_dropout(self, r: Rec):
+        x, y = r.x, r.y
+        self._emit(self.fwd, "dropout_fwd", self.net.lib.fn_dropout_fwd, _ptr(x.buf.act), _ptr(y.buf.act), *self._dropout_args(r),
+                   r=[self._ra(x), region(self.step_word)], w=[self._ra(y)])
+
     def _fwd_head_bn(self, r: Rec):
         if not self.training:
             return  # folded into the Dense epilogue
@@ -961,7 +1027,7 @@ class Lowering:
         o = L.bn_off
         self._emit(self.fwd, "head_bn_fwd", net.lib.fn_head_bn_fwd, _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, net.E,
                    _ptr(net.P, net.beta_base + o), _ptr(net.S_mean, o), _ptr(net.S_var, o), _ptr(self.head_mean), _ptr(self.head_rstd), 1,
-                   BN_MOMENTUM, BN_EPS,
+                   net.bn_momentum, BN_EPS,
                    r=[self._ra(r.x), region(net.P, net.beta_base + o, net.beta_base + o + net.E)],
                    w=[self._ra(r.y), region(self.head_mean), region(self.head_rstd), region(net.S_mean, o, o + net.E),
                       region(net.S_var, o, o + net.E)])
@@ -1153,6 +1219,18 @@ class Lowering:
         assert self._grad_mode(x) == 0
         self._emit(self.bwd, "avgpool_bwd", self.net.lib.fn_avgpool_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), self.N, x.buf.H * x.buf.W, x.C, self.dt,
                    r=[self._rg(y)], w=[self._rg(x)])
+
+    def _bwd_avgpool3(self, r: Rec):
+        x, y = r.x, r.y
+        acc = self._grad_mode(x)
+        self._emit(self.bwd, "avgpool3x3s1_bwd", self.net.lib.fn_avgpool3x3s1_bwd, _ptr(y.buf.grad, y.c0), y.buf.C, _ptr(x.buf.grad, x.c0),
+                   x.buf.C, self.N, x.buf.H, x.buf.W, x.C, acc, self.dt, r=[self._rg(y)] + ([self._rg(x)] if acc else []), w=[self._rg(x)])
+
+    def _bwd_dropout(self, r: Rec):
+        x, y = r.x, r.y
+        assert self._grad_mode(x) == 0
+        self._emit(self.bwd, "dropout_bwd", self.net.lib.fn_dropout_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), *self._dropout_args(r),
+                   r=[self._rg(y), region(self.step_word)], w=[self._rg(x)])
 
     # ---- execution -----------------------------------------------------------------------------
     @staticmethod

@@ -248,7 +248,7 @@ def _streams_for(net: Network, n_streams: int) -> StreamSet:
 
 class Trainer:
     def __init__(self, net: Network, batch: int, loss: str = "triplet", alpha: float = 0.2, lr: float = 0.05, beta1: float = 0.9,
-                 beta2: float = 0.999, epsilon: float = 0.1, l2: float = L2_WEIGHT, world_size: int = 1, process_group=None,
+                 beta2: float = 0.999, epsilon: float = 0.1, l2: Optional[float] = None, world_size: int = 1, process_group=None,
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False):
         self.group_wgrad = group_wgrad
         # force_segments: a single replica runs the data-parallel step structure (backward cut at the bucket boundaries, one graph
@@ -265,6 +265,7 @@ class Trainer:
         if loss == "softmax" and net.nrof_classes is None:
             raise ValueError("softmax training needs Network(nrof_classes=...)")
         self.net, self.N, self.loss_kind, self.alpha = net, batch, loss, alpha
+        l2 = net.l2_weight if l2 is None else l2      # v1: L2_WEIGHT (Keras L2(5e-4)); v2: slim weight_decay / 2
         self.beta1, self.beta2, self.eps, self.l2 = beta1, beta2, epsilon, l2
         self.world, self.pg = world_size, process_group
         self.n_streams = n_streams
@@ -283,7 +284,13 @@ class Trainer:
             parallel.broadcast_parameters([net.P, net.S_mean, net.S_var], src=0, group=process_group)
             net.folded_valid = False
             net.refresh_packs()
-        self.plan: Lowering = net.plan(batch, training=True)
+        # dropout (Inception-ResNet-v2) draws its masks from Keras' `iterations` word: forward and backward of a step read it
+        # before the step's adam_tick, and graph replays see it advance; masks differ per data-parallel rank
+        rank = 0
+        if self.exchange:
+            import torch.distributed as dist
+            rank = dist.get_rank(process_group)
+        self.plan: Lowering = net.plan(batch, training=True, step_word=self.hyper.view(torch.int32)[4:5], rank=rank)
         self.demb = torch.zeros(batch, E, dtype=torch.float32, device=dev)
         self.dt = _lib.dtype_code(net.train_dtype)
         ebuf = self.plan.embedding.buf
@@ -567,9 +574,8 @@ class Trainer:
         ``Adam/<var>/v``, ``Adam/iter`` and the schedule position: everything ``fit`` needs to resume."""
         from . import keras_names
         net = self.net
-        rep = int(net.cfg["block8_1"]["repeat"])
         out = {k: v.numpy() for k, v in net.keras_variables(self.averaged_moving_stats()).items()}
-        table = dict((i, k) for k, i in keras_names.keras_variable_table(net.layers, rep))
+        table = dict((i, k) for k, i in net.variable_table())
         for slot, buf in (("m", self.M), ("v", self.V)):
             for key, t in net.export_keras_grads(buf).items():
                 out[keras_names.optimizer_slot_names(table[key])[0 if slot == "m" else 1]] = t.numpy()
@@ -591,10 +597,9 @@ class Trainer:
             sd = {k: z[k] for k in z.files}
         net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith("Adam/") and k != "epoch"})
         if "Adam/iter:0" in sd:
-            rep = int(net.cfg["block8_1"]["repeat"])
             for slot, buf in ((0, self.M), (1, self.V)):
                 tmp = {}
-                for k, i in keras_names.keras_variable_table(net.layers, rep):
+                for k, i in net.variable_table():
                     if i.endswith(("/moving_mean", "/moving_variance")):
                         continue
                     tmp[i] = torch.from_numpy(sd[keras_names.optimizer_slot_names(k)[slot]])

@@ -260,6 +260,15 @@ int fn_nms_greedy_batch(const double* boxes, int ld, const int32_t* order, const
                         int njobs, void* workspace, long workspace_bytes, int32_t* keep, int32_t* n_keep, void* stream);
 int fn_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int dtype, void* stream);
 int fn_avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, int dtype, void* stream);
+/* Inception-ResNet-v2: AvgPool 3x3 / stride 1 / SAME over an NHWC channel slice (ld = channel stride of the buffer); the divisor is
+ * the number of in-map taps (TF).  bwd: dx (+)= the gather of dy/taps over the covering windows (accumulate = 1 adds). */
+int fn_avgpool3x3s1_fwd(const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, int dtype, void* stream);
+int fn_avgpool3x3s1_bwd(const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C, int accumulate, int dtype,
+                        void* stream);
+/* Dropout on [N,C] (C % 8 == 0, 0 < keep < 1): y = x/keep where lowbias32-fold(seed, rank, *step, n, c) < round(keep * 2^32), else 0.
+ * step is a device int32 read by the kernel (HIP-graph replays see it advance); bwd applies the same mask to dy. */
+int fn_dropout_fwd(const void* x, void* y, int N, int C, float keep, unsigned seed, int rank, const int32_t* step, int dtype, void* stream);
+int fn_dropout_bwd(const void* dy, void* dx, int N, int C, float keep, unsigned seed, int rank, const int32_t* step, int dtype, void* stream);
 
 /* ---- residual backward for "net = act(net + scale*up)" (:145-148,199-202,254-257) ------------
  * dpre = dout * (out>0 if relu); dtrunk = dpre (or += when accumulate); dup = scale*dpre; dbias[C] += sum(dup). */
