@@ -64,7 +64,9 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         nrof_classes=nrof_classes, device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
-    trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group)
+    # loss.center_* / prelogits_norm_* (train_softmax.yaml:73-78): center loss and prelogits-norm loss on the embedding
+    trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group,
+                      **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p")})
     first_epoch = 0
     if cfg.model.checkpoint:                                      # network.load_weights(checkpoint) before fit (:68-71)
         ckpt = Path(cfg.model.checkpoint).expanduser()
@@ -89,7 +91,11 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if rank == 0:
-            log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  xent {trainer.loss_value():.4f}  lr {scheduler(epoch)}  "
+            reg = ""
+            if trainer.regularized:                               # the reference's logged names (models/*/logs/report.h5)
+                t = trainer.loss_terms()
+                reg = "".join(f"  {k} {t[k]:.4f}" for k in ("center_loss", "prelogits_norm", "loss") if t[k] is not None)
+            log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  xent {trainer.loss_value():.4f}{reg}  lr {scheduler(epoch)}  "
                 f"{cfg.batch_size * cfg.train.epoch.size / dt:.1f} img/s")
         if cfg.model.path:                                        # ModelCheckpoint(save_weights_only=True) each epoch (:74-78)
             path = Path(cfg.model.path).expanduser()
@@ -98,6 +104,11 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
             # Keras variable names and order + Adam slots, iteration count and epoch; moving statistics averaged over replicas
             trainer.save_checkpoint(path / f"{path.stem}.npz", epoch=epoch + 1)
     return net, trainer
+
+
+def _loss_key(cfg, key):
+    """cfg.loss.<key>, or the reference default when the settings tree lacks it (a Config not built by load_config)."""
+    return cfg.loss.as_dict[key] if cfg.loss.exists(key) else config_mod.DEFAULTS["loss"][key]
 
 
 def _chain_first(first, rest):

@@ -5,6 +5,8 @@
 //    counter-based hash below is shared bit-for-bit with oracle/facenet_oracle.py:hash_u32 so the
 //    selected indices can be compared exactly.
 //  * softmax cross-entropy = SparseCategoricalCrossentropy(from_logits=True), apps/train_softmax.py:91.
+//  * center loss + its center update = facenet/facenet.py:204-217 (center_loss); prelogits norm = the
+//    loss.prelogits_norm_* keys of apps/configs/train_softmax.yaml:73-78 (formula: DESIGN.md section 11).
 #include "common.h"
 #include "../../include/facenet_hip.h"
 
@@ -289,6 +291,153 @@ __global__ void loss_finish_kernel(float* loss) {
     loss[0] = reinterpret_cast<const unsigned*>(loss)[1] ? __builtin_nanf("") : v;
 }
 
+
+// ---- embedding regularisers of softmax training ------------------------------------------------------
+// terms words: [0] center loss, [1] prelogits norm (fp32 results), [2] flags (bit 0: center term invalid, bit 1: norm term
+// invalid), [3] spare, [4..5] and [6..7] the fixed-point accumulators (ACC_GRAD) of the two terms.  The finish kernel reads and
+// re-zeroes words 2..7, so one launch per step is enough and the caller zeroes the buffer only once, at allocation.
+enum { REG_FLAG = 2, REG_ACC_CENTER = 4, REG_ACC_NORM = 6 };
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// a row term goes into the fixed-point sum only when the conversion is defined (|v| < 2^(62-40)); otherwise the term's flag is set
+__device__ __forceinline__ void reg_acc_add(float* terms, int word, unsigned flag_bit, double v) {
+    if (isfinite(v) && fabs(v) < 4194304.0) acc_add<ACC_GRAD>(reinterpret_cast<acc_t*>(terms + word), (float)v);
+    else atomicOr(reinterpret_cast<unsigned*>(terms + REG_FLAG), flag_bit);
+}
+
+// One wave per row i (4 rows per 256-thread workgroup), 16-byte loads (E % 4 == 0).  a = |x| + 1e-4 is formed in fp32 (x is
+// fp32); every other quantity -- sums, the norm, both gradient terms and the update of demb -- is computed in double and demb is
+// rounded once, so demb + g is within half an ulp of the exact sum.  p == 1 and p == 2 avoid pow().
+__global__ __launch_bounds__(256) void center_loss_kernel(const float* __restrict__ x, const int* __restrict__ labels,
+                                                          const float* __restrict__ centers, float* __restrict__ demb,
+                                                          float* __restrict__ terms, float* __restrict__ xy, int ld_xy, int N, int E,
+                                                          int C, float center_factor, float norm_factor, float p) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;
+    const int lab = labels[i];
+    const bool use_c = centers != nullptr && lab >= 0 && lab < C;
+    const float* xr = x + (long)i * E;
+    const float* cr = use_c ? centers + (long)lab * E : nullptr;
+    const double pd = (double)p;
+    const int mode = p == 1.f ? 1 : (p == 2.f ? 2 : 0);
+    double sd = 0.0, sa = 0.0;
+    for (int e = 4 * lane; e < E; e += 256) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + e);
+        f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+        if (use_c) cv = *reinterpret_cast<const f32x4*>(cr + e);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double d = (double)xv[t] - (double)cv[t];
+            sd += d * d;
+            const double a = (double)(fabsf(xv[t]) + 1e-4f);
+            sa += mode == 1 ? a : (mode == 2 ? a * a : pow(a, pd));
+        }
+        if (xy) {
+            float* o = xy + (long)i * ld_xy + e;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) o[t] = xv[t];
+        }
+    }
+    sd = wave_sum_d(sd);
+    sa = wave_sum_d(sa);
+    const double n = mode == 1 ? sa : (mode == 2 ? sqrt(sa) : pow(sa, 1.0 / pd));
+    if (lane == 0) {
+        if (centers) {
+            if (use_c) reg_acc_add(terms, REG_ACC_CENTER, 1u, sd / ((double)N * (double)E));
+            else atomicOr(reinterpret_cast<unsigned*>(terms + REG_FLAG), 1u);    // a class index outside [0, C): no center to read
+        }
+        reg_acc_add(terms, REG_ACC_NORM, 2u, n / (double)N);
+        if (xy) xy[(long)i * ld_xy + E] = (float)lab;      // exact for |label| < 2^24
+    }
+    const bool g_c = use_c && center_factor != 0.f, g_n = norm_factor != 0.f;
+    if (!demb || !(g_c || g_n)) return;
+    // d/dx of factor_c * mean (x - c)^2 and of factor_n * mean_i n_i: 2 (x - c) / (N E) and sign(x) a^(p-1) n^(1-p) / N
+    const double kc = 2.0 * (double)center_factor / ((double)N * (double)E);
+    const double kn = (double)norm_factor / (double)N * (mode == 1 ? 1.0 : (mode == 2 ? 1.0 / n : pow(n, 1.0 - pd)));
+    float* dr = demb + (long)i * E;
+    for (int e = 4 * lane; e < E; e += 256) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + e);
+        f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+        if (g_c) cv = *reinterpret_cast<const f32x4*>(cr + e);
+        f32x4 dv = *reinterpret_cast<const f32x4*>(dr + e);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            double g = 0.0;
+            if (g_c) g += kc * ((double)xv[t] - (double)cv[t]);
+            if (g_n && xv[t] != 0.f) {         // sign(0) = 0: TF's gradient of abs
+                const double a = (double)(fabsf(xv[t]) + 1e-4f);
+                const double w = mode == 1 ? 1.0 : (mode == 2 ? a : pow(a, pd - 1.0));
+                g += (xv[t] > 0.f ? kn : -kn) * w;
+            }
+            dv[t] = (float)((double)dv[t] + g);
+        }
+        *reinterpret_cast<f32x4*>(dr + e) = dv;
+    }
+}
+
+__global__ void center_loss_finish_kernel(float* terms) {
+    unsigned* flags = reinterpret_cast<unsigned*>(terms + REG_FLAG);
+    acc_t* acc = reinterpret_cast<acc_t*>(terms + REG_ACC_CENTER);
+    const unsigned f = *flags;
+    terms[0] = (f & 1u) ? __builtin_nanf("") : acc_get<ACC_GRAD>(acc[0]);
+    terms[1] = (f & 2u) ? __builtin_nanf("") : acc_get<ACC_GRAD>(acc[1]);
+    *flags = 0u;
+    acc[0] = 0;
+    acc[1] = 0;
+}
+
+// facenet.py:212-213 with a fixed order for repeated labels: the workgroup of the FIRST row carrying a class owns that class and
+// walks the rows that carry it in ascending order, c <- c - k (c_old - x_j); every other workgroup leaves at once.  No atomics:
+// every center row has exactly one writer.  rows: [M][ld] fp32 = x_j (E values) followed by float(label_j).  Every rounding is
+// spelled out (no fused multiply-add) so a float32 NumPy restatement gives the same bits.
+__global__ __launch_bounds__(256) void center_update_kernel(const float* __restrict__ rows, int ld, int M, int E,
+                                                            float* __restrict__ centers, int C, float k) {
+#pragma clang fp contract(off)
+    __shared__ int s_lab[4096];
+    __shared__ int s_rows[4096];        // the rows carrying this workgroup's class, ascending
+    __shared__ int s_wcnt[4];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int j = tid; j < M; j += 256) {
+        const float v = rows[(long)j * ld + E];
+        s_lab[j] = (v >= 0.f && v < (float)C && v == floorf(v)) ? (int)v : -1;    // NaN / out of range: no class
+    }
+    __syncthreads();
+    const int y = s_lab[i];
+    int dup = 0;
+    for (int j = tid; j < i; j += 256) dup |= (s_lab[j] == y);
+    if (__syncthreads_or(dup) || y < 0) return;
+    // ordered compaction of the rows j >= i with label y (wave ballots + the counts of the waves before): the walk below then
+    // visits only them, instead of testing all M labels per element
+    int n = 0;
+    for (int base = i; base < M; base += 256) {
+        const int j = base + tid;
+        const bool hit = j < M && s_lab[j] == y;
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) s_wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = n;
+        for (int w = 0; w < wave; ++w) off += s_wcnt[w];
+        if (hit) s_rows[off + __popcll(m & ((1ull << lane) - 1ull))] = j;
+        n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        __syncthreads();
+    }
+    float* cr = centers + (long)y * E;
+    for (int e = tid; e < E; e += 256) {
+        const float c_old = cr[e];
+        float c = c_old;
+        for (int r = 0; r < n; ++r) {
+            const float t = c_old - rows[(long)s_rows[r] * ld + e];
+            const float u = k * t;
+            c = c - u;
+        }
+        cr[e] = c;
+    }
+}
 }  // namespace fn
 using namespace fn;
 
@@ -339,4 +488,28 @@ extern "C" int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_
         hipLaunchKernelGGL(softmax_xent_kernel<_Float16>, dim3(N), dim3(256), 0, st, logits, ld, labels, lacc, (unsigned short*)dlogits_lp, ld_d, dbias, N, C, grad_scale);
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(1), 0, st, loss);
     return check_launch("softmax_xent");
+}
+
+extern "C" int fn_center_loss_fwd_bwd(const float* x, const int32_t* labels, const float* centers, float* demb, float* terms, float* xy,
+                                      int ld_xy, int N, int E, int C, float center_factor, float norm_factor, float p, void* stream) {
+    FN_REQUIRE(x && labels && terms && N > 0 && E > 0 && E % 4 == 0, "center_loss: bad arguments (E must be a multiple of 4)");
+    FN_REQUIRE(((uintptr_t)x & 15) == 0 && (!demb || ((uintptr_t)demb & 15) == 0) && (!centers || ((uintptr_t)centers & 15) == 0),
+               "center_loss: x, demb and centers must be 16-byte aligned");
+    FN_REQUIRE(((uintptr_t)terms & 7) == 0, "center_loss: terms must be an 8-byte aligned fp32[8]");
+    FN_REQUIRE(!centers || C > 0, "center_loss: centers need C > 0");
+    FN_REQUIRE(!xy || ld_xy > E, "center_loss: ld_xy must be > E");
+    FN_REQUIRE(center_factor >= 0.f && norm_factor >= 0.f && p > 0.f, "center_loss: factors must be >= 0 and p > 0");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(center_loss_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, x, labels, centers, demb, terms, xy, ld_xy, N, E, C,
+                       center_factor, norm_factor, p);
+    hipLaunchKernelGGL(center_loss_finish_kernel, dim3(1), dim3(1), 0, st, terms);
+    return check_launch("center_loss");
+}
+
+extern "C" int fn_center_update(const float* rows, int ld, int M, int E, float* centers, int C, double alfa, void* stream) {
+    FN_REQUIRE(rows && centers && M > 0 && M <= 4096 && E > 0 && ld > E && C > 0, "center_update: bad arguments (M <= 4096, ld > E)");
+    FN_REQUIRE(alfa >= 0.0 && alfa <= 1.0, "center_update: alfa must be in [0, 1]");
+    const float k = (float)(1.0 - alfa);      // (1 - alfa) of facenet.py:213: a Python float, rounded to fp32 once
+    hipLaunchKernelGGL(center_update_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, rows, ld, M, E, centers, C, k);
+    return check_launch("center_update");
 }

@@ -6,6 +6,8 @@
 * ``Trainer(loss='triplet')`` is the north-star path the reference lacks (build-defined
   from arXiv 1503.03832): forward(training=True) -> l2_normalize -> triplet loss over rows laid out
   (a0,p0,n0,a1,...).  ``TripletMiner`` does the online selection in a PxK pool on device.
+* ``Trainer(loss='softmax', center_factor=..., prelogits_norm_factor=...)`` adds the reference's embedding regularisers
+  (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
 * Data parallelism restates ``tf.distribute.MirroredStrategy()`` (apps/train_softmax_tf2_gpus.py:49):
   one process per GPU, per-replica BatchNorm, gradients summed by RCCL all-reduce in backward-ordered
   buckets on a side stream (overlapped with the rest of backward), divided by the replica count
@@ -249,7 +251,8 @@ def _streams_for(net: Network, n_streams: int) -> StreamSet:
 class Trainer:
     def __init__(self, net: Network, batch: int, loss: str = "triplet", alpha: float = 0.2, lr: float = 0.05, beta1: float = 0.9,
                  beta2: float = 0.999, epsilon: float = 0.1, l2: Optional[float] = None, world_size: int = 1, process_group=None,
-                 n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False):
+                 n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
+                 center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0):
         self.group_wgrad = group_wgrad
         # force_segments: a single replica runs the data-parallel step structure (backward cut at the bucket boundaries, one graph
         # per segment, per-segment grouped weight gradients) with the all-reduce left out: what the segmentation alone costs
@@ -264,6 +267,19 @@ class Trainer:
             raise ValueError("triplet batches are laid out (a,p,n,...): batch must be a multiple of 3")
         if loss == "softmax" and net.nrof_classes is None:
             raise ValueError("softmax training needs Network(nrof_classes=...)")
+        # loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p (train_softmax.yaml:73-78)
+        if not (center_factor >= 0 and prelogits_norm_factor >= 0):
+            raise ValueError(f"center_factor and prelogits_norm_factor must be >= 0, got {center_factor}, {prelogits_norm_factor}")
+        if not 0 <= center_alfa <= 1:
+            raise ValueError(f"center_alfa must be in [0, 1], got {center_alfa}")
+        if not prelogits_norm_p > 0:
+            raise ValueError(f"prelogits_norm_p must be > 0, got {prelogits_norm_p}")
+        if loss == "triplet" and (center_factor > 0 or prelogits_norm_factor > 0):
+            raise ValueError("center loss and prelogits-norm loss need class labels: they belong to softmax training")
+        self.center_factor, self.center_alfa = float(center_factor), float(center_alfa)
+        self.prelogits_norm_factor, self.prelogits_norm_p = float(prelogits_norm_factor), float(prelogits_norm_p)
+        self.regularized = center_factor > 0 or prelogits_norm_factor > 0
+        self.centers: Optional[torch.Tensor] = None
         self.net, self.N, self.loss_kind, self.alpha = net, batch, loss, alpha
         l2 = net.l2_weight if l2 is None else l2      # v1: L2_WEIGHT (Keras L2(5e-4)); v2: slim weight_decay / 2
         self.beta1, self.beta2, self.eps, self.l2 = beta1, beta2, epsilon, l2
@@ -341,6 +357,8 @@ class Trainer:
             g.y, g.w, g.dx, g.out_f32 = _ptr(self.dlogits), _ptr(net.Wt_train, L.w_off), _ptr(self.demb), 1
             self._op(self.loss_ops, "conv_dgrad:classifier", lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
                      r=[region(self.dlogits), rwt], w=[region(self.demb)])
+            if self.regularized:
+                self._build_regularizers(Cr, rank, r_emb)
         self.plan.build_backward(self.demb)
         self.opt_ops: List[Op] = []
         self._op(self.opt_ops, "adam_tick", lib.fn_adam_tick, _ptr(self.hyper), beta1, beta2, w=[region(self.hyper)])
@@ -349,6 +367,9 @@ class Trainer:
                  r=[region(self.G), region(self.hyper)], w=[region(net.P), region(self.M), region(self.V), region(net.W_train)])
         self._op(self.opt_ops, "pack_transpose", lib.fn_pack_transpose, _ptr(net.W_train), _ptr(net.Wt_train), _ptr(net.table),
                  len(net.layers), net.max_layer_elems, self.dt, r=[region(net.W_train)], w=[region(net.Wt_train)])
+        if self.centers is not None:      # the final segment: under data parallelism it reads the gathered global batch
+            self._op(self.opt_ops, "center_update", lib.fn_center_update, _ptr(self.center_rows), E + 1, self.world * batch, E,
+                     _ptr(self.centers), self.centers.shape[0], self.center_alfa, r=[region(self.center_rows)], w=[region(self.centers)])
         n_buckets = int(os.environ.get("FACENET_DP_BUCKETS", n_buckets))      # tuning aid: gradient buckets of the data-parallel step
         self.buckets = self._make_buckets(n_buckets) if self.segmented else []
         self.comm_stream = torch.cuda.Stream(device=dev) if self.exchange else None
@@ -360,6 +381,29 @@ class Trainer:
 
     def _op(self, lst, name, fn, *args, keep=(), r=(), w=()):
         lst.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
+
+    def _build_regularizers(self, n_classes: int, rank: int, r_emb):
+        """Center loss and prelogits norm: one launch after the classifier's data gradient adds their
+        gradient into demb and reports the terms.  With center loss on it also writes this rank's (x, label) rows into
+        center_rows [world, N, E+1]; the other ranks' slots arrive by an all-reduce (SUM) of the zeroed buffer -- an exact
+        all-gather -- before the final segment's center_update."""
+        net, lib, N, E, dev = self.net, self.net.lib, self.N, self.net.E, self.net.device
+        self.reg_terms = torch.zeros(8, dtype=torch.float32, device=dev)    # zeroed once: the launch leaves its words zeroed
+        reads, writes = [r_emb, region(self.labels), region(self.demb)], [region(self.demb), region(self.reg_terms)]
+        rows, slot = None, None
+        if self.center_factor > 0:
+            self.centers = torch.zeros(n_classes, E, dtype=torch.float32, device=dev)     # tf.constant_initializer(0), not trainable
+            self.center_rows = torch.zeros(self.world, N, E + 1, dtype=torch.float32, device=dev)
+            rows, slot = self.center_rows[rank], region(self.center_rows, rank * N * (E + 1), (rank + 1) * N * (E + 1))
+            reads.append(region(self.centers))
+            writes.append(slot)
+            if self.world > 1:        # the other ranks' slots must be zero when the all-reduce sums them
+                self.pre_ops.append(Op("zero_center_rows", torch_op(lambda: self.center_rows.zero_()), (),
+                                       writes=(region(self.center_rows),)))
+        self._op(self.loss_ops, "center_loss", lib.fn_center_loss_fwd_bwd, _ptr(self.emb), _ptr(self.labels),
+                 None if self.centers is None else _ptr(self.centers), _ptr(self.demb), _ptr(self.reg_terms),
+                 None if rows is None else _ptr(rows), E + 1, N, E, n_classes, self.center_factor, self.prelogits_norm_factor,
+                 self.prelogits_norm_p, r=reads, w=writes)
 
     def _cls_desc(self, L):
         d = _lib.ConvDesc()
@@ -457,6 +501,10 @@ class Trainer:
             ev.record(cur)
             self.comm_stream.wait_event(ev)
             with torch.cuda.stream(self.comm_stream):
+                if i == 0 and self.centers is not None and self.world > 1:
+                    # the head segment wrote this rank's center-loss rows: gather the global batch for center_update
+                    import torch.distributed as dist
+                    dist.all_reduce(self.center_rows, op=dist.ReduceOp.SUM, group=self.pg)
                 if prof is not None:
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record(self.comm_stream)
@@ -518,10 +566,11 @@ class Trainer:
         # restored around it, so capture() followed by n steps equals n eager steps (Adam's t, the moving statistics and the
         # parameters are untouched; the reference's fit() has no uncounted step either).
         net = self.net
-        saved = [t.clone() for t in (net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper)]
+        state = (net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper) + (() if self.centers is None else (self.centers,))
+        saved = [t.clone() for t in state]
         self.step_eager()           # warm-up: first-call attribute set-up, allocator
         torch.cuda.synchronize(net.device)
-        for t, s in zip((net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper), saved):
+        for t, s in zip(state, saved):
             t.copy_(s)
         net.folded_valid = False
         net.refresh_packs()
@@ -582,6 +631,8 @@ class Trainer:
         out["Adam/iter:0"] = np.asarray(self.iterations, dtype=np.int64)
         out["Adam/learning_rate:0"] = np.asarray(self.hyper[0].item(), dtype=np.float32)
         out["epoch"] = np.asarray(int(epoch), dtype=np.int64)
+        if self.centers is not None:
+            out["centers:0"] = self.centers.cpu().numpy()      # the TF1 variable of facenet.py:208 (identical on every replica)
         return out
 
     def save_checkpoint(self, path, epoch: int = 0):
@@ -596,6 +647,14 @@ class Trainer:
         with np.load(path, allow_pickle=False) as z:
             sd = {k: z[k] for k in z.files}
         net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith("Adam/") and k != "epoch"})
+        if self.centers is not None:
+            if "centers:0" in sd:
+                c = np.asarray(sd["centers:0"], dtype=np.float32)
+                if c.shape != tuple(self.centers.shape):
+                    raise ValueError(f"checkpoint centers:0 has shape {c.shape}, this trainer's centers are {tuple(self.centers.shape)}")
+                self.centers.copy_(torch.from_numpy(c))
+            else:
+                self.centers.zero_()                            # a checkpoint from a run without center loss
         if "Adam/iter:0" in sd:
             for slot, buf in ((0, self.M), (1, self.V)):
                 tmp = {}
@@ -633,7 +692,26 @@ class Trainer:
         self.hyper[0:1].fill_(float(lr))     # device write: visible to the next graph replay
 
     def loss_value(self) -> float:
+        """The cross-entropy (softmax) or triplet loss of the last step, without the regularisers (see loss_terms)."""
         return float(self.loss[0].item())
+
+    def loss_terms(self) -> Dict[str, Optional[float]]:
+        """The last step's terms under the names the reference logged: ``xent``, ``center_loss``, ``prelogits_norm`` and their
+        weighted sum ``loss`` (xent + center_factor * center_loss + prelogits_norm_factor * prelogits_norm).  A term that is
+        switched off is None; the prelogits norm is reported whenever a regulariser is on, even at factor 0."""
+        xent = self.loss_value()
+        center = norm = None
+        if self.regularized:
+            t = self.reg_terms[:2].cpu().tolist()
+            norm = float(t[1])
+            if self.centers is not None:
+                center = float(t[0])
+        total = xent
+        if center is not None:
+            total += self.center_factor * center
+        if self.prelogits_norm_factor > 0:
+            total += self.prelogits_norm_factor * norm
+        return {"xent": xent, "center_loss": center, "prelogits_norm": norm, "loss": total}
 
 
 class TripletMiner:

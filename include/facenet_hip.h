@@ -310,6 +310,23 @@ int fn_confidence_counts(const float* emb, const int32_t* cls_start, int C, int 
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
                             int C, float grad_scale, int dtype, void* stream);
 
+/* ---- embedding regularisers of softmax training ------------------------------------------------------
+ * fn_center_loss_fwd_bwd: center loss of facenet/facenet.py:204-217 (center_loss) and the prelogits-norm loss named by
+ * loss.prelogits_norm_factor / prelogits_norm_p of apps/configs/train_softmax.yaml:73-78, one launch (+ a one-thread finish).
+ * x fp32 [N,E] (E % 4 == 0; x, demb, centers 16-byte aligned), labels int32 [N], centers fp32 [C,E] or NULL (no center term).
+ *   terms: fp32[8], 8-byte aligned, ZEROED ONCE by the caller (every call leaves words 2..7 zeroed again).  word 0 receives
+ *   center_loss = mean_{i,e} (x - centers[label])^2 (unset without centers; NaN for a non-finite term / a label outside [0, C)),
+ *   word 1 prelogits_norm = mean_i (sum_e (|x|+1e-4)^p)^(1/p) (NaN for a non-finite term).
+ *   demb (optional) fp32 [N,E] += center_factor * 2 (x - c)/(N E) + norm_factor * sign(x) a^(p-1) n_i^(1-p) / N; a term whose
+ *   factor is 0 adds nothing.  xy (optional) [N][ld_xy] receives x (E values) and float(label) at column E: the rows
+ *   fn_center_update reads.
+ * fn_center_update: facenet.py:212-213 (scatter_sub of (1 - alfa)(centers[label] - x)) in a fixed order: per class, the rows that
+ *   carry it in ascending row order, c <- c - k (c_old - x_j), k = float(1 - alfa).  rows [M][ld] as written by the above (M <= 4096;
+ *   under data parallelism the gathered global batch in rank order); rows whose label is not an integer in [0, C) are skipped. */
+int fn_center_loss_fwd_bwd(const float* x, const int32_t* labels, const float* centers, float* demb, float* terms, float* xy, int ld_xy,
+                           int N, int E, int C, float center_factor, float norm_factor, float p, void* stream);
+int fn_center_update(const float* rows, int ld, int M, int E, float* centers, int C, double alfa, void* stream);
+
 /* ---- optimiser: tf.keras.optimizers.Adam(epsilon=0.1) apps/train_softmax.py:92 + Keras L2(5e-4) (:65) ----
  * hyper = device word[8] {lr, beta1^t, beta2^t, grad_scale, t (int32: Keras' `iterations`), 3 spare}; fn_adam_tick advances t and
  * re-derives the beta powers from it on the device (graph replay safe; t survives past the fp32 underflow of beta1^t).
