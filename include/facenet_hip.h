@@ -327,6 +327,32 @@ int fn_center_loss_fwd_bwd(const float* x, const int32_t* labels, const float* c
                            int N, int E, int C, float center_factor, float norm_factor, float p, void* stream);
 int fn_center_update(const float* rows, int ld, int M, int E, float* centers, int C, double alfa, void* stream);
 
+/* ---- face-to-face pair classifiers ---------------------------------------------------------------------
+ * facenet/faceclass.py:8-118: d(x, y) = 2 (1 - x.y / (|x| |y|)) + theta (2 (|x| - |y|) / (|x| + |y|))^2 (mode 0, distance
+ * classifier) or 2 (1 - x.y) (mode 1, normalized classifier); logits = alpha (threshold - d); predict = d < threshold.
+ * Tables fp32 [n][E], E % 4 == 0, 16-byte aligned.  params: device fp32[4] = {alpha, threshold, theta, 0}, read on the device
+ * (graph replays see the optimiser's updates).  norms = fn_f2f_row_norms of the same table; NULL allowed in mode 1 only.  The
+ * three pair entry points share one per-pair distance function: their distances agree bit for bit.
+ * fn_f2f_row_norms: norms[r] = |x_r| (fp64 sum of squares, rounded once).
+ * fn_f2f_pair_loss_fwd_bwd: apps/train_classifier.py:60-84 (binary_cross_entropy_loss) + its gradient.  Batch row b is table
+ *   row rows[b] (device int32 [P K], grouped by class: z = (a / K == b / K)); pairs a < b; weighted_cross_entropy_with_logits with
+ *   pos_weight q.  loss: fp32[1] = mean over the pairs; grad: fp32[4] = dL/d{alpha, threshold, theta, 0} (theta's is 0 in mode 1),
+ *   the g of fn_adam_keras with n = 4.  ws: fp64 workspace of >= 4 T doubles, T = nt (nt + 1) / 2, nt = ceil(P K / 64) (one slot
+ *   per upper-triangle 64 x 64 tile, summed in tile order: same bits every run; a NaN embedding gives a NaN loss and gradient).
+ *   An index outside [0, n_rows) reads as a NaN row.
+ * fn_f2f_pair_counts: apps/train_classifier.py:27-39 (ConfusionMatrix: classifier.predict for every class pair).  Class c =
+ *   table rows cls_start[c] .. cls_start[c+1] (device int32 [C+1]); counts int64 [C (C+1) / 2], slot i (i+1)/2 + k for k <= i,
+ *   receives #(d < threshold) over the whole n_i x n_k rectangle (the whole square, diagonal included, for k == i).
+ * fn_f2f_distance: faceclass.py:45-77 / :102-110 (distance) or :23-27 (__call__, logits != 0): out fp32 [N, M] for x [N, E],
+ *   y [M, E] (y == x for the reference's y=None). */
+int fn_f2f_row_norms(const float* x, int n, int E, float* norms, void* stream);
+int fn_f2f_pair_loss_fwd_bwd(const float* table, const float* norms, int n_rows, const int32_t* rows, int P, int K, int E, int mode,
+                             float q, const float* params, float* loss, float* grad, double* ws, long ws_len, void* stream);
+int fn_f2f_pair_counts(const float* table, const float* norms, const int32_t* cls_start, int C, int E, int mode, const float* params,
+                       int64_t* counts, void* stream);
+int fn_f2f_distance(const float* x, const float* nx, int N, const float* y, const float* ny, int M, int E, int mode, const float* params,
+                    int logits, float* out, void* stream);
+
 /* ---- optimiser: tf.keras.optimizers.Adam(epsilon=0.1) apps/train_softmax.py:92 + Keras L2(5e-4) (:65) ----
  * hyper = device word[8] {lr, beta1^t, beta2^t, grad_scale, t (int32: Keras' `iterations`), 3 spare}; fn_adam_tick advances t and
  * re-derives the beta powers from it on the device (graph replay safe; t survives past the fp32 underflow of beta1^t).
