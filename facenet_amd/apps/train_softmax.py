@@ -106,6 +106,22 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     return net, trainer
 
 
+def dataset_batches(cfg, rank: int = 0, world: int = 1, log=print, **kw):
+    """apps/train_softmax.py:28-47: (Database of cfg.dataset.path, this rank's endless shuffled batch pipeline).  The image.random_*
+    keys (train_softmax.yaml:85-91) augment the batches, drawn from a generator seeded by seed + rank; rank 0 logs them once."""
+    from facenet_amd import dataset
+    loader = dataset.ImageLoader(config=cfg.image)
+    train_dbase = dataset.Database(cfg.dataset)
+    augment = dataset.Augmentation.from_config(cfg.image, cfg.seed + rank)
+    if augment is not None and rank == 0:
+        log(f"augmentation: {augment}")
+    np.random.seed(cfg.seed + rank)                               # every replica walks its own permutation of the data set
+    kw.setdefault("processes", True)
+    batches = train_dbase.tf_dataset_api(loader=loader, batch_size=cfg.batch_size // world, repeat=True, buffer_size=10,
+                                         augment=augment, **kw)
+    return train_dbase, batches
+
+
 def _loss_key(cfg, key):
     """cfg.loss.<key>, or the reference default when the settings tree lacks it (a Config not built by load_config)."""
     return cfg.loss.as_dict[key] if cfg.loss.exists(key) else config_mod.DEFAULTS["loss"][key]
@@ -123,12 +139,8 @@ def main(**options):
     cfg = config_mod.load_config(options["config"])
     rank, world, pg, device = init_distributed()                  # python -m torch.distributed.run --nproc-per-node N -m facenet_amd.apps.train_softmax
     kw = dict(device=device, world_size=world, process_group=pg, rank=rank)
-    if cfg.dataset.path:                                          # apps/train_softmax.py:28-47
-        from facenet_amd import dataset
-        loader = dataset.ImageLoader(config=cfg.image)
-        train_dbase = dataset.Database(cfg.dataset)
-        np.random.seed(cfg.seed + rank)                           # every replica walks its own permutation of the data set
-        batches = train_dbase.tf_dataset_api(loader=loader, batch_size=cfg.batch_size // world, repeat=True, buffer_size=10, processes=True)
+    if cfg.dataset.path:
+        train_dbase, batches = dataset_batches(cfg, rank, world)
         train_softmax(cfg, train_dbase.nrof_classes, batches, **kw)
     else:
         train_softmax(cfg, options["nrof_classes"], **kw)

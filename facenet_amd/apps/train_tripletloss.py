@@ -59,15 +59,25 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
     return net, trainer
 
 
+def dataset_pools(cfg, log=print, **kw):
+    """P x K batches from cfg.dataset.path: the reference's equal-batches sampler (dataset.py:46-101), 20 classes x 5 images.
+    The image.random_* keys (train_softmax.yaml:85-91) augment them, drawn from a generator seeded by cfg.seed; logged once."""
+    from facenet_amd import dataset
+    loader = dataset.ImageLoader(config=cfg.image)
+    dbase = dataset.Database(cfg.dataset)
+    augment = dataset.Augmentation.from_config(cfg.image, cfg.seed)
+    if augment is not None:
+        log(f"augmentation: {augment}")
+    kw.setdefault("processes", True)
+    return dataset.pipeline_with_equal_batches(loader, dbase.classes, cfg, augment=augment, **kw)
+
+
 @click.command()
 @click.option("--config", default=None, type=Path, help="Path to yaml config file with used options of the application.")
 def main(**options):
     cfg = config_mod.load_config(options["config"])
-    if cfg.dataset.path:      # P x K batches from disk: the reference's equal-batches sampler (dataset.py:46-101), 20 classes x 5 images
-        from facenet_amd import dataset
-        loader = dataset.ImageLoader(config=cfg.image)
-        dbase = dataset.Database(cfg.dataset)
-        pipe = dataset.pipeline_with_equal_batches(loader, dbase.classes, cfg, processes=True)
+    if cfg.dataset.path:
+        pipe = dataset_pools(cfg)
         train_tripletloss(cfg, people_per_batch=cfg.nrof_classes_per_batch, images_per_person=cfg.nrof_examples_per_class,
                           pools=(images for images, _ in pipe))
     else:

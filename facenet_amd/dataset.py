@@ -4,8 +4,9 @@ Directory-per-class listing (`ImageClass`, `Database`), the shuffled batch itera
 identity sampler (`pipeline_with_equal_batches`) keep the reference's names, attributes and errors.  What changes is
 where the pixels are handled: a thread pool decodes files to ragged HWC uint8 arrays, a batch is packed back to back
 into pinned host memory, copied on a side stream and centre-cropped / zero-padded on the GPU
-(`fn_crop_or_pad_u8` = tf.image.resize_with_crop_or_pad), so what reaches the step is the uint8 NHWC batch its first
-kernel (`fn_image_normalize`) reads.  Batches are prefetched `prefetch` deep; the consumer's stream waits on an event.
+(`fn_crop_or_pad_u8` = tf.image.resize_with_crop_or_pad) -- or, for training with an `Augmentation`, randomly rotated,
+cropped and flipped in the same single launch (`fn_augment_u8`) -- so what reaches the step is the
+uint8 NHWC batch its first kernel (`fn_image_normalize`) reads.  Batches are prefetched `prefetch` deep; the consumer's stream waits on an event.
 
 Not carried over: the `h5file` validity filter (h5py is not in this image: a config that
 sets it raises) and tqdm/loguru progress output.
@@ -40,12 +41,11 @@ class ImageLoader:
         return crop_or_pad_batch([self.decode(path)], self.height)[0]
 
 
-def crop_or_pad_batch(arrays, size: int, device="cuda", stream=None, staging=None) -> torch.Tensor:
-    """Ragged list of HWC uint8 arrays -> uint8 [N, size, size, 3] on the device (one H2D copy + one launch)."""
-    lib = _lib.load()
+def _pack_ragged(arrays, staging, extra: int = 0):
+    """Pack a ragged list of HWC uint8 arrays into (pinned) host staging: int64 byte offsets, int32 (h, w) pairs, `extra`
+    bytes for the caller, then the pixels back to back.  Returns (staging, meta = bytes in front of the pixels, total pixel
+    bytes)."""
     n = len(arrays)
-    if n == 0:
-        return torch.empty(0, size, size, 3, dtype=torch.uint8, device=device)
     hw = np.empty((n, 2), np.int32)
     off = np.empty(n, np.int64)
     total = 0
@@ -55,15 +55,25 @@ def crop_or_pad_batch(arrays, size: int, device="cuda", stream=None, staging=Non
         hw[i] = a.shape[:2]
         off[i] = total
         total += a.size
-    meta = 8 * n + 8 * n                                   # offsets (i64) then hw (2 x i32) in front of the pixels
+    meta = 8 * n + 8 * n + extra                           # offsets (i64) then hw (2 x i32) in front of the pixels
     if staging is None or staging.numel() < meta + total:
         staging = torch.empty(meta + total, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else \
             torch.empty(meta + total, dtype=torch.uint8)
     host = staging.numpy()
     host[:8 * n] = off.view(np.uint8)
-    host[8 * n:meta] = hw.reshape(-1).view(np.uint8)
+    host[8 * n:16 * n] = hw.reshape(-1).view(np.uint8)
     for i, a in enumerate(arrays):
         host[meta + off[i]:meta + off[i] + a.size] = a.reshape(-1)
+    return staging, meta, total
+
+
+def crop_or_pad_batch(arrays, size: int, device="cuda", stream=None, staging=None) -> torch.Tensor:
+    """Ragged list of HWC uint8 arrays -> uint8 [N, size, size, 3] on the device (one H2D copy + one launch)."""
+    lib = _lib.load()
+    n = len(arrays)
+    if n == 0:
+        return torch.empty(0, size, size, 3, dtype=torch.uint8, device=device)
+    staging, meta, total = _pack_ragged(arrays, staging)
     st = stream if stream is not None else torch.cuda.current_stream()
     with torch.cuda.stream(st):
         dev = staging[:meta + total].to(device, non_blocking=True)
@@ -71,6 +81,86 @@ def crop_or_pad_batch(arrays, size: int, device="cuda", stream=None, staging=Non
         _lib.check(lib.fn_crop_or_pad_u8(dev.data_ptr() + meta, dev.data_ptr(), dev.data_ptr() + 8 * n, out.data_ptr(), n, size,
                                          st.cuda_stream))
     out._staging = staging          # kept alive (and reusable) until the batch is dropped
+    return out
+
+
+# ---- training-time augmentation (image.random_crop / random_flip / random_rotate) ----------------------
+AUGMENT_PARAM = np.dtype([("y0", "<i4"), ("x0", "<i4"), ("flip", "<i4"), ("cos", "<f4"), ("sin", "<f4")])   # fn_augment_param
+AUGMENT_DRAW = np.dtype([("theta", "<f8"), ("ry", "<i8"), ("rx", "<i8"), ("flip", "?")])
+AUGMENT_KEYS = ("random_crop", "random_flip", "random_rotate")
+
+
+class Augmentation:
+    """The three augmentation switches of the reference's training config (apps/configs/train_softmax.yaml:85-91), which the
+    reference documents but never reads.  Owns a np.random.Generator seeded by `seed`; `draw(n)` takes the next n per-image
+    tuples (theta, r_y, r_x, flip) from it.  Every image consumes four doubles of Generator.random, whatever keys are on:
+    theta = 20 u0 - 10 degrees, r_y = floor(2^31 u1), r_x = floor(2^31 u2), flip = u3 < 1/2; a key that is off cancels its
+    own effect (theta 0, centre offsets (r = -1), no flip).  Turning one key on therefore leaves the others' draws alone."""
+
+    MAX_DEGREES = 10.0
+
+    def __init__(self, random_crop: bool = False, random_flip: bool = False, random_rotate: bool = False, seed: int = 0):
+        self.random_crop, self.random_flip, self.random_rotate = bool(random_crop), bool(random_flip), bool(random_rotate)
+        self.seed = seed
+        self.rng = np.random.default_rng(seed)
+
+    @classmethod
+    def from_config(cls, image_cfg, seed: int):
+        """`cfg.image` -> Augmentation, or None when every key is off or missing (the pipeline then runs the plain crop)."""
+        keys = {k: bool(getattr(image_cfg, k)) for k in AUGMENT_KEYS}
+        return cls(**keys, seed=seed) if any(keys.values()) else None
+
+    def __repr__(self):
+        on = [k for k in AUGMENT_KEYS if getattr(self, k)]
+        return f"Augmentation({', '.join(on) or 'none'}; seed {self.seed})"
+
+    def draw(self, n: int) -> np.ndarray:
+        u = self.rng.random((n, 4))
+        d = np.empty(n, AUGMENT_DRAW)
+        d["theta"] = (20.0 * u[:, 0] - self.MAX_DEGREES) if self.random_rotate else 0.0
+        d["ry"] = np.floor(u[:, 1] * 2.0 ** 31) if self.random_crop else -1
+        d["rx"] = np.floor(u[:, 2] * 2.0 ** 31) if self.random_crop else -1
+        d["flip"] = (u[:, 3] < 0.5) & self.random_flip
+        return d
+
+
+def augment_params(draws: np.ndarray, hw, size: int) -> np.ndarray:
+    """Resolve draws against the decoded sources' (h, w): one fn_augment_param record per image.  Per axis, a source no larger
+    than `size` is centred with zero padding (offset -((size - h) // 2)); a larger one is cropped at r % (h - size + 1), or at
+    the centre (h - size) // 2 when the draw is -1 (random_crop off).  cos / sin are computed in float64 and stored as float32."""
+    hw = np.asarray(hw, np.int64).reshape(-1, 2)
+    if len(hw) != len(draws):
+        raise ValueError(f"{len(draws)} draws for {len(hw)} images")
+    p = np.zeros(len(draws), AUGMENT_PARAM)
+    for axis, (field, r) in enumerate((("y0", draws["ry"]), ("x0", draws["rx"]))):
+        over = hw[:, axis] - size
+        crop = np.where(r >= 0, r % np.maximum(over + 1, 1), over // 2)
+        p[field] = np.where(over > 0, crop, -((size - hw[:, axis]) // 2))
+    p["flip"] = draws["flip"]
+    rad = np.deg2rad(draws["theta"])
+    p["cos"], p["sin"] = np.cos(rad), np.sin(rad)
+    return p
+
+
+def augment_batch(arrays, size: int, params: np.ndarray, device="cuda", stream=None, staging=None) -> torch.Tensor:
+    """crop_or_pad_batch with per-image augmentation records (AUGMENT_PARAM, e.g. from augment_params): ragged HWC uint8 arrays
+    -> uint8 [N, size, size, 3] on the device through fn_augment_u8 (one H2D copy + one launch)."""
+    lib = _lib.load()
+    n = len(arrays)
+    params = np.ascontiguousarray(params)
+    if params.dtype != AUGMENT_PARAM or params.shape != (n,):
+        raise ValueError(f"expected {n} records of dtype AUGMENT_PARAM, got {params.dtype} {params.shape}")
+    if n == 0:
+        return torch.empty(0, size, size, 3, dtype=torch.uint8, device=device)
+    staging, meta, total = _pack_ragged(arrays, staging, extra=params.nbytes)
+    staging.numpy()[16 * n:meta] = params.view(np.uint8)
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        dev = staging[:meta + total].to(device, non_blocking=True)
+        out = torch.empty(n, size, size, 3, dtype=torch.uint8, device=device)
+        _lib.check(lib.fn_augment_u8(dev.data_ptr() + meta, dev.data_ptr(), dev.data_ptr() + 8 * n, dev.data_ptr() + 16 * n,
+                                     out.data_ptr(), n, size, st.cuda_stream))
+    out._staging = staging
     return out
 
 
@@ -158,8 +248,8 @@ class Database:
     def nrof_images_per_class(self):
         return [cls.nrof_images for cls in self.classes]
 
-    def tf_dataset_api(self, loader, batch_size, buffer_size=None, repeat=False, **kw):
-        return tf_dataset_api(self.files, self.labels, loader, batch_size, buffer_size=buffer_size, repeat=repeat, **kw)
+    def tf_dataset_api(self, loader, batch_size, buffer_size=None, repeat=False, augment=None, **kw):
+        return tf_dataset_api(self.files, self.labels, loader, batch_size, buffer_size=buffer_size, repeat=repeat, augment=augment, **kw)
 
 
 class BatchPipeline:
@@ -168,13 +258,17 @@ class BatchPipeline:
     `plan()` yields (files, labels) per batch; decode runs in `workers` threads -- or, with `processes=True`, in that
     many spawned worker processes (PIL decode holds the GIL for part of its work; processes scale with the cores) --
     `prefetch` batches are in flight, the H2D copy and the crop/pad launch go to a side stream and the consumer's current
-    stream waits on the batch's event.  Worker processes never touch the GPU (they import facenet_amd._decode only)."""
+    stream waits on the batch's event.  Worker processes never touch the GPU (they import facenet_amd._decode only).
+
+    With an `augment` (Augmentation), every batch takes its per-image draws when its plan is pulled (in the parent, in plan
+    order, so the batches depend on the seed and the file order only), resolves them once the decoded shapes are known and
+    launches fn_augment_u8 instead of fn_crop_or_pad_u8.  With augment=None nothing changes."""
 
     CHUNK = 10      # files per worker task in process mode
 
     def __init__(self, plan, loader: ImageLoader, cardinality=None, workers=8, prefetch=2, device="cuda", processes=False,
-                 max_image_bytes: int = 300 * 300 * 3):
-        self._plan, self.loader, self._card = plan, loader, cardinality
+                 max_image_bytes: int = 300 * 300 * 3, augment: Augmentation = None):
+        self._plan, self.loader, self._card, self.augment = plan, loader, cardinality, augment
         self.workers, self.prefetch, self.device, self.processes = workers, max(1, prefetch), device, processes
         self.max_image_bytes = (int(max_image_bytes) + 15) // 16 * 16
         self._pool = None
@@ -234,12 +328,12 @@ class BatchPipeline:
         lib = _lib.load()
         pool = self._executor()
         side = torch.cuda.Stream(device=self.device)
-        stride, size = self.max_image_bytes, self.loader.height
+        size = self.loader.height
         pending, free = deque(), list(range(len(self._slots)))
         plan = iter(self._plan())
 
         def submit():
-            nonlocal stride
+            # a local stride: the batch being consumed keeps the stride it was decoded with, even when an earlier batch grew it
             try:
                 files, labels = next(plan)
             except StopIteration:
@@ -254,7 +348,8 @@ class BatchPipeline:
                 free.remove(k)
             name = self._slots[k]["shm"].name
             futs = [pool.submit(_decode_into, name, stride, i, files[i:i + self.CHUNK]) for i in range(0, len(files), self.CHUNK)]
-            pending.append((futs, labels, k, len(files), stride))
+            draws = self.augment.draw(len(files)) if self.augment is not None else None
+            pending.append((futs, labels, k, len(files), stride, draws))
             return True
 
         try:
@@ -262,7 +357,7 @@ class BatchPipeline:
                 if not submit():
                     break
             while pending:
-                futs, labels, k, n, stride = pending.popleft()
+                futs, labels, k, n, stride, draws = pending.popleft()
                 res = [r for f in futs for r in f.result()]
                 submit()
                 slot = self._slots[k]
@@ -272,7 +367,10 @@ class BatchPipeline:
                     arrays = [arr if arr is not None else
                               np.frombuffer(slot["shm"].buf, np.uint8, count=h * w * 3, offset=i * stride).reshape(h, w, 3).copy()
                               for i, (h, w, arr) in enumerate(res)]
-                    images = crop_or_pad_batch(arrays, size, self.device, side)
+                    if draws is None:
+                        images = crop_or_pad_batch(arrays, size, self.device, side)
+                    else:
+                        images = augment_batch(arrays, size, augment_params(draws, [a.shape[:2] for a in arrays], size), self.device, side)
                     del images._staging
                     with torch.cuda.stream(side):
                         lab = torch.as_tensor(np.asarray(labels, np.int64)).to(self.device)
@@ -284,8 +382,14 @@ class BatchPipeline:
                         dev = slot["tensor"][:n * stride].to(self.device, non_blocking=slot["pinned"])
                         d_hw, d_off = hw.to(self.device), off.to(self.device)
                         images = torch.empty(n, size, size, 3, dtype=torch.uint8, device=self.device)
-                        _lib.check(lib.fn_crop_or_pad_u8(dev.data_ptr(), d_off.data_ptr(), d_hw.data_ptr(), images.data_ptr(), n, size,
-                                                         side.cuda_stream))
+                        if draws is None:
+                            _lib.check(lib.fn_crop_or_pad_u8(dev.data_ptr(), d_off.data_ptr(), d_hw.data_ptr(), images.data_ptr(), n, size,
+                                                             side.cuda_stream))
+                        else:
+                            params = augment_params(draws, hw.numpy(), size)
+                            d_prm = torch.from_numpy(params.view(np.uint8)).to(self.device)
+                            _lib.check(lib.fn_augment_u8(dev.data_ptr(), d_off.data_ptr(), d_hw.data_ptr(), d_prm.data_ptr(), images.data_ptr(),
+                                                         n, size, side.cuda_stream))
                         lab = torch.as_tensor(np.asarray(labels, np.int64)).to(self.device)
                 done = torch.cuda.Event()
                 done.record(side)
@@ -319,7 +423,8 @@ class BatchPipeline:
                 futs = [pool.submit(_decode_many, files[i:i + self.CHUNK]) for i in range(0, len(files), self.CHUNK)]
             else:
                 futs = [pool.submit(self.loader.decode, f) for f in files]
-            pending.append((futs, labels))
+            draws = self.augment.draw(len(files)) if self.augment is not None else None
+            pending.append((futs, labels, draws))
             return True
 
         try:
@@ -327,13 +432,17 @@ class BatchPipeline:
                 if not submit():
                     break
             while pending:
-                futs, labels = pending.popleft()
+                futs, labels, draws = pending.popleft()
                 arrays = [a for f in futs for a in f.result()] if decode_many else [f.result() for f in futs]
                 submit()
-                need = sum(a.size for a in arrays) + 16 * len(arrays)
+                need = sum(a.size for a in arrays) + (16 if draws is None else 16 + AUGMENT_PARAM.itemsize) * len(arrays)
                 k = next((i for i, s in enumerate(free) if s.numel() >= need), None)
                 staging = free.pop(k) if k is not None else None
-                images = crop_or_pad_batch(arrays, self.loader.height, self.device, side, staging)
+                if draws is None:
+                    images = crop_or_pad_batch(arrays, self.loader.height, self.device, side, staging)
+                else:
+                    params = augment_params(draws, [a.shape[:2] for a in arrays], self.loader.height)
+                    images = augment_batch(arrays, self.loader.height, params, self.device, side, staging)
                 with torch.cuda.stream(side):
                     lab = torch.as_tensor(np.asarray(labels, np.int64)).to(self.device, non_blocking=True)
                 done = torch.cuda.Event()
@@ -346,16 +455,17 @@ class BatchPipeline:
                 del images._staging
                 yield images, lab
         finally:
-            for futs, _ in pending:
+            for futs, *_ in pending:
                 for f in futs:
                     f.cancel()
 
 
-def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=False, **kw):
+def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=False, augment=None, **kw):
     """dataset.py:15-43: zip(files, labels) -> optional shuffle -> optional repeat -> batch -> prefetch.  With a
     `buffer_size` the reference shuffles once globally and then through a buffer_size*batch_size window, reshuffled
     every iteration; here every epoch is a fresh full permutation (the window's limit case).  `repeat` comes before
-    `batch` as in the reference, so a repeating stream has full batches that span epochs and only a finite one ends short."""
+    `batch` as in the reference, so a repeating stream has full batches that span epochs and only a finite one ends short.
+    `augment`: an Augmentation for training batches (BatchPipeline), None for the plain centre crop / pad."""
     files, labels = list(files), list(np.asarray(labels).tolist())
     if len(files) != len(labels):
         raise ValueError("files and labels differ in length")
@@ -377,13 +487,13 @@ def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=F
                 return
 
     card = None if repeat else (n + batch_size - 1) // batch_size
-    return BatchPipeline(plan, loader, card, **kw)
+    return BatchPipeline(plan, loader, card, augment=augment, **kw)
 
 
-def pipeline_with_equal_batches(loader, classes, config, **kw):
+def pipeline_with_equal_batches(loader, classes, config, augment=None, **kw):
     """dataset.py:46-101: endless P x K batches, 20 random classes x 5 random files each (the reference overwrites the
     two config values the same way, :61-62); labels are class indexes.  Raises ValueError (from random.sample) when there
-    are fewer classes / files than asked for, as the reference's generator does."""
+    are fewer classes / files than asked for, as the reference's generator does.  `augment` as for tf_dataset_api."""
     config.nrof_classes_per_batch = 20
     config.nrof_examples_per_class = 5
     for idx, _class in enumerate(classes):
@@ -397,4 +507,4 @@ def pipeline_with_equal_batches(loader, classes, config, **kw):
                 _indexes += [cls.index] * config.nrof_examples_per_class
             yield _files, _indexes
 
-    return BatchPipeline(plan, loader, None, **kw)
+    return BatchPipeline(plan, loader, None, augment=augment, **kw)

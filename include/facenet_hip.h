@@ -189,6 +189,22 @@ int fn_image_resize_bilinear(const void* img, int src_is_f32, float* out, int N,
  * (offset max((h-S)//2, 0)) and centre zero-pad (offset max((S-h)//2, 0)) to dst u8 [N,S,S,3].  Sizes are not checked against
  * the src allocation: the caller owns the packing. */
 int fn_crop_or_pad_u8(const uint8_t* src, const long long* offsets, const int32_t* hw, uint8_t* dst, int N, int S, void* stream);
+/* Training-time augmentation (image.random_rotate / random_crop / random_flip), one record per image:
+ *   y0, x0   signed offset of the S x S window in the rotated image R (R has the source's size h x w): C[y][x] = R[y+y0][x+x0]
+ *            where that lies inside R, else 0.  >= 0 crops at that offset, < 0 zero-pads by -y0 / -x0.
+ *   flip     non-zero: out[y][x] = C[y][S-1-x]
+ *   cos_t, sin_t  of the rotation angle.  R[y][x] is the bilinear sample (zero outside the source) of the source at
+ *            sx = c*u - s*v + w/2 - 0.5, sy = s*u + c*v + h/2 - 0.5 with u = x + 0.5 - w/2, v = y + 0.5 - h/2, in fp32 without
+ *            contraction, rounded half-to-even and clamped to [0, 255].  (sin_t, cos_t) == (0, 1) is a pure byte copy. */
+typedef struct fn_augment_param {
+    int32_t y0, x0;
+    int32_t flip;
+    float cos_t, sin_t;
+} fn_augment_param;
+/* fn_crop_or_pad_u8's ragged src / offsets / hw input and one fn_augment_param per image (device memory) -> dst u8 [N,S,S,3] in
+ * one launch; S must be even.  Sizes are not checked against the src allocation: the caller owns the packing. */
+int fn_augment_u8(const uint8_t* src, const long long* offsets, const int32_t* hw, const fn_augment_param* params, uint8_t* dst, int N,
+                  int S, void* stream);
 /* gather rows of a u8 image pool by index (triplet batch assembly): out[i] = pool[idx[i]] */
 int fn_gather_images(const uint8_t* pool, const int32_t* idx, uint8_t* out, int n_out, int bytes_per_image, void* stream);
 
