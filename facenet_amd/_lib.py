@@ -106,6 +106,7 @@ _SIGNATURES = {
     "fn_f2f_pair_counts": [_p, _p, _p, _i, _i, _i, _p, _p, _p],
     "fn_f2f_distance": [_p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p],
     "fn_adam_keras":[_p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p],
+    "fn_adam_keras_ema": [_p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p],
     "fn_adam_tick": [_p, _f, _f, _p],
     "fn_pack_transpose": [_p, _p, _p, _i, _i, _i, _p],
     "fn_fold_bn": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p],

@@ -21,7 +21,7 @@ import torch
 from facenet_amd import config as config_mod
 from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
-from facenet_amd.train import Trainer
+from facenet_amd.train import Trainer, moving_average_decay
 
 
 def synthetic_batches(batch_size, nrof_classes, size, seed):
@@ -64,8 +64,10 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         nrof_classes=nrof_classes, device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
-    # loss.center_* / prelogits_norm_* (train_softmax.yaml:73-78): center loss and prelogits-norm loss on the embedding
+    # loss.center_* / prelogits_norm_* (train_softmax.yaml:73-78): center loss and prelogits-norm loss on the embedding;
+    # train.moving_average_decay (:28): the moving average of the weights
     trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group,
+                      moving_average_decay=moving_average_decay(cfg),
                       **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p")})
     first_epoch = 0
     if cfg.model.checkpoint:                                      # network.load_weights(checkpoint) before fit (:68-71)
@@ -103,6 +105,10 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
                 path.mkdir(parents=True, exist_ok=True)
             # Keras variable names and order + Adam slots, iteration count and epoch; moving statistics averaged over replicas
             trainer.save_checkpoint(path / f"{path.stem}.npz", epoch=epoch + 1)
+            if trainer.shadow is not None:                        # the averaged model, loadable by FaceNet(config.path=...)
+                if rank == 0:
+                    (path / "averaged").mkdir(exist_ok=True)
+                trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
     return net, trainer
 
 

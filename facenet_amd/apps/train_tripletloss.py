@@ -18,7 +18,7 @@ import torch
 from facenet_amd import config as config_mod
 from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
-from facenet_amd.train import GraphRunner, Trainer, TripletMiner
+from facenet_amd.train import GraphRunner, Trainer, TripletMiner, moving_average_decay
 from facenet_amd.schedule import make_events
 
 
@@ -30,7 +30,7 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
                         device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=3 * nrof_triplets, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size,
-                      process_group=process_group)
+                      process_group=process_group, moving_average_decay=moving_average_decay(cfg))
     n = people_per_batch * images_per_person
     miner = TripletMiner(net, n, np.repeat(np.arange(people_per_batch), images_per_person), nrof_triplets, alpha=alpha, seed=cfg.seed)
     miner.build(trainer.plan.images)
@@ -56,6 +56,11 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
         dt = time.perf_counter() - t0
         log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  triplet loss {trainer.loss_value():.4f}  "
             f"{3 * nrof_triplets * cfg.train.epoch.size * world_size / dt:.1f} img/s")
+        if trainer.shadow is not None and cfg.model.path:        # the averaged model, loadable by FaceNet(config.path=...)
+            path = Path(cfg.model.path).expanduser()
+            if trainer.rank == 0:
+                (path / "averaged").mkdir(parents=True, exist_ok=True)
+            trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
     return net, trainer
 
 

@@ -4,6 +4,9 @@
 //    w -= lr_t*m/(sqrt(v)+eps), with the Keras L2(5e-4) kernel regulariser (inception_resnet_v1.py:65)
 //    folded in as a coupled term g += 2*l2*w on the first n_decay elements.  One fused multi-tensor
 //    pass over the flat parameter buffer also emits the low-precision weight copy the MFMA kernels read.
+//  * fn_adam_keras_ema: the same pass plus the exponential moving average of the new weights (TF1's
+//    ExponentialMovingAverage(decay, num_updates = t), zero_debias=False):
+//    d = min(decay, (1+t)/(10+t)), s -= (s - w) * (1 - d), read and written in the same sweep.
 //  * fn_pack_transpose: [Cout][tap][Cin] -> [Cin][tap][Cout] (operand of the dgrad implicit GEMM).
 //  * fn_fold_bn: inference weights with BatchNorm folded in, the formula of facenet/tfutils.py:244-250.
 #include "common.h"
@@ -12,18 +15,28 @@
 namespace fn {
 
 // hyper: [0]=lr [1]=beta1^t [2]=beta2^t [3]=grad_scale [4]=t (int32 bits) ; powers are those AFTER this step's tick
-template <typename T>
+// EMA: also s -= (s - w) * (1 - d) on `shadow` with the step's new w; the Adam arithmetic is the same code in both instantiations
+template <typename T, bool EMA>
 __global__ __launch_bounds__(256) void adam_keras_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, unsigned short* __restrict__ w_lp, long n_lp, long n, long n_decay,
-                                                         const float* __restrict__ hyper, float beta1, float beta2, float eps, float l2) {
+                                                         const float* __restrict__ hyper, float beta1, float beta2, float eps, float l2,
+                                                         float* __restrict__ shadow, float decay) {
     const float lr = hyper[0], b1t = hyper[1], b2t = hyper[2], gs = hyper[3];
     const float lr_t = lr * sqrtf(1.f - b2t) / (1.f - b1t);
+    float one_minus_d = 0.f;
+    if constexpr (EMA) {
+        // TF1 num_updates = Keras `iterations` after this step's tick; IEEE division, three separately rounded operations below
+        const float tf = (float)reinterpret_cast<const int*>(hyper)[4];
+        one_minus_d = 1.0f - fminf(decay, (1.0f + tf) / (10.0f + tf));
+    }
     const long n4 = n >> 2;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
         f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
         f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+        f32x4 sv;
+        if constexpr (EMA) sv = reinterpret_cast<const f32x4*>(shadow)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float gg = gv[e] * gs;
@@ -36,6 +49,12 @@ __global__ __launch_bounds__(256) void adam_keras_kernel(float* __restrict__ w, 
         __builtin_nontemporal_store(wv, reinterpret_cast<f32x4*>(w) + i);
         __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
+        if constexpr (EMA) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sv[e] = sv[e] - (sv[e] - wv[e]) * one_minus_d;
+            __builtin_nontemporal_store(sv, reinterpret_cast<f32x4*>(shadow) + i);
+        }
         if (w_lp && i * 4 < n_lp) {
             const unsigned lo = (unsigned)LP<T>::from_f32(wv[0]) | ((unsigned)LP<T>::from_f32(wv[1]) << 16);
             const unsigned hi = (unsigned)LP<T>::from_f32(wv[2]) | ((unsigned)LP<T>::from_f32(wv[3]) << 16);
@@ -147,18 +166,33 @@ __global__ __launch_bounds__(256) void fold_bn_kernel(const float* __restrict__ 
 }  // namespace fn
 using namespace fn;
 
+template <bool EMA>
+static int launch_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                             float beta1, float beta2, float eps, float l2, float* shadow, float decay, int dtype, void* stream) {
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (dtype == FN_BF16)
+        hipLaunchKernelGGL((adam_keras_kernel<__bf16, EMA>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, shadow, decay);
+    else
+        hipLaunchKernelGGL((adam_keras_kernel<_Float16, EMA>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, shadow, decay);
+    return check_launch(EMA ? "adam_keras_ema" : "adam_keras");
+}
+
 extern "C" int fn_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper, float beta1,
                              float beta2, float eps, float l2, int dtype, void* stream) {
     FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
     FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp % 4 == 0 && n_lp <= n,
                "adam_keras: bad arguments (n %% 4 == 0)");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (dtype == FN_BF16)
-        hipLaunchKernelGGL(adam_keras_kernel<__bf16>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2);
-    else
-        hipLaunchKernelGGL(adam_keras_kernel<_Float16>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2);
-    return check_launch("adam_keras");
+    return launch_adam_keras<false>(w, g, m, v, w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, nullptr, 0.f, dtype, stream);
+}
+
+extern "C" int fn_adam_keras_ema(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                                 float beta1, float beta2, float eps, float l2, int dtype, float* shadow, float decay, void* stream) {
+    FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
+    FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp % 4 == 0 && n_lp <= n,
+               "adam_keras_ema: bad arguments (n %% 4 == 0)");
+    FN_REQUIRE(shadow && decay > 0.f && decay < 1.f, "adam_keras_ema: null shadow or decay %g outside (0, 1)", (double)decay);
+    return launch_adam_keras<true>(w, g, m, v, w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, shadow, decay, dtype, stream);
 }
 
 extern "C" int fn_adam_tick(float* hyper, float beta1, float beta2, void* stream) {

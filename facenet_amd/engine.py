@@ -346,10 +346,12 @@ class Network:
         from . import keras_names
         return keras_names.keras_variable_table(self.layers, int(self.cfg["block8_1"]["repeat"]))
 
-    def keras_variables(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
-        """``model.weights`` of the reference model: Keras variable names, Keras layouts, Keras order (keras_names.py)."""
+    def keras_variables(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                        params: Optional[torch.Tensor] = None) -> "OrderedDict[str, torch.Tensor]":
+        """``model.weights`` of the reference model: Keras variable names, Keras layouts, Keras order (keras_names.py).
+        ``params``: a flat buffer laid out like ``P`` to export instead of ``P`` (the Trainer's moving average)."""
         from . import keras_names
-        return keras_names.to_keras(self.export_keras_params(moving_stats), self.layers, int(self.cfg["block8_1"]["repeat"]))
+        return keras_names.to_keras(self.export_keras_params(moving_stats, params), self.layers, int(self.cfg["block8_1"]["repeat"]))
 
     def export_folded_params(self) -> "OrderedDict[str, torch.Tensor]":
         """BN-folded inference weights as facenet/tfutils.py:229-258 (export_h5) writes them: per layer ``<name>/weights`` =
@@ -370,10 +372,11 @@ class Network:
                 out[L.name + "/biases"] = P[L.bias_off:L.bias_off + L.cout_real].clone()
         return out
 
-    def export_keras_params(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> "OrderedDict[str, torch.Tensor]":
+    def export_keras_params(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                            params: Optional[torch.Tensor] = None) -> "OrderedDict[str, torch.Tensor]":
         """Keras-layout tensors under the engine's keys.  ``moving_stats``: (mean, var) to export instead of this replica's
-        (data parallelism: the cross-replica average, Trainer.averaged_moving_stats)."""
-        P = self.P.detach().cpu()
+        (data parallelism: the cross-replica average, Trainer.averaged_moving_stats); ``params``: flat buffer instead of ``P``."""
+        P = (self.P if params is None else params).detach().cpu()
         mean, var = (self.S_mean.cpu(), self.S_var.cpu()) if moving_stats is None else (moving_stats[0].cpu(), moving_stats[1].cpu())
         out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         for L in self.layers.values():

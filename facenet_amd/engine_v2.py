@@ -160,9 +160,9 @@ class NetworkV2(Network):
             raise KeyError(f"weights file lacks {len(missing)} variables, first: {missing[0]}")
         return out
 
-    def keras_variables(self, moving_stats=None) -> "OrderedDict[str, torch.Tensor]":
+    def keras_variables(self, moving_stats=None, params=None) -> "OrderedDict[str, torch.Tensor]":
         """Every variable under its slim name (``variable_table`` order)."""
-        p = self.export_keras_params(moving_stats)
+        p = self.export_keras_params(moving_stats, params)
         return OrderedDict((k, p[i]) for k, i in self.variable_table())
 
 

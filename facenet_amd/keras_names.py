@@ -112,3 +112,9 @@ def optimizer_slot_names(var_name: str) -> Tuple[str, str]:
     """Keras Adam slot variables of one model variable: 'Adam/<var>/m:0', 'Adam/<var>/v:0'."""
     base = var_name[:-2] if var_name.endswith(":0") else var_name
     return f"Adam/{base}/m:0", f"Adam/{base}/v:0"
+
+
+def moving_average_name(var_name: str) -> str:
+    """TF1 ExponentialMovingAverage shadow of one trainable variable: '<var>/ExponentialMovingAverage:0'."""
+    base = var_name[:-2] if var_name.endswith(":0") else var_name
+    return f"{base}/ExponentialMovingAverage:0"

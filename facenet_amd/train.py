@@ -8,6 +8,8 @@
   (a0,p0,n0,a1,...).  ``TripletMiner`` does the online selection in a PxK pool on device.
 * ``Trainer(loss='softmax', center_factor=..., prelogits_norm_factor=...)`` adds the reference's embedding regularisers
   (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
+* ``Trainer(..., moving_average_decay=0.9999)`` keeps TF1's ``ExponentialMovingAverage(decay, global_step)`` of the trainable
+  variables (train.moving_average_decay, apps/configs/train_softmax.yaml:28), fused into the optimiser pass.
 * Data parallelism restates ``tf.distribute.MirroredStrategy()`` (apps/train_softmax_tf2_gpus.py:49):
   one process per GPU, per-replica BatchNorm, gradients summed by RCCL all-reduce in backward-ordered
   buckets on a side stream (overlapped with the rest of backward), divided by the replica count
@@ -240,6 +242,23 @@ def adam_beta_powers(t: int, beta1: float, beta2: float) -> Tuple[float, float]:
     return float(np.float32(np.float64(np.float32(beta1)) ** t)), float(np.float32(np.float64(np.float32(beta2)) ** t))
 
 
+def check_moving_average_decay(decay) -> Optional[float]:
+    """The decay of the weights' moving average, or None when it is off (None or 0); anything outside (0, 1) raises."""
+    if decay is None or decay == 0:
+        return None
+    d = float(decay)
+    if not 0.0 < d < 1.0:
+        raise ValueError(f"moving_average_decay must be in (0, 1), or None / 0 for off; got {decay!r}")
+    return d
+
+
+def moving_average_decay(cfg) -> Optional[float]:
+    """``cfg.train.moving_average_decay`` (apps/configs/train_softmax.yaml:28) as the Trainer takes it: a missing key, null or
+    0 is off (None)."""
+    value = cfg.train.moving_average_decay
+    return check_moving_average_decay(value if value else None)
+
+
 def _streams_for(net: Network, n_streams: int) -> StreamSet:
     ss = getattr(net, "_stream_set", None)
     if ss is None or len(ss.side) < n_streams - 1:
@@ -252,8 +271,10 @@ class Trainer:
     def __init__(self, net: Network, batch: int, loss: str = "triplet", alpha: float = 0.2, lr: float = 0.05, beta1: float = 0.9,
                  beta2: float = 0.999, epsilon: float = 0.1, l2: Optional[float] = None, world_size: int = 1, process_group=None,
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
-                 center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0):
+                 center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0,
+                 moving_average_decay: Optional[float] = None):
         self.group_wgrad = group_wgrad
+        self.ema_decay = check_moving_average_decay(moving_average_decay)
         # force_segments: a single replica runs the data-parallel step structure (backward cut at the bucket boundaries, one graph
         # per segment, per-segment grouped weight gradients) with the all-reduce left out: what the segmentation alone costs
         # A process group given together with world_size == 1 still EXCHANGES: the bucket all-reduces run through that one-rank
@@ -300,12 +321,16 @@ class Trainer:
             parallel.broadcast_parameters([net.P, net.S_mean, net.S_var], src=0, group=process_group)
             net.folded_valid = False
             net.refresh_packs()
+        # the moving average of every trainable variable (all of P; not the moving statistics, not the centers), initialised
+        # from the weights every replica starts with; each replica applies the same update to the same reduced step: no exchange
+        self.shadow: Optional[torch.Tensor] = None if self.ema_decay is None else net.P.clone()
         # dropout (Inception-ResNet-v2) draws its masks from Keras' `iterations` word: forward and backward of a step read it
         # before the step's adam_tick, and graph replays see it advance; masks differ per data-parallel rank
         rank = 0
         if self.exchange:
             import torch.distributed as dist
             rank = dist.get_rank(process_group)
+        self.rank = rank
         self.plan: Lowering = net.plan(batch, training=True, step_word=self.hyper.view(torch.int32)[4:5], rank=rank)
         self.demb = torch.zeros(batch, E, dtype=torch.float32, device=dev)
         self.dt = _lib.dtype_code(net.train_dtype)
@@ -362,9 +387,14 @@ class Trainer:
         self.plan.build_backward(self.demb)
         self.opt_ops: List[Op] = []
         self._op(self.opt_ops, "adam_tick", lib.fn_adam_tick, _ptr(self.hyper), beta1, beta2, w=[region(self.hyper)])
-        self._op(self.opt_ops, "adam_keras", lib.fn_adam_keras, _ptr(net.P), _ptr(self.G), _ptr(self.M), _ptr(self.V), _ptr(net.W_train),
-                 net.n_kernel, net.n_params, net.n_decay, _ptr(self.hyper), beta1, beta2, epsilon, l2, self.dt,
-                 r=[region(self.G), region(self.hyper)], w=[region(net.P), region(self.M), region(self.V), region(net.W_train)])
+        adam_args = (_ptr(net.P), _ptr(self.G), _ptr(self.M), _ptr(self.V), _ptr(net.W_train), net.n_kernel, net.n_params, net.n_decay,
+                     _ptr(self.hyper), beta1, beta2, epsilon, l2, self.dt)
+        adam_writes = [region(net.P), region(self.M), region(self.V), region(net.W_train)]
+        if self.shadow is None:
+            self._op(self.opt_ops, "adam_keras", lib.fn_adam_keras, *adam_args, r=[region(self.G), region(self.hyper)], w=adam_writes)
+        else:      # the same launch with the moving-average update fused in (one pass, same launch count)
+            self._op(self.opt_ops, "adam_keras_ema", lib.fn_adam_keras_ema, *adam_args, _ptr(self.shadow), self.ema_decay,
+                     r=[region(self.G), region(self.hyper)], w=adam_writes + [region(self.shadow)])
         self._op(self.opt_ops, "pack_transpose", lib.fn_pack_transpose, _ptr(net.W_train), _ptr(net.Wt_train), _ptr(net.table),
                  len(net.layers), net.max_layer_elems, self.dt, r=[region(net.W_train)], w=[region(net.Wt_train)])
         if self.centers is not None:      # the final segment: under data parallelism it reads the gathered global batch
@@ -378,6 +408,7 @@ class Trainer:
         self._build_segments()
         self._graph = None
         self._exchange_events: Optional[dict] = None     # set by exchange_profile() around a step
+        self._eval_plans: Dict[int, Tuple[Lowering, torch.Tensor]] = {}   # evaluate(): inference plan + output per batch size
 
     def _op(self, lst, name, fn, *args, keep=(), r=(), w=()):
         lst.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
@@ -566,7 +597,7 @@ class Trainer:
         # restored around it, so capture() followed by n steps equals n eager steps (Adam's t, the moving statistics and the
         # parameters are untouched; the reference's fit() has no uncounted step either).
         net = self.net
-        state = (net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper) + (() if self.centers is None else (self.centers,))
+        state = (net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper) + tuple(t for t in (self.centers, self.shadow) if t is not None)
         saved = [t.clone() for t in state]
         self.step_eager()           # warm-up: first-call attribute set-up, allocator
         torch.cuda.synchronize(net.device)
@@ -633,6 +664,9 @@ class Trainer:
         out["epoch"] = np.asarray(int(epoch), dtype=np.int64)
         if self.centers is not None:
             out["centers:0"] = self.centers.cpu().numpy()      # the TF1 variable of facenet.py:208 (identical on every replica)
+        if self.shadow is not None:                            # TF1's shadow variables, next to the Adam slots
+            for key, t in net.export_keras_grads(self.shadow).items():
+                out[keras_names.moving_average_name(table[key])] = t.numpy()
         return out
 
     def save_checkpoint(self, path, epoch: int = 0):
@@ -665,7 +699,70 @@ class Trainer:
                 buf.copy_(net.flat_from_keras(tmp))
             self.hyper[0:1].fill_(float(sd["Adam/learning_rate:0"]))
             self.iterations = int(sd["Adam/iter:0"])
+        if self.shadow is not None:
+            trainable = [(k, i) for k, i in net.variable_table() if not i.endswith(("/moving_mean", "/moving_variance"))]
+            if keras_names.moving_average_name(trainable[0][0]) in sd:
+                self.shadow.copy_(net.flat_from_keras({i: torch.from_numpy(sd[keras_names.moving_average_name(k)]) for k, i in trainable}))
+            else:                                               # a checkpoint of a run without the moving average
+                self.reset_average()
         return int(sd.get("epoch", 0))
+
+    # ---- the moving average of the weights ---------------------------------------------------------
+    def _require_average(self):
+        if self.shadow is None:
+            raise RuntimeError("this Trainer keeps no moving average: build it with moving_average_decay in (0, 1)")
+
+    def reset_average(self):
+        """Restart the moving average from the current weights."""
+        self._require_average()
+        self.shadow.copy_(self.net.P)
+
+    def averaged_variables(self) -> Dict[str, torch.Tensor]:
+        """``keras_variables()`` with the moving average in place of every trainable variable and the replica-averaged moving
+        statistics.  Collective under data parallelism: every rank must call it."""
+        self._require_average()
+        return self.net.keras_variables(self.averaged_moving_stats(), params=self.shadow)
+
+    def save_averaged_weights(self, path):
+        """The averaged model as an ``.npz`` with the keys and order of ``InceptionResnetV1.save_weights`` (readable by
+        ``load_weights`` and ``FaceNet``).  Collective under data parallelism; rank 0 writes."""
+        variables = self.averaged_variables()
+        if self.rank == 0:
+            np.savez(path, **{k: v.numpy() for k, v in variables.items()})
+
+    def evaluate(self, images, averaged: bool = False) -> torch.Tensor:
+        """L2-normalised inference embeddings [N, E] of uint8 NHWC images through the network's inference plan, from the raw
+        weights or (``averaged``) from the moving average with this replica's moving statistics.  The inference plans read
+        biases from ``P`` itself, so the average is swapped into ``P`` for the call and ``P`` is restored bit for bit after it."""
+        net = self.net
+        x = torch.as_tensor(images)
+        S = net.image_size
+        if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (S, S, 3):
+            raise ValueError(f"expected uint8 images [N,{S},{S},3], got {x.dtype} {tuple(x.shape)}")
+        if averaged:
+            self._require_average()
+        n = x.shape[0]
+        if n > 256:      # the per-plan batch limit of inference (InceptionResnetV1.MAX_PLAN_BATCH)
+            return torch.cat([self.evaluate(x[i:i + 256], averaged) for i in range(0, n, 256)])
+        st = net.stream()
+        if n not in self._eval_plans:
+            self._eval_plans[n] = (net.plan(n, training=False), torch.empty(n, net.E, dtype=torch.float32, device=net.device))
+        plan, out = self._eval_plans[n]
+        plan.images.copy_(x.to(net.device))
+        saved = None
+        try:
+            if averaged:
+                saved = net.P.clone()
+                net.P.copy_(self.shadow)
+                net.folded_valid = False
+            net.refresh_folded(st, force=False)
+            Lowering.run_ops(plan.fwd, st)
+            _lib.check(self.lib.fn_l2norm_fwd(_ptr(plan.embedding.buf.act), _ptr(out), n, net.E, 1e-10, st), "l2norm")
+            return out.clone()
+        finally:
+            if saved is not None:
+                net.P.copy_(saved)
+                net.folded_valid = False       # the fold holds the average: the next raw inference refolds
 
     @property
     def iterations(self) -> int:

@@ -375,6 +375,10 @@ int fn_f2f_distance(const float* x, const float* nx, int N, const float* y, cons
  * Elements [0, n_decay) get the coupled L2 term g += 2*l2*w.  w_lp receives the low-precision copy of w[0, n_lp). */
 int fn_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper, float beta1,
                   float beta2, float eps, float l2, int dtype, void* stream);
+/* fn_adam_keras_ema: fn_adam_keras (w, m, v, w_lp bit-identical) fused with the moving average of the new weights over [0, n):
+ * shadow = shadow - (shadow - w) * (1 - d), d = fminf(decay, (1 + t) / (10 + t)), t = word 4 of hyper; decay in (0, 1). */
+int fn_adam_keras_ema(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                      float beta1, float beta2, float eps, float l2, int dtype, float* shadow, float decay, void* stream);
 int fn_adam_tick(float* hyper, float beta1, float beta2, void* stream);
 
 /* ---- weight packs ----------------------------------------------------------------------------------
