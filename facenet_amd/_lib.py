@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfacenet_hip.so")
 
 FN_BF16, FN_F16 = 0, 1
+FN_OPT_ADAGRAD, FN_OPT_ADADELTA, FN_OPT_RMSPROP, FN_OPT_MOM = 1, 2, 3, 4     # fn_opt_keras rule codes
 
 
 class ConvDesc(C.Structure):
@@ -108,6 +109,8 @@ _SIGNATURES = {
     "fn_adam_keras":[_p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p],
     "fn_adam_keras_ema": [_p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p],
     "fn_adam_tick": [_p, _f, _f, _p],
+    "fn_opt_keras": [_i, _p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p],
+    "fn_opt_keras_ema": [_i, _p, _p, _p, _p, _p, _l, _l, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p],
     "fn_pack_transpose": [_p, _p, _p, _i, _i, _i, _p],
     "fn_fold_bn": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p],
 }

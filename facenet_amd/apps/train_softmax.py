@@ -3,7 +3,8 @@
 ``python -m facenet_amd.apps.train_softmax --config x.yaml``.
 
 model = InceptionResnetV1; network = Sequential([model, Dense(nrof_classes)]) (:55-66); loss =
-SparseCategoricalCrossentropy(from_logits=True) (:91); Adam(epsilon=0.1) (:92); LR set per epoch by
+SparseCategoricalCrossentropy(from_logits=True) (:91); Adam(epsilon=0.1) (:92), or the Keras optimizer train.optimizer names
+(DESIGN.md section 15); LR set per epoch by
 LearningRateScheduler (:80-83); ``train.epoch.size`` steps per epoch (:95-104).
 
 Batches come from ``batches`` (an iterable of (uint8 images [N,160,160,3], int labels [N])); ``main`` builds them from
@@ -21,7 +22,7 @@ import torch
 from facenet_amd import config as config_mod
 from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
-from facenet_amd.train import Trainer, moving_average_decay
+from facenet_amd.train import Trainer, moving_average_decay, optimizer_name
 
 
 def synthetic_batches(batch_size, nrof_classes, size, seed):
@@ -60,6 +61,7 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     if cfg.batch_size % world_size:
         raise ValueError(f"batch_size {cfg.batch_size} is not divisible by the {world_size} replicas")
     local_batch = cfg.batch_size // world_size
+    optimizer = optimizer_name(cfg)                               # train.optimizer (train_softmax.yaml:25-26): checked before any GPU work
     # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         nrof_classes=nrof_classes, device=device, seed=cfg.seed)
@@ -67,8 +69,10 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
     # loss.center_* / prelogits_norm_* (train_softmax.yaml:73-78): center loss and prelogits-norm loss on the embedding;
     # train.moving_average_decay (:28): the moving average of the weights
     trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group,
-                      moving_average_decay=moving_average_decay(cfg),
+                      moving_average_decay=moving_average_decay(cfg), optimizer=optimizer,
                       **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p")})
+    if rank == 0 and optimizer != "ADAM":                        # once; an Adam run logs exactly what it always did
+        log(f"optimizer: {optimizer}")
     first_epoch = 0
     if cfg.model.checkpoint:                                      # network.load_weights(checkpoint) before fit (:68-71)
         ckpt = Path(cfg.model.checkpoint).expanduser()
@@ -103,7 +107,7 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
             path = Path(cfg.model.path).expanduser()
             if rank == 0:
                 path.mkdir(parents=True, exist_ok=True)
-            # Keras variable names and order + Adam slots, iteration count and epoch; moving statistics averaged over replicas
+            # Keras variable names and order + optimizer slots, iteration count and epoch; moving statistics averaged over replicas
             trainer.save_checkpoint(path / f"{path.stem}.npz", epoch=epoch + 1)
             if trainer.shadow is not None:                        # the averaged model, loadable by FaceNet(config.path=...)
                 if rank == 0:

@@ -3,7 +3,8 @@
 SURVEY.md A13): ``python -m facenet_amd.apps.train_tripletloss --config x.yaml``.
 
 Per step: embed a P x K pool with the inference path -> [PK,PK] squared distances -> online selection (alpha) ->
-train on the selected (a,p,n) rows: forward(training=True) -> l2_normalize -> triplet loss -> backward -> Keras Adam.
+train on the selected (a,p,n) rows: forward(training=True) -> l2_normalize -> triplet loss -> backward -> the Keras optimizer
+train.optimizer names (Adam by default).
 Pools come from ``pools`` (an iterable of (uint8 images [P*K,160,160,3])) with labels repeat(arange(P), K) or, by
 default, from a seeded synthetic generator."""
 from __future__ import annotations
@@ -18,19 +19,22 @@ import torch
 from facenet_amd import config as config_mod
 from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
-from facenet_amd.train import GraphRunner, Trainer, TripletMiner, moving_average_decay
+from facenet_amd.train import GraphRunner, Trainer, TripletMiner, moving_average_decay, optimizer_name
 from facenet_amd.schedule import make_events
 
 
 def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 4, nrof_triplets: int = 30, embedding_size: int = 128,
                       pools=None, device: str = "cuda", use_graph: bool = True, world_size: int = 1, process_group=None, log=print):
     alpha = cfg.loss.alpha if cfg.loss.alpha else 0.2
+    optimizer = optimizer_name(cfg)                               # train.optimizer: checked before any GPU work
     # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=3 * nrof_triplets, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size,
-                      process_group=process_group, moving_average_decay=moving_average_decay(cfg))
+                      process_group=process_group, moving_average_decay=moving_average_decay(cfg), optimizer=optimizer)
+    if trainer.rank == 0 and optimizer != "ADAM":                # once; an Adam run logs exactly what it always did
+        log(f"optimizer: {optimizer}")
     n = people_per_batch * images_per_person
     miner = TripletMiner(net, n, np.repeat(np.arange(people_per_batch), images_per_person), nrof_triplets, alpha=alpha, seed=cfg.seed)
     miner.build(trainer.plan.images)

@@ -75,7 +75,8 @@ DEFAULTS = {   # apps/configs/config.yaml:4-15 and train_softmax.yaml:37-47 (the
     "batch_size": 100,
     "image": {"size": 160, "margin": 0, "normalization": 0},
     "train": {"epoch": {"nrof_epochs": None, "size": 1000},
-              "learning_rate": {"value": None, "schedule": [[100, 0.05], [200, 0.005], [300, 0.0005]]}},
+              "learning_rate": {"value": None, "schedule": [[100, 0.05], [200, 0.005], [300, 0.0005]]},
+              "optimizer": "ADAM"},         # train_softmax.yaml:25-26
     # apps/configs/train_softmax.yaml:73-78 (prelogits_hist_max only fed a TensorBoard histogram: not read)
     "loss": {"alpha": 0.2, "center_factor": 0.0, "center_alfa": 0.95, "prelogits_norm_factor": 0.0, "prelogits_norm_p": 1.0},
 }

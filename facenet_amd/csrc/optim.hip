@@ -7,6 +7,8 @@
 //  * fn_adam_keras_ema: the same pass plus the exponential moving average of the new weights (TF1's
 //    ExponentialMovingAverage(decay, num_updates = t), zero_debias=False):
 //    d = min(decay, (1+t)/(10+t)), s -= (s - w) * (1 - d), read and written in the same sweep.
+//  * fn_opt_keras / fn_opt_keras_ema: the other update rules of train.optimizer (Keras Adagrad, Adadelta, RMSprop and
+//    Nesterov SGD) as one templated sweep of the same shape, with or without the moving average.
 //  * fn_pack_transpose: [Cout][tap][Cin] -> [Cin][tap][Cout] (operand of the dgrad implicit GEMM).
 //  * fn_fold_bn: inference weights with BatchNorm folded in, the formula of facenet/tfutils.py:244-250.
 #include "common.h"
@@ -72,6 +74,86 @@ __global__ void adam_tick_kernel(float* hyper, float beta1, float beta2) {
     *it = t;
     hyper[1] = (float)pow((double)beta1, (double)t);
     hyper[2] = (float)pow((double)beta2, (double)t);
+}
+
+// The update rules of fn_opt_keras (rule codes FN_OPT_*), each the Keras optimizer train.optimizer names.
+// g is the gradient adam_keras_kernel forms; lr = hyper[0] is read on every launch.  Operation order, every operation an IEEE
+// fp32 operation rounded on its own (no contraction, IEEE sqrtf and division; restated by tests/optimizer_oracle.py):
+//   g = G * gs;  g = g + (2 * l2) * w                          on [0, n_decay)
+//   ADAGRAD   s1 = accumulator:             a = a + g * g;  w = w - (lr * g) / (sqrt(a) + eps)
+//   ADADELTA  s1 = accum_grad, s2 = accum_var:
+//             ag = rho * ag + (1 - rho) * (g * g);  u = sqrt(av + eps) / sqrt(ag + eps) * g;  w = w - lr * u;
+//             av = rho * av + (1 - rho) * (u * u)
+//   RMSPROP   s1 = rms, s2 = momentum:      ms = rho * ms + (1 - rho) * (g * g);  mom = mu * mom + (lr * g) / sqrt(ms + eps);
+//             w = w - mom
+//   MOM       s1 = momentum (Nesterov):     acc = mu * acc - lr * g;  w = w + (mu * acc - lr * g)
+// EMA: the moving average of adam_keras_kernel on the new w.  The rule is a template argument: no per-element branch on it.
+template <int RULE>
+struct OptSlots {
+    static constexpr bool two = RULE == FN_OPT_ADADELTA || RULE == FN_OPT_RMSPROP;
+};
+
+template <typename T, int RULE, bool EMA>
+__global__ __launch_bounds__(256) void opt_keras_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s1,
+                                                        float* __restrict__ s2, unsigned short* __restrict__ w_lp, long n_lp, long n,
+                                                        long n_decay, const float* __restrict__ hyper, float rho, float mu, float eps,
+                                                        float l2, float* __restrict__ shadow, float decay) {
+#pragma clang fp contract(off)
+    constexpr bool TWO = OptSlots<RULE>::two;
+    const float lr = hyper[0], gs = hyper[3];
+    const float one_minus_rho = 1.f - rho, two_l2 = 2.f * l2;
+    float one_minus_d = 0.f;
+    if constexpr (EMA) {
+        const float tf = (float)reinterpret_cast<const int*>(hyper)[4];
+        one_minus_d = 1.0f - fminf(decay, (1.0f + tf) / (10.0f + tf));
+    }
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 av = reinterpret_cast<f32x4*>(s1)[i];
+        f32x4 bv;
+        if constexpr (TWO) bv = reinterpret_cast<f32x4*>(s2)[i];
+        f32x4 sv;
+        if constexpr (EMA) sv = reinterpret_cast<const f32x4*>(shadow)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float gg = gv[e] * gs;
+            if (i * 4 + e < n_decay) gg = gg + two_l2 * wv[e];
+            if constexpr (RULE == FN_OPT_ADAGRAD) {
+                av[e] = av[e] + gg * gg;
+                wv[e] = wv[e] - (lr * gg) / (sqrtf(av[e]) + eps);
+            } else if constexpr (RULE == FN_OPT_ADADELTA) {
+                av[e] = rho * av[e] + one_minus_rho * (gg * gg);
+                const float u = sqrtf(bv[e] + eps) / sqrtf(av[e] + eps) * gg;
+                wv[e] = wv[e] - lr * u;
+                bv[e] = rho * bv[e] + one_minus_rho * (u * u);
+            } else if constexpr (RULE == FN_OPT_RMSPROP) {
+                av[e] = rho * av[e] + one_minus_rho * (gg * gg);
+                bv[e] = mu * bv[e] + (lr * gg) / sqrtf(av[e] + eps);
+                wv[e] = wv[e] - bv[e];
+            } else {
+                static_assert(RULE == FN_OPT_MOM, "unknown update rule");
+                const float step = lr * gg;
+                av[e] = mu * av[e] - step;
+                wv[e] = wv[e] + (mu * av[e] - step);
+            }
+        }
+        // streamed, as in adam_keras_kernel: nothing reads the parameters or the slots before the next step
+        __builtin_nontemporal_store(wv, reinterpret_cast<f32x4*>(w) + i);
+        __builtin_nontemporal_store(av, reinterpret_cast<f32x4*>(s1) + i);
+        if constexpr (TWO) __builtin_nontemporal_store(bv, reinterpret_cast<f32x4*>(s2) + i);
+        if constexpr (EMA) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sv[e] = sv[e] - (sv[e] - wv[e]) * one_minus_d;
+            __builtin_nontemporal_store(sv, reinterpret_cast<f32x4*>(shadow) + i);
+        }
+        if (w_lp && i * 4 < n_lp) {
+            const unsigned lo = (unsigned)LP<T>::from_f32(wv[0]) | ((unsigned)LP<T>::from_f32(wv[1]) << 16);
+            const unsigned hi = (unsigned)LP<T>::from_f32(wv[2]) | ((unsigned)LP<T>::from_f32(wv[3]) << 16);
+            reinterpret_cast<uint2*>(w_lp)[i] = make_uint2(lo, hi);
+        }
+    }
 }
 
 // one workgroup column per layer (blockIdx.y); table row = {w_off, cout, ktot, taps, cin, bn_off, fold_bias_off, 0}.
@@ -193,6 +275,57 @@ extern "C" int fn_adam_keras_ema(float* w, const float* g, float* m, float* v, v
                "adam_keras_ema: bad arguments (n %% 4 == 0)");
     FN_REQUIRE(shadow && decay > 0.f && decay < 1.f, "adam_keras_ema: null shadow or decay %g outside (0, 1)", (double)decay);
     return launch_adam_keras<true>(w, g, m, v, w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, shadow, decay, dtype, stream);
+}
+
+template <int RULE, bool EMA>
+static int launch_opt_rule(float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay, const float* hyper,
+                           float rho, float mu, float eps, float l2, float* shadow, float decay, int dtype, void* stream) {
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (dtype == FN_BF16)
+        hipLaunchKernelGGL((opt_keras_kernel<__bf16, RULE, EMA>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, s1, s2, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay);
+    else
+        hipLaunchKernelGGL((opt_keras_kernel<_Float16, RULE, EMA>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, g, s1, s2, (unsigned short*)w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay);
+    return check_launch(EMA ? "opt_keras_ema" : "opt_keras");
+}
+
+template <bool EMA>
+static int launch_opt_keras(int rule, float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay,
+                            const float* hyper, float rho, float mu, float eps, float l2, float* shadow, float decay, int dtype, void* stream) {
+    switch (rule) {
+        case FN_OPT_ADAGRAD:
+            return launch_opt_rule<FN_OPT_ADAGRAD, EMA>(w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay, dtype, stream);
+        case FN_OPT_ADADELTA:
+            return launch_opt_rule<FN_OPT_ADADELTA, EMA>(w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay, dtype, stream);
+        case FN_OPT_RMSPROP:
+            return launch_opt_rule<FN_OPT_RMSPROP, EMA>(w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay, dtype, stream);
+        default:
+            return launch_opt_rule<FN_OPT_MOM, EMA>(w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, mu, eps, l2, shadow, decay, dtype, stream);
+    }
+}
+
+static int check_opt_keras_args(const char* what, int rule, const float* w, const float* g, const float* s1, const float* s2, long n_lp, long n,
+                                long n_decay, const float* hyper, int dtype) {
+    FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
+    FN_REQUIRE(rule == FN_OPT_ADAGRAD || rule == FN_OPT_ADADELTA || rule == FN_OPT_RMSPROP || rule == FN_OPT_MOM,
+               "%s: unknown update rule %d", what, rule);
+    FN_REQUIRE(w && g && s1 && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp >= 0 && n_lp % 4 == 0 && n_lp <= n,
+               "%s: bad arguments (n %% 4 == 0)", what);
+    FN_REQUIRE(s2 || !(rule == FN_OPT_ADADELTA || rule == FN_OPT_RMSPROP), "%s: rule %d keeps two slots, the second is null", what, rule);
+    return 0;
+}
+
+extern "C" int fn_opt_keras(int rule, float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                            float rho, float momentum, float eps, float l2, int dtype, void* stream) {
+    if (int rc = check_opt_keras_args("opt_keras", rule, w, g, s1, s2, n_lp, n, n_decay, hyper, dtype)) return rc;
+    return launch_opt_keras<false>(rule, w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, momentum, eps, l2, nullptr, 0.f, dtype, stream);
+}
+
+extern "C" int fn_opt_keras_ema(int rule, float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay,
+                                float* hyper, float rho, float momentum, float eps, float l2, int dtype, float* shadow, float decay, void* stream) {
+    if (int rc = check_opt_keras_args("opt_keras_ema", rule, w, g, s1, s2, n_lp, n, n_decay, hyper, dtype)) return rc;
+    FN_REQUIRE(shadow && decay > 0.f && decay < 1.f, "opt_keras_ema: null shadow or decay %g outside (0, 1)", (double)decay);
+    return launch_opt_keras<true>(rule, w, g, s1, s2, w_lp, n_lp, n, n_decay, hyper, rho, momentum, eps, l2, shadow, decay, dtype, stream);
 }
 
 extern "C" int fn_adam_tick(float* hyper, float beta1, float beta2, void* stream) {

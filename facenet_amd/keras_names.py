@@ -108,10 +108,11 @@ def from_keras(params: Dict, layers, block8_repeat: int = 5) -> "Dict":
     return out
 
 
-def optimizer_slot_names(var_name: str) -> Tuple[str, str]:
-    """Keras Adam slot variables of one model variable: 'Adam/<var>/m:0', 'Adam/<var>/v:0'."""
+def optimizer_slot_names(var_name: str, optimizer: str = "Adam", slots: Tuple[str, ...] = ("m", "v")) -> Tuple[str, ...]:
+    """Keras slot variables of one model variable, '<optimizer>/<var>/<slot>:0' per slot: by default Adam's 'Adam/<var>/m:0',
+    'Adam/<var>/v:0'; e.g. ('RMSprop', ('rms', 'momentum')) for RMSprop."""
     base = var_name[:-2] if var_name.endswith(":0") else var_name
-    return f"Adam/{base}/m:0", f"Adam/{base}/v:0"
+    return tuple(f"{optimizer}/{base}/{slot}:0" for slot in slots)
 
 
 def moving_average_name(var_name: str) -> str:

@@ -10,6 +10,8 @@
   (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
 * ``Trainer(..., moving_average_decay=0.9999)`` keeps TF1's ``ExponentialMovingAverage(decay, global_step)`` of the trainable
   variables (train.moving_average_decay, apps/configs/train_softmax.yaml:28), fused into the optimiser pass.
+* ``Trainer(..., optimizer='RMSPROP')`` picks the update rule by the names of train.optimizer (apps/configs/train_softmax.yaml:25-26):
+  ADAGRAD, ADADELTA, ADAM, RMSPROP, MOM, each the Keras optimizer the TF1 line's name maps to.
 * Data parallelism restates ``tf.distribute.MirroredStrategy()`` (apps/train_softmax_tf2_gpus.py:49):
   one process per GPU, per-replica BatchNorm, gradients summed by RCCL all-reduce in backward-ordered
   buckets on a side stream (overlapped with the rest of backward), divided by the replica count
@@ -20,12 +22,14 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+import warnings
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib, parallel
+from .config import Config
 from .engine import BN_EPS, L2_WEIGHT, Lowering, Network, _pad8, _ptr
 from .schedule import Op, Schedule, StreamSet, levelize, make_events, region, run_schedule, torch_op
 
@@ -259,6 +263,46 @@ def moving_average_decay(cfg) -> Optional[float]:
     return check_moving_average_decay(value if value else None)
 
 
+class OptimizerRule(NamedTuple):
+    """One value of train.optimizer: the Keras optimizer it maps to (its class name prefixes the checkpoint keys), the slot
+    variables it keeps per parameter with their initial values, and the constants fn_opt_keras takes."""
+    code: int                                   # fn_opt_keras rule code; 0: Adam (fn_adam_keras, the Trainer's beta1 / beta2 / epsilon)
+    keras: str
+    slots: Tuple[Tuple[str, float], ...]        # (Keras slot name, initial value)
+    rho: float = 0.0
+    momentum: float = 0.0
+    epsilon: float = 0.0
+
+    @property
+    def op(self) -> str:
+        """Name of the update launch in a step's schedule."""
+        return f"{self.keras.lower()}_keras"
+
+
+# The TF1 line's optimizer names (facenet.train) -> the Keras optimizers with the hyperparameters that line passes, as Adam's
+# epsilon=0.1 carried over (DESIGN.md section 15).  The only table of these constants.
+OPTIMIZERS: Dict[str, OptimizerRule] = {
+    "ADAGRAD": OptimizerRule(_lib.FN_OPT_ADAGRAD, "Adagrad", (("accumulator", 0.1),), epsilon=1e-7),
+    "ADADELTA": OptimizerRule(_lib.FN_OPT_ADADELTA, "Adadelta", (("accum_grad", 0.0), ("accum_var", 0.0)), rho=0.9, epsilon=1e-6),
+    "ADAM": OptimizerRule(0, "Adam", (("m", 0.0), ("v", 0.0))),
+    "RMSPROP": OptimizerRule(_lib.FN_OPT_RMSPROP, "RMSprop", (("rms", 0.0), ("momentum", 0.0)), rho=0.9, momentum=0.9, epsilon=1.0),
+    "MOM": OptimizerRule(_lib.FN_OPT_MOM, "SGD", (("momentum", 0.0),), momentum=0.9),
+}
+
+
+def check_optimizer(name) -> str:
+    """A train.optimizer name; anything else raises the TF1 line's error."""
+    if not isinstance(name, str) or name not in OPTIMIZERS:
+        raise ValueError(f"Invalid optimization algorithm {name!r}: expected one of {', '.join(OPTIMIZERS)}")
+    return name
+
+
+def optimizer_name(cfg) -> str:
+    """``cfg.train.optimizer`` (apps/configs/train_softmax.yaml:25-26) checked; a missing key or null is ADAM."""
+    value = cfg.train.optimizer
+    return check_optimizer("ADAM" if value is None or (isinstance(value, Config) and not value) else value)
+
+
 def _streams_for(net: Network, n_streams: int) -> StreamSet:
     ss = getattr(net, "_stream_set", None)
     if ss is None or len(ss.side) < n_streams - 1:
@@ -272,8 +316,10 @@ class Trainer:
                  beta2: float = 0.999, epsilon: float = 0.1, l2: Optional[float] = None, world_size: int = 1, process_group=None,
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
                  center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0,
-                 moving_average_decay: Optional[float] = None):
+                 moving_average_decay: Optional[float] = None, optimizer: str = "ADAM"):
         self.group_wgrad = group_wgrad
+        self.optimizer = check_optimizer(optimizer)        # beta1, beta2 and epsilon are Adam's; the other rules' constants: OPTIMIZERS
+        self.rule = OPTIMIZERS[self.optimizer]
         self.ema_decay = check_moving_average_decay(moving_average_decay)
         # force_segments: a single replica runs the data-parallel step structure (backward cut at the bucket boundaries, one graph
         # per segment, per-segment grouped weight gradients) with the all-reduce left out: what the segmentation alone costs
@@ -309,10 +355,12 @@ class Trainer:
         dev, E, lib = net.device, net.E, net.lib
         self.lib = lib
         self.G = net.alloc_grads()       # + net.Gacc: fixed-point accumulators of the bias gradients (engine.Network.alloc_grads)
-        self.M = torch.zeros_like(self.G)
-        self.V = torch.zeros_like(self.G)
+        # the optimizer's slot variables in the order of its OPTIMIZERS row, at their initial values; under Adam M and V name its
+        # moments, the other rules leave them None
+        self.slots: List[torch.Tensor] = [torch.full_like(self.G, init) for _, init in self.rule.slots]
+        self.M, self.V = self.slots if self.optimizer == "ADAM" else (None, None)
         # hyper = {lr, beta1^t, beta2^t, grad_scale, t (int32 bits), 3 spare words}; lives on device so HIP-graph replays see
-        # LR changes and advance Adam's step count themselves (fn_adam_tick)
+        # LR changes and advance Keras' step count themselves (fn_adam_tick: every rule; only Adam reads the beta powers)
         self.hyper = torch.tensor([lr, 1.0, 1.0, 1.0 / world_size, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
         self.loss = torch.zeros(4, dtype=torch.float32, device=dev)     # [0] the loss; [1..3] the launch's flag + fixed-point accumulator
         if world_size > 1:
@@ -387,14 +435,22 @@ class Trainer:
         self.plan.build_backward(self.demb)
         self.opt_ops: List[Op] = []
         self._op(self.opt_ops, "adam_tick", lib.fn_adam_tick, _ptr(self.hyper), beta1, beta2, w=[region(self.hyper)])
-        adam_args = (_ptr(net.P), _ptr(self.G), _ptr(self.M), _ptr(self.V), _ptr(net.W_train), net.n_kernel, net.n_params, net.n_decay,
-                     _ptr(self.hyper), beta1, beta2, epsilon, l2, self.dt)
-        adam_writes = [region(net.P), region(self.M), region(self.V), region(net.W_train)]
+        opt_writes = [region(net.P)] + [region(s) for s in self.slots] + [region(net.W_train)]
+        if self.optimizer == "ADAM":
+            name, fn, fn_ema = "adam_keras", lib.fn_adam_keras, lib.fn_adam_keras_ema
+            opt_args = (_ptr(net.P), _ptr(self.G), _ptr(self.M), _ptr(self.V), _ptr(net.W_train), net.n_kernel, net.n_params,
+                        net.n_decay, _ptr(self.hyper), beta1, beta2, epsilon, l2, self.dt)
+        else:      # one pass of the same shape (fn_opt_keras); a one-slot rule passes no second slot
+            rule = self.rule
+            name, fn, fn_ema = rule.op, lib.fn_opt_keras, lib.fn_opt_keras_ema
+            s2 = _ptr(self.slots[1]) if len(self.slots) > 1 else None
+            opt_args = (rule.code, _ptr(net.P), _ptr(self.G), _ptr(self.slots[0]), s2, _ptr(net.W_train), net.n_kernel, net.n_params,
+                        net.n_decay, _ptr(self.hyper), rule.rho, rule.momentum, rule.epsilon, l2, self.dt)
         if self.shadow is None:
-            self._op(self.opt_ops, "adam_keras", lib.fn_adam_keras, *adam_args, r=[region(self.G), region(self.hyper)], w=adam_writes)
+            self._op(self.opt_ops, name, fn, *opt_args, r=[region(self.G), region(self.hyper)], w=opt_writes)
         else:      # the same launch with the moving-average update fused in (one pass, same launch count)
-            self._op(self.opt_ops, "adam_keras_ema", lib.fn_adam_keras_ema, *adam_args, _ptr(self.shadow), self.ema_decay,
-                     r=[region(self.G), region(self.hyper)], w=adam_writes + [region(self.shadow)])
+            self._op(self.opt_ops, name + "_ema", fn_ema, *opt_args, _ptr(self.shadow), self.ema_decay,
+                     r=[region(self.G), region(self.hyper)], w=opt_writes + [region(self.shadow)])
         self._op(self.opt_ops, "pack_transpose", lib.fn_pack_transpose, _ptr(net.W_train), _ptr(net.Wt_train), _ptr(net.table),
                  len(net.layers), net.max_layer_elems, self.dt, r=[region(net.W_train)], w=[region(net.Wt_train)])
         if self.centers is not None:      # the final segment: under data parallelism it reads the gathered global batch
@@ -578,7 +634,7 @@ class Trainer:
                 "allreduce_ms": round(total / steps, 4), "overlapped_frac": round(hidden / total, 4) if total > 0 else None}
 
     def step_eager(self):
-        """zero -> forward -> loss -> backward (+ bucketed all-reduce) -> Adam; the loss stays on device."""
+        """zero -> forward -> loss -> backward (+ bucketed all-reduce) -> optimizer; the loss stays on device."""
         self._run_segments(lambda i: run_schedule(self.segments[i][0], self.streams))
 
     def capture(self):
@@ -594,10 +650,10 @@ class Trainer:
             raise ValueError(f"captured schedules span at most 2 streams (got n_streams={self.n_streams}); build the Trainer with "
                              f"n_streams <= 2 or replay eagerly (step_eager)")
         # The warm-up below is a full training step on whatever the image buffer holds.  Training state is snapshotted and
-        # restored around it, so capture() followed by n steps equals n eager steps (Adam's t, the moving statistics and the
-        # parameters are untouched; the reference's fit() has no uncounted step either).
+        # restored around it, so capture() followed by n steps equals n eager steps (the optimizer's t and slots, the moving
+        # statistics and the parameters are untouched; the reference's fit() has no uncounted step either).
         net = self.net
-        state = (net.P, net.S_mean, net.S_var, self.M, self.V, self.hyper) + tuple(t for t in (self.centers, self.shadow) if t is not None)
+        state = (net.P, net.S_mean, net.S_var, *self.slots, self.hyper) + tuple(t for t in (self.centers, self.shadow) if t is not None)
         saved = [t.clone() for t in state]
         self.step_eager()           # warm-up: first-call attribute set-up, allocator
         torch.cuda.synchronize(net.device)
@@ -650,17 +706,19 @@ class Trainer:
         return mean, var
 
     def state_dict(self, epoch: int = 0) -> "Dict[str, np.ndarray]":
-        """Model variables under their Keras names (replica-averaged moving statistics) + the Keras-Adam slots ``Adam/<var>/m``,
-        ``Adam/<var>/v``, ``Adam/iter`` and the schedule position: everything ``fit`` needs to resume."""
+        """Model variables under their Keras names (replica-averaged moving statistics) + the Keras optimizer's slots
+        ``<Optimizer>/<var>/<slot>`` (``Adam/<var>/m``, ``RMSprop/<var>/rms``, ...), ``<Optimizer>/iter``, its learning rate and
+        the schedule position: everything ``fit`` needs to resume."""
         from . import keras_names
         net = self.net
         out = {k: v.numpy() for k, v in net.keras_variables(self.averaged_moving_stats()).items()}
         table = dict((i, k) for k, i in net.variable_table())
-        for slot, buf in (("m", self.M), ("v", self.V)):
+        prefix, slot_names = self.rule.keras, tuple(s for s, _ in self.rule.slots)
+        for j, buf in enumerate(self.slots):
             for key, t in net.export_keras_grads(buf).items():
-                out[keras_names.optimizer_slot_names(table[key])[0 if slot == "m" else 1]] = t.numpy()
-        out["Adam/iter:0"] = np.asarray(self.iterations, dtype=np.int64)
-        out["Adam/learning_rate:0"] = np.asarray(self.hyper[0].item(), dtype=np.float32)
+                out[keras_names.optimizer_slot_names(table[key], prefix, slot_names)[j]] = t.numpy()
+        out[f"{prefix}/iter:0"] = np.asarray(self.iterations, dtype=np.int64)
+        out[f"{prefix}/learning_rate:0"] = np.asarray(self.hyper[0].item(), dtype=np.float32)
         out["epoch"] = np.asarray(int(epoch), dtype=np.int64)
         if self.centers is not None:
             out["centers:0"] = self.centers.cpu().numpy()      # the TF1 variable of facenet.py:208 (identical on every replica)
@@ -675,12 +733,15 @@ class Trainer:
             np.savez(path, **sd)
 
     def load_checkpoint(self, path) -> int:
-        """Restore parameters, moving statistics and optimiser state; returns the stored epoch."""
+        """Restore parameters, moving statistics and optimiser state; returns the stored epoch.  A checkpoint written under
+        another optimizer restores everything but the optimizer, which starts fresh (Keras ``load_weights`` into a model
+        compiled with another optimizer): initial slots, t = 0, this trainer's learning rate; a warning names both."""
         from . import keras_names
         net = self.net
         with np.load(path, allow_pickle=False) as z:
             sd = {k: z[k] for k in z.files}
-        net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith("Adam/") and k != "epoch"})
+        optimizer_keys = tuple(r.keras + "/" for r in OPTIMIZERS.values())
+        net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith(optimizer_keys) and k != "epoch"})
         if self.centers is not None:
             if "centers:0" in sd:
                 c = np.asarray(sd["centers:0"], dtype=np.float32)
@@ -689,16 +750,26 @@ class Trainer:
                 self.centers.copy_(torch.from_numpy(c))
             else:
                 self.centers.zero_()                            # a checkpoint from a run without center loss
-        if "Adam/iter:0" in sd:
-            for slot, buf in ((0, self.M), (1, self.V)):
+        prefix, slot_names = self.rule.keras, tuple(s for s, _ in self.rule.slots)
+        saved_by = [name for name, r in OPTIMIZERS.items() if f"{r.keras}/iter:0" in sd]
+        if f"{prefix}/iter:0" in sd:
+            for slot, (buf, (_, init)) in enumerate(zip(self.slots, self.rule.slots)):
                 tmp = {}
                 for k, i in net.variable_table():
                     if i.endswith(("/moving_mean", "/moving_variance")):
                         continue
-                    tmp[i] = torch.from_numpy(sd[keras_names.optimizer_slot_names(k)[slot]])
-                buf.copy_(net.flat_from_keras(tmp))
-            self.hyper[0:1].fill_(float(sd["Adam/learning_rate:0"]))
-            self.iterations = int(sd["Adam/iter:0"])
+                    tmp[i] = torch.from_numpy(sd[keras_names.optimizer_slot_names(k, prefix, slot_names)[slot]])
+                flat = net.flat_from_keras(tmp)
+                if init != 0:      # the channel padding has no Keras value: it keeps the slot's initial value, as in a fresh trainer
+                    real = net.flat_from_keras({i: torch.ones_like(t) for i, t in tmp.items()}) != 0
+                    flat = torch.where(real, flat, torch.full_like(flat, init))
+                buf.copy_(flat)
+            self.hyper[0:1].fill_(float(sd[f"{prefix}/learning_rate:0"]))
+            self.iterations = int(sd[f"{prefix}/iter:0"])
+        elif saved_by:
+            warnings.warn(f"checkpoint {path} holds {saved_by[0]} optimizer state but this trainer's optimizer is {self.optimizer}: "
+                          f"the model variables are restored and the {self.optimizer} state starts fresh")
+            self.reset_optimizer()
         if self.shadow is not None:
             trainable = [(k, i) for k, i in net.variable_table() if not i.endswith(("/moving_mean", "/moving_variance"))]
             if keras_names.moving_average_name(trainable[0][0]) in sd:
@@ -766,21 +837,22 @@ class Trainer:
 
     @property
     def iterations(self) -> int:
-        """Keras' ``optimizer.iterations``: optimiser steps taken so far (an int32 word on the device, bumped by fn_adam_tick)."""
+        """Keras' ``optimizer.iterations``: optimiser steps taken so far (an int32 word on the device, bumped by fn_adam_tick
+        under every rule)."""
         return int(self.hyper.view(torch.int32)[4].item())
 
     @iterations.setter
     def iterations(self, t: int):
         """Sets the step count and the beta powers that belong to it (what the NEXT tick will overwrite with t + 1)."""
         if t < 0:
-            raise ValueError(f"Adam iteration count must be >= 0, got {t}")
+            raise ValueError(f"iteration count must be >= 0, got {t}")
         self.hyper.view(torch.int32)[4:5].fill_(int(t))
         self.hyper[1:3].copy_(torch.tensor(adam_beta_powers(t, self.beta1, self.beta2)))
 
     def reset_optimizer(self, lr: Optional[float] = None):
-        """Adam as freshly constructed: zero moments, t = 0."""
-        self.M.zero_()
-        self.V.zero_()
+        """The optimizer as freshly constructed: every slot at its initial value (Adam: zero moments; Adagrad: 0.1), t = 0."""
+        for buf, (_, init) in zip(self.slots, self.rule.slots):
+            buf.fill_(init)
         self.iterations = 0
         if lr is not None:
             self.set_learning_rate(lr)

@@ -380,6 +380,23 @@ int fn_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long
 int fn_adam_keras_ema(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
                       float beta1, float beta2, float eps, float l2, int dtype, float* shadow, float decay, void* stream);
 int fn_adam_tick(float* hyper, float beta1, float beta2, void* stream);
+/* fn_opt_keras: the other update rules of train.optimizer, the Keras optimizers of the TF1 names, in one
+ * fused pass with the g, hyper (lr = word 0, grad_scale = word 3), n_decay and w_lp pack of fn_adam_keras.  rule = FN_OPT_*:
+ *   FN_OPT_ADAGRAD  s1 = accumulator                      a += g^2; w -= lr g / (sqrt(a) + eps)
+ *   FN_OPT_ADADELTA s1 = accum_grad, s2 = accum_var       ag = rho ag + (1-rho) g^2; u = sqrt(av+eps) / sqrt(ag+eps) g; w -= lr u;
+ *                                                         av = rho av + (1-rho) u^2
+ *   FN_OPT_RMSPROP  s1 = rms, s2 = momentum               ms = rho ms + (1-rho) g^2; mom = momentum mom + lr g / sqrt(ms+eps); w -= mom
+ *   FN_OPT_MOM      s1 = momentum (Nesterov)              acc = momentum acc - lr g; w += momentum acc - lr g
+ * Unused constants are ignored; s2 may be null for the one-slot rules.  fn_adam_tick still advances t (word 4) once per step.
+ * fn_opt_keras_ema: the same pass (w, slots, w_lp bit-identical) fused with the moving average of fn_adam_keras_ema. */
+#define FN_OPT_ADAGRAD 1
+#define FN_OPT_ADADELTA 2
+#define FN_OPT_RMSPROP 3
+#define FN_OPT_MOM 4
+int fn_opt_keras(int rule, float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                 float rho, float momentum, float eps, float l2, int dtype, void* stream);
+int fn_opt_keras_ema(int rule, float* w, const float* g, float* s1, float* s2, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
+                     float rho, float momentum, float eps, float l2, int dtype, float* shadow, float decay, void* stream);
 
 /* ---- weight packs ----------------------------------------------------------------------------------
  * table = device int32 [n_layers][8] {w_off, cout, ktot, taps, cin, bn_off(-1 none), fold_bias_off, 0}.
