@@ -20,6 +20,8 @@ CASES = [  # kind, H, W, C, N, scale, relu, repeat
     ("block35", 17, 17, 256, 32, 0.17, True, 1),
     ("block17", 8, 8, 896, 32, 0.10, True, 1),
     ("block17", 8, 8, 896, 32, 0.10, True, 3),   # a chain: the residual backward of block i runs in the epilogue of block i+1's data gradient
+    ("block35", 17, 17, 256, 32, 0.17, True, 2),  # ... merged over the three Block35 tower entries
+    ("block8", 3, 3, 1792, 48, 0.2, True, 2),     # ... on 3x3 maps (ragged row tiles)
     ("block8", 3, 3, 1792, 48, 0.2, True, 1),
     ("block8", 3, 3, 1792, 48, 1.0, False, 1),   # the last Block8: scale 1, no activation (:453)
     ("reduction_a", 17, 17, 256, 32, 0.0, True, 1),

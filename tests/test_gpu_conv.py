@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from facenet_amd import _lib
-from tests.util import ACC_GRAD_BITS, ACC_STAT_BITS, conv_desc, from_acc, lp_dtype, ptr, ref_conv, rel_err, stream, to_acc
+from tests.util import (ACC_GRAD_BITS, ACC_STAT_BITS, U_LP, assert_acc_sums, assert_elementwise, bitpattern, conv_desc, conv_fp64, dgrad_fp64,
+                        from_acc, gamma, lp_dtype, ptr, ref_conv, rel_err, same_bits, stream, to_acc)
 
 pytestmark = pytest.mark.gpu
 
@@ -192,7 +193,7 @@ TILE_CASES = [(2, 37, 37, 80, 192, 3, 3, 1, 0, 0),      # 4a: general gather, K 
               (2, 17, 17, 192, 192, 3, 3, 1, 1, 1)]     # 'same' padding
 
 
-@pytest.mark.parametrize("tile", [128128, 128064, 64128, 32032])
+@pytest.mark.parametrize("tile", [128128, 128064, 128032, 64128, 64064, 64032, 32128, 32064, 32032])
 @pytest.mark.parametrize("case", TILE_CASES)
 def test_conv_explicit_tiles(lib, case, tile):
     """Every tile a caller may pin (fn_conv_desc.tile_fwd / tile_dgrad) gives the convolution, its BatchNorm statistics and the
@@ -522,3 +523,511 @@ def test_dgrad_sibling_sources_equal_the_sum_of_single_dgrads(lib, dt, nsrc, til
     d.Cout2 = 33                                                    # not a multiple of 8
     with pytest.raises(ValueError):
         _lib.check(lib.fn_conv2d_dgrad(C.byref(d), stream()))
+
+
+# ---- element-wise bounds: grouped launches, the fused residual backward, every tile / split-K variant ------------------------
+# References are fp64 on the CPU from the operands the kernel reads; tests.util.assert_elementwise holds EVERY element to the
+# worst-case fp32-accumulation bound plus one rounding to the storage type, tests.util.assert_acc_sums the fixed-point sums.
+# Outputs start as NaN, bytes a launch must not touch hold tests.util.bitpattern and are compared bit for bit afterwards.
+
+def _pack_t(lib, w, dt):
+    """Transposed pack [Cin][tap][Cout] of w [Cout][kh][kw][Cin] (what the data gradient reads)."""
+    Cout, kh, kw, Cin = w.shape
+    wt = torch.zeros_like(w).view(-1)
+    table = torch.tensor([[0, Cout, kh * kw * Cin, kh * kw, Cin, -1, -1, 0]], dtype=torch.int32, device="cuda")
+    _lib.check(lib.fn_pack_transpose(ptr(w), ptr(wt), ptr(table), 1, w.numel(), dt, stream()))
+    return wt
+
+
+class _Buf:
+    """Low-precision buffer: claimed channel slices start as NaN (or a given base), everything else as a fixed bit pattern."""
+
+    def __init__(self, shape, dt):
+        self.t = torch.empty(shape, dtype=lp_dtype(dt), device="cuda")
+        self.init = bitpattern(shape, dt)
+        self.free = torch.ones(shape[-1], dtype=torch.bool, device="cuda")
+
+    def claim(self, c0, c, base=None):
+        assert bool(self.free[c0:c0 + c].all())
+        self.free[c0:c0 + c] = False
+        self.init[..., c0:c0 + c] = float("nan") if base is None else base
+
+    def reset(self):
+        self.t.copy_(self.init)
+
+    def check_untouched(self, what):
+        assert same_bits(self.t[..., self.free], self.init[..., self.free]), f"{what}: bytes outside the written slices changed"
+
+
+class _Acc:
+    """Fixed-point accumulators [replicas][2 * CB] (sum | sum of squares), zero outside the claimed columns."""
+
+    def __init__(self, reps, CB):
+        self.t = torch.zeros(reps, 2 * CB, dtype=torch.int64, device="cuda")
+        self.CB = CB
+        self.free = torch.ones(reps, 2 * CB, dtype=torch.bool, device="cuda")
+
+    def claim(self, off, c, reps, sq=True):
+        for o in ((off, off + self.CB) if sq else (off,)):
+            assert bool(self.free[:reps, o:o + c].all())
+            self.free[:reps, o:o + c] = False
+
+    def reset(self):
+        self.t.zero_()
+
+    def check_untouched(self, what):
+        assert int(self.t[self.free].abs().sum()) == 0, f"{what}: accumulators outside the claimed columns changed"
+
+
+def _geo(geo):
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw = geo
+    return N, H, W, Cin, Cout, kh, kw, s, ph, pw, (H + 2 * ph - kh) // s + 1, (W + 2 * pw - kw) // s + 1
+
+
+def _tiles(M):
+    return (M + 31) // 32 + 4          # workgroups that can add into one column of a fixed-point sum (any tile, parity classes)
+
+
+class _Layer:
+    """One convolution launch (forward op 0 / data gradient op 1) with its fp64 reference and its checks."""
+
+    def __init__(self, op, d, keep, checks, bufs):
+        self.op, self.d, self.keep, self.checks, self.bufs = op, d, keep, checks, bufs
+
+    def launch(self, lib):
+        _lib.check((lib.fn_conv2d_fwd if self.op == 0 else lib.fn_conv2d_dgrad)(C.byref(self.d), stream()))
+
+    def check(self, what):
+        for c in self.checks:
+            c(what)
+
+
+def _fwd_layer(lib, dt, geo, seed, out, c0=0, x=None, x_c0=0, stats=None, bias=False, resid=False, scale=1.0, relu=0, tile=0):
+    """out: _Buf receiving channels [c0, c0 + Cout); x: shared input buffer (channels [x_c0, x_c0 + Cin)); stats: (_Acc, offset, replicas)."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(geo)
+    if x is None:
+        x = _mk((N, H, W, Cin), dt, seed=seed)
+    w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=seed + 1)
+    d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=x.shape[-1], ld_y=out.t.shape[-1])
+    d.x, d.w, d.y, d.relu, d.tile_fwd = ptr(x, x_c0), ptr(w), ptr(out.t, c0), relu, tile
+    out.claim(c0, Cout)
+    conv, aconv = conv_fp64(x[..., x_c0:x_c0 + Cin], w, s, ph, pw)
+    ref, aref, keep = conv, aconv, [x, w]
+    if bias:
+        b = (torch.randn(Cout, generator=torch.Generator().manual_seed(seed + 2)) * 0.5).cuda()
+        d.bias = ptr(b)
+        keep.append(b)
+        ref, aref = ref + b.double().cpu(), aref + b.double().abs().cpu()
+    if resid:
+        r = _mk((N, OH, OW, Cout), dt, seed=seed + 3)
+        d.resid, d.ld_res, d.scale = ptr(r), Cout, scale
+        keep.append(r)
+        ref, aref = r.double().cpu() + scale * ref, r.double().abs().cpu() + abs(scale) * aref
+    if relu:
+        ref = ref.clamp_min(0)
+    K = kh * kw * Cin
+    checks = [lambda what: assert_elementwise(out.t[..., c0:c0 + Cout], ref, aref, K + 3, dt, what + ": y")]
+    bufs = [out]
+    if stats is not None:
+        acc, off, reps = stats
+        acc.claim(off, Cout, reps)
+        d.stats, d.stats_sq_off, d.stats_replicas, d.stats_rep_stride = ptr(acc.t, off), acc.CB, reps, 2 * acc.CB
+        bufs.append(acc)
+        M = N * OH * OW
+        y, e = conv.reshape(M, Cout), gamma(K) * aconv.reshape(M, Cout)       # the un-rounded fp32 accumulators and their error
+
+        def chk_stats(what):
+            s_, q_ = acc.t[:, off:off + Cout].sum(0), acc.t[:, acc.CB + off:acc.CB + off + Cout].sum(0)
+            assert_acc_sums(s_, y.sum(0), y.abs().sum(0), ACC_STAT_BITS, _tiles(M), what + ": sum", term_err=e.sum(0))
+            qe = 2 * y.abs() * e + e * e + 2.0 ** -24 * (y.abs() + e) ** 2
+            assert_acc_sums(q_, (y * y).sum(0), (y * y).sum(0), ACC_STAT_BITS, _tiles(M), what + ": sum of squares", term_err=qe.sum(0))
+        checks.append(chk_stats)
+    return _Layer(0, d, keep, checks, bufs)
+
+
+def _dgrad_layer(lib, dt, geo, seed, out, c0=0, accumulate=0, bn=None, tile=0, siblings=(), rb=None):
+    """out: _Buf receiving dX channels [c0, c0 + Cin); accumulate: dX adds to a random base; bn: (_Acc, offset, replicas, relu)
+    for the fused BatchNorm-backward reduction of the layer that produced x; siblings: Cout of the 1x1 sources dy2 / dy3;
+    rb: the fused residual backward (see _fuse_rb)."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(geo)
+    dy = _mk((N, OH, OW, Cout), dt, seed=seed)
+    w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=seed + 1)
+    wt = _pack_t(lib, w, dt)
+    d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=out.t.shape[-1])
+    d.y, d.w, d.dx, d.accumulate, d.tile_dgrad = ptr(dy), ptr(wt), ptr(out.t, c0), accumulate, tile
+    g, ag = dgrad_fp64(dy, w, H, W, s, ph, pw)
+    ref, aref, keep = g, ag, [dy, w, wt]
+    K = kh * kw * Cout
+    for i, c2 in enumerate(siblings):          # sibling 1x1 layers reading the same x: their products join the same GEMM
+        dyi, wi = _mk((N, OH, OW, c2), dt, seed=seed + 10 + i), _mk((c2, 1, 1, Cin), dt, 0.1, seed=seed + 20 + i)
+        wti = _pack_t(lib, wi, dt)
+        setattr(d, ("dy2", "dy3")[i], ptr(dyi)); setattr(d, ("w2", "w3")[i], ptr(wti))
+        setattr(d, ("Cout2", "Cout3")[i], c2); setattr(d, ("ld_y2", "ld_y3")[i], c2)
+        gi, agi = dgrad_fp64(dyi, wi, H, W, 1, 0, 0)
+        ref, aref, K = ref + gi, aref + agi, K + c2
+        keep += [dyi, wi, wti]
+    if rb is not None:
+        return _fuse_rb(lib, dt, d, out, c0, ref, aref, K, seed, keep, **rb)
+    if accumulate:
+        base = _mk((N, H, W, Cin), dt, seed=seed + 2)
+        out.claim(c0, Cin, base)
+        ref, aref = ref + base.double().cpu(), aref + base.double().abs().cpu()
+    else:
+        out.claim(c0, Cin)
+    checks = [lambda what: assert_elementwise(out.t[..., c0:c0 + Cin], ref, aref, K + 2, dt, what + ": dx")]
+    bufs = [out]
+    if bn is not None:
+        acc, off, reps, relu = bn
+        acc.claim(off, Cin, reps)
+        M = N * H * W
+        yraw = _mk((N, H, W, Cin), dt, seed=seed + 3, scale=2.0)
+        gen = torch.Generator().manual_seed(seed + 4)
+        sc = (torch.rand(Cin, generator=gen) + 0.5).cuda()
+        sh = (torch.randn(Cin, generator=gen) * 0.5).cuda()
+        beta = (torch.randn(Cin, generator=gen) * 0.3).cuda()
+        d.bn_y, d.ld_bn_y, d.bn_scale, d.bn_shift, d.bn_beta = ptr(yraw), Cin, ptr(sc), ptr(sh), ptr(beta)
+        d.bn_acc, d.bn_sq_off, d.bn_replicas, d.bn_rep_stride, d.bn_relu = ptr(acc.t, off), acc.CB, reps, 2 * acc.CB, relu
+        keep += [yraw, sc, sh, beta]
+        bufs.append(acc)
+        z = yraw.double().cpu().reshape(M, Cin) * sc.double().cpu() + sh.double().cpu()      # fma(y, scale, shift) before its rounding
+        keep_m = (z > 0).double() if relu else torch.ones_like(z)
+        gm, e = g.reshape(M, Cin) * keep_m, gamma(K) * ag.reshape(M, Cin) * keep_m         # the un-rounded fp32 gradient
+        zb = z - beta.double().cpu()
+        zab = z.abs() + beta.double().abs().cpu()
+        u = 2.0 ** -24
+
+        def chk_bn(what):
+            s_, q_ = acc.t[:, off:off + Cin].sum(0), acc.t[:, acc.CB + off:acc.CB + off + Cin].sum(0)
+            assert_acc_sums(s_, gm.sum(0), gm.abs().sum(0), ACC_GRAD_BITS, _tiles(M), what + ": sum dyh", term_err=e.sum(0))
+            qe = e * zab + (gm.abs() + e) * 4 * u * zab
+            assert_acc_sums(q_, (gm * zb).sum(0), (gm * zb).abs().sum(0), ACC_GRAD_BITS, _tiles(M), what + ": sum dyh*xhat", term_err=qe.sum(0))
+        checks.append(chk_bn)
+    return _Layer(1, d, keep, checks, bufs)
+
+
+def _plain_bits(d, op):
+    return int(d.KH == 1 and d.KW == 1 and d.stride == 1 and d.pad_h == 0 and d.pad_w == 0) | (2 if op == 0 and d.nrm_stats else 0)
+
+
+def _group(lib, layers, dt):
+    """The grouped launch train.group_convs builds for these layers: records of fn_conv2d_arg_bytes(), the prefix array and
+    the LDS size fn_conv2d_group_build returns."""
+    n, op = len(layers), layers[0].op
+    variant = lib.fn_conv2d_variant(C.byref(layers[0].d), op)
+    assert all(lib.fn_conv2d_variant(C.byref(L.d), op) == variant for L in layers), [lib.fn_conv2d_variant(C.byref(L.d), op) for L in layers]
+    plain = _plain_bits(layers[0].d, op)
+    descs = (_lib.ConvDesc * n)(*[L.d for L in layers])
+    host_args, host_prefix, smem = (C.c_uint8 * (lib.fn_conv2d_arg_bytes() * n))(), (C.c_int32 * (n + 1))(), C.c_int32(0)
+    total = lib.fn_conv2d_group_build(descs, n, op, variant, host_args, host_prefix, C.byref(smem))
+    if total < 0:
+        _lib.check(total, "conv_group_build")
+    prefix = list(host_prefix)
+    assert prefix[0] == 0 and prefix[-1] == total and all(b > a for a, b in zip(prefix, prefix[1:]))
+    dev_args = torch.frombuffer(bytearray(host_args), dtype=torch.uint8).cuda()
+    dev_prefix = torch.tensor(prefix, dtype=torch.int32, device="cuda")
+
+    def run():
+        _lib.check(lib.fn_conv2d_grouped(ptr(dev_args), ptr(dev_prefix), n, total, variant, plain, smem.value, dt, stream()))
+    return run, variant, prefix
+
+
+def _check_group(lib, layers, dt, what):
+    """Single launches, then the grouped launch twice: every buffer bit-equal, every layer within the element-wise bound, bytes
+    outside the layers' slices untouched.  Returns (variant, prefix)."""
+    bufs = list({id(b): b for L in layers for b in L.bufs}.values())
+
+    def snap(fn):
+        for b in bufs:
+            b.reset()
+        fn()
+        torch.cuda.synchronize()
+        return [b.t.clone() for b in bufs]
+    single = snap(lambda: [L.launch(lib) for L in layers])
+    run, variant, prefix = _group(lib, layers, dt)
+    first, second = snap(run), snap(run)
+    for i, (b, s, g1, g2) in enumerate(zip(bufs, single, first, second)):
+        assert same_bits(g1, s), f"{what}: buffer {i} of the grouped launch differs from the single launches"
+        assert same_bits(g2, g1), f"{what}: buffer {i} differs between two grouped launches"
+    for i, L in enumerate(layers):
+        L.check(f"{what}, layer {i}")
+    for i, b in enumerate(bufs):
+        b.check_untouched(f"{what}, buffer {i}")
+    return variant, prefix
+
+
+def _fwd_group(lib, dt, kind):
+    if kind == "fwd_1x1_heads":        # Block35's three tower-entry 1x1 layers: one input, channel slices of one buffer, replicas
+        x = _mk((2, 17, 17, 256), dt, seed=100)
+        y, st = _Buf((2, 17, 17, 104), dt), _Acc(4, 128)
+        return [_fwd_layer(lib, dt, (2, 17, 17, 256, 32, 1, 1, 1, 0, 0), 101 + 10 * i, y, c0=8 + 32 * i, x=x, stats=(st, 40 * i, 4 - i))
+                for i in range(3)]
+    if kind == "fwd_kxk":              # general gathers in one launch (ragged M = 162), ReLU / bias on members >= 1
+        y1, y2, st = _Buf((2, 9, 9, 80), dt), _Buf((2, 9, 9, 64), dt), _Acc(2, 64)
+        return [_fwd_layer(lib, dt, (2, 9, 9, 64, 32, 1, 7, 1, 0, 3), 110, y1, c0=0, stats=(st, 0, 2)),
+                _fwd_layer(lib, dt, (2, 9, 9, 64, 32, 7, 1, 1, 3, 0), 120, y1, c0=40, bias=True, relu=1),
+                _fwd_layer(lib, dt, (2, 9, 9, 48, 32, 3, 3, 1, 1, 1), 130, y2, c0=0, relu=1),
+                _fwd_layer(lib, dt, (2, 19, 19, 48, 32, 3, 3, 2, 0, 0), 140, y2, c0=32, bias=True, stats=(st, 32, 1))]
+    if kind == "fwd_up":               # the blocks' `up` layers: bias, residual, scale, with and without ReLU
+        x = _mk((3, 8, 8, 96), dt, seed=150)
+        y = _Buf((3, 8, 8, 200), dt)
+        return [_fwd_layer(lib, dt, (3, 8, 8, 96, 64, 1, 1, 1, 0, 0), 151, y, c0=0, x=x, bias=True, resid=True, scale=0.17, relu=1),
+                _fwd_layer(lib, dt, (3, 8, 8, 96, 64, 1, 1, 1, 0, 0), 161, y, c0=64, x=x, bias=True, resid=True, scale=0.1),
+                _fwd_layer(lib, dt, (3, 8, 8, 96, 64, 1, 1, 1, 0, 0), 171, y, c0=136, x=x, bias=True, relu=1)]
+    if kind == "fwd_64x64_ks2":        # in-launch split-K (tile pinned as the autotuner pins it)
+        y, st = _Buf((3, 8, 8, 136), dt), _Acc(2, 136)
+        return [_fwd_layer(lib, dt, (3, 8, 8, 128, 64, 1, 7, 1, 0, 3), 180, y, c0=0, stats=(st, 0, 2), tile=64064),
+                _fwd_layer(lib, dt, (3, 8, 8, 128, 64, 7, 1, 1, 3, 0), 190, y, c0=72, bias=True, relu=1, tile=64064)]
+    raise KeyError(kind)
+
+
+def _dgrad_group(lib, dt, kind):
+    if kind == "dgrad_8":              # eight layers, one of them a single workgroup: accumulate, fused BN reduction, stride 2
+        a, b, c = _Buf((2, 9, 9, 112), dt), _Buf((2, 19, 19, 40), dt), _Buf((1, 3, 3, 32), dt)
+        bn = _Acc(3, 96)
+        return [_dgrad_layer(lib, dt, (2, 9, 9, 32, 48, 3, 3, 1, 1, 1), 200, a, c0=0),
+                _dgrad_layer(lib, dt, (2, 9, 9, 32, 48, 3, 3, 1, 1, 1), 210, a, c0=32, accumulate=1),
+                _dgrad_layer(lib, dt, (2, 9, 9, 24, 48, 3, 3, 1, 1, 1), 220, a, c0=64, bn=(bn, 0, 3, 1)),
+                _dgrad_layer(lib, dt, (2, 9, 9, 16, 32, 1, 7, 1, 0, 3), 230, a, c0=96, bn=(bn, 32, 2, 0)),
+                _dgrad_layer(lib, dt, (2, 19, 19, 32, 48, 3, 3, 2, 0, 0), 240, b, c0=0),
+                _dgrad_layer(lib, dt, (2, 19, 19, 8, 32, 3, 3, 2, 0, 0), 250, b, c0=32, accumulate=1),
+                _dgrad_layer(lib, dt, (2, 9, 9, 32, 48, 7, 1, 1, 3, 0), 260, _Buf((2, 9, 9, 32), dt), bn=(bn, 56, 1, 1)),
+                _dgrad_layer(lib, dt, (1, 3, 3, 32, 32, 3, 3, 1, 1, 1), 270, c)]
+    if kind == "dgrad_32x64_ks4":        # in-launch split-K, with a fused residual backward member
+        a = _Buf((2, 8, 8, 208), dt)
+        return [_dgrad_layer(lib, dt, (2, 8, 8, 64, 160, 1, 7, 1, 0, 3), 280, a, c0=0, tile=32064),
+                _dgrad_layer(lib, dt, (2, 8, 8, 128, 128, 3, 3, 1, 1, 1), 290, a, c0=72, accumulate=1, tile=32064),
+                _dgrad_layer(lib, dt, (2, 8, 8, 64, 160, 1, 7, 1, 0, 3), 295, _Buf((2, 8, 8, 80), dt), c0=8, tile=32064,    # single-source rb_*
+                             rb=dict(prev=True, mask=True, acc=0, scale=0.17))]
+    raise KeyError(kind)
+
+
+GROUPS = {"fwd_1x1_heads": (32032, 3), "fwd_kxk": (32032, 4), "fwd_up": (32032, 3), "fwd_64x64_ks2": (2064064, 2),
+          "dgrad_8": (32032, 8), "dgrad_32x64_ks4": (4032064, 3)}
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("kind", list(GROUPS))
+def test_grouped_convolutions_match_single_launches(lib, kind, dt):
+    """fn_conv2d_grouped (how Trainer.step runs same-level forward / data-gradient convolutions of one tile variant) == the
+    members' own fn_conv2d_fwd / fn_conv2d_dgrad launches bit for bit -- outputs, BatchNorm statistics over replicas, fused
+    BatchNorm-backward sums -- the same bits on a second launch, every element within the fp64 bound, neighbours untouched."""
+    layers = _fwd_group(lib, dt, kind) if kind.startswith("fwd") else _dgrad_group(lib, dt, kind)
+    variant, prefix = _check_group(lib, layers, dt, kind)
+    assert (variant, len(layers)) == GROUPS[kind]
+    if kind == "dgrad_8":
+        assert min(b - a for a, b in zip(prefix, prefix[1:])) == 1          # a member with a single workgroup
+
+
+def test_conv_group_build_rejects_mixed_members(lib):
+    """Layers that cannot share a grouped launch are refused at build time (ValueError), never launched."""
+    dt = _lib.FN_BF16
+
+    def desc(geo, dtype=dt, **kw):
+        d = conv_probe(conv_desc(*geo, dtype))
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def build(descs, op):
+        n = len(descs)
+        variant = lib.fn_conv2d_variant(C.byref(descs[0]), op)
+        return lib.fn_conv2d_group_build((_lib.ConvDesc * n)(*descs), n, op, variant, (C.c_uint8 * (lib.fn_conv2d_arg_bytes() * n))(),
+                                         (C.c_int32 * (n + 1))(), C.byref(C.c_int32(0)))
+    one, kxk = (2, 9, 9, 64, 32, 1, 1, 1, 0, 0), (2, 9, 9, 64, 32, 3, 3, 1, 1, 1)
+    assert build([desc(one), desc(one)], 0) > 0 and build([desc(kxk), desc(kxk)], 1) > 0        # the well-formed groups build
+    st = torch.zeros(256, dtype=torch.int64, device="cuda")
+    norm = dict(nrm_stats=ptr(st), nrm_beta=ptr(st), nrm_count=162, nrm_eps=1e-3, nrm_sq_off=64)
+    sib = dict(dy2=4096, w2=4096, Cout2=32, ld_y2=32)
+    cases = {"mixed dtypes": ([desc(one), desc(one, _lib.FN_F16)], 0),
+             "1x1 with general": ([desc(one), desc((2, 9, 9, 64, 32, 3, 1, 1, 1, 0))], 0),
+             "normalise-on-load with plain": ([desc(one, **norm), desc(one)], 0),
+             "another variant": ([desc(one), desc(one, tile_fwd=64064)], 0),
+             "sibling sources": ([desc(one), desc(one, **sib)], 1),
+             "halo kernel": ([desc(kxk), desc(kxk, tile_dgrad=HALO)], 1)}
+    for what, (descs, op) in cases.items():
+        with pytest.raises(ValueError):
+            _lib.check(build(descs, op), what)
+
+
+def _fuse_rb(lib, dt, d, out, c0, g, ag, K, seed, keep, prev=True, mask=True, acc=0, scale=0.17, positive=False, rb_bufs=None):
+    """Sets fn_conv_desc.rb_* on data-gradient descriptor d (fp64 gradient g, |.| sums ag, K products) and returns the _Layer
+    checking the contract of include/facenet_hip.h against fp64:
+        total = rb_prev + g,  m = total * [rb_out > 0],  rb_dtrunk (+)= m,  rb_dup = rb_scale * m,  rb_dbias += sum_pixels rb_dup.
+    dx (`out` at c0) must keep its bits.  rb_bufs: (dtrunk _Buf, dup _Buf, dbias _Acc, dbias offset) to share buffers; by default
+    they get dx's geometry and channel offset."""
+    N, H, W, Cin = d.N, d.H, d.W, d.Cin
+    M = N * H * W
+    shape = tuple(out.t.shape)
+    dtr, dup, dbias, boff = rb_bufs or (_Buf(shape, dt), _Buf(shape, dt), _Acc(1, Cin), 0)
+    p = _mk((N, H, W, Cin), dt, seed=seed + 5) if prev else None
+    o = _mk((N, H, W, Cin), dt, seed=seed + 6) if mask else None
+    if positive:
+        o = o.abs() + 0.5
+    base = _mk((N, H, W, Cin), dt, seed=seed + 7) if acc else None
+    pb = _Buf(shape, dt)                                  # rb_prev / rb_out live in buffers of dx's geometry too
+    ob = _Buf(shape, dt)
+    if prev:
+        pb.init[..., c0:c0 + Cin] = p
+    if mask:
+        ob.init[..., c0:c0 + Cin] = o
+    pb.reset(); ob.reset()
+    dtr.claim(c0, Cin, base)
+    dup.claim(c0, Cin)
+    dbias.claim(boff, Cin, 1, sq=False)
+    d.rb_prev = ptr(pb.t, c0) if prev else None
+    d.rb_out = ptr(ob.t, c0) if mask else None
+    d.rb_dtrunk, d.rb_dup, d.rb_dbias, d.rb_scale, d.rb_accumulate = ptr(dtr.t, c0), ptr(dup.t, c0), ptr(dbias.t, boff), scale, acc
+    keep += [pb, ob, p, o, base]
+    tot, atot = (g + p.double().cpu(), ag + p.double().abs().cpu()) if prev else (g, ag)
+    mk = (o.double().cpu() > 0).double() if mask else torch.ones_like(tot)
+    m, am = tot * mk, atot * mk
+    t_ref, t_abs = (m + base.double().cpu(), am + base.double().abs().cpu()) if acc else (m, am)
+    Mv, e = m.reshape(M, Cin) * scale, abs(scale) * (gamma(K + 2) * am.reshape(M, Cin))
+    te = e + 2.0 ** -24 * (Mv.abs() + e)                  # error of the fp32 terms rb_scale * m that rb_dbias sums
+
+    def checks(what):
+        got_t, got_u = dtr.t[..., c0:c0 + Cin], dup.t[..., c0:c0 + Cin]
+        assert_elementwise(got_t, t_ref, t_abs, K + 3, dt, what + ": rb_dtrunk")
+        assert_elementwise(got_u, scale * m, abs(scale) * am, K + 4, dt, what + ": rb_dup")
+        off = mk == 0                                      # masked elements are exactly zero
+        assert float(got_u.float().cpu()[off].abs().sum()) == 0, what + ": rb_dup not exactly 0 under the mask"
+        if not acc:
+            assert float(got_t.float().cpu()[off].abs().sum()) == 0, what + ": rb_dtrunk not exactly 0 under the mask"
+        assert_acc_sums(dbias.t[0, boff:boff + Cin], Mv.sum(0), Mv.abs().sum(0), ACC_GRAD_BITS, _tiles(M), what + ": rb_dbias",
+                        term_err=te.sum(0))
+    L = _Layer(1, d, keep, [checks], [out, dtr, dup, dbias, pb, ob])
+    L.rb = dict(prev=p, mask=o, acc=acc, scale=scale, dtr=dtr, dup=dup, dbias=dbias, boff=boff, c0=c0, M=M)
+    return L
+
+
+def _unfused(lib, dt, L):
+    """The sequence the fusion replaces: the data gradient accumulated onto rb_prev, then fn_residual_bwd (dx contiguous)."""
+    d, r = _lib.ConvDesc.from_buffer_copy(L.d), L.rb
+    N, H, W, Cin = d.N, d.H, d.W, d.Cin
+    dx = r["prev"].clone() if r["prev"] is not None else torch.zeros(N, H, W, Cin, dtype=lp_dtype(dt), device="cuda")
+    d.rb_prev = d.rb_out = d.rb_dtrunk = d.rb_dup = d.rb_dbias = None
+    d.dx, d.accumulate = ptr(dx), 1
+    _lib.check(lib.fn_conv2d_dgrad(C.byref(d), stream()))
+    dtr = r["dtr"].init.clone() if r["acc"] else torch.zeros_like(dx)
+    dup = torch.zeros_like(dx)
+    dbias = torch.zeros(Cin, dtype=torch.int64, device="cuda")
+    mask = r["mask"]
+    _lib.check(lib.fn_residual_bwd(ptr(dx), ptr(mask) if mask is not None else None, ptr(dtr), ptr(dup), ptr(dbias), r["M"], Cin,
+                                   r["scale"], 1 if mask is not None else 0, r["acc"], dt, stream()))
+    torch.cuda.synchronize()
+    return dtr, dup, dbias
+
+
+def _run_rb(lib, L, dt, what):
+    """One fused launch from fresh buffers: the contract against fp64, dx untouched, rb_dbias the same bits on a second run, and
+    within one rounding of dx of the unfused sequence (rb_dtrunk bit for bit when it is not accumulated)."""
+    bufs = list({id(b): b for b in L.bufs}.values())
+    runs = []
+    for _ in range(2):
+        for b in bufs:
+            b.reset()
+        L.launch(lib)
+        torch.cuda.synchronize()
+        runs.append([b.t.clone() for b in bufs])
+    for i, (a, b) in enumerate(zip(*runs)):
+        assert same_bits(a, b), f"{what}: buffer {i} differs between two runs"
+    L.check(what)
+    for i, b in enumerate(bufs):
+        b.check_untouched(f"{what}, buffer {i}")          # dx (buffer 0) is not written at all
+    r = L.rb
+    c0, Cin = r["c0"], L.d.Cin
+    if L.d.ld_x != Cin:
+        return
+    dtr_u, dup_u, dbias_u = _unfused(lib, dt, L)
+    got_t, got_u = r["dtr"].t[..., c0:c0 + Cin], r["dup"].t[..., c0:c0 + Cin]
+    u, s = U_LP[dt], abs(r["scale"])
+    tu = dtr_u.double().cpu() - (r["dtr"].init.double().cpu() if r["acc"] else 0)      # the masked gradient, rounded once
+    if not r["acc"]:
+        assert same_bits(got_t, dtr_u), f"{what}: rb_dtrunk differs from the unfused sequence"
+    else:
+        assert bool(((got_t.double().cpu() - dtr_u.double().cpu()).abs() <= 2.01 * u * (tu.abs() + dtr_u.double().cpu().abs()) + 1e-7).all()), what
+    du = dup_u.double().cpu().abs()                        # |rb_scale * m| within (1 + u)^2: one rounding of dx, one of the product
+    assert bool(((got_u.double().cpu() - dup_u.double().cpu()).abs() <= 3.1 * u * du + 1e-7).all()), what + ": rb_dup vs unfused"
+    db, dbu = r["dbias"].t[0, r["boff"]:r["boff"] + Cin].double().cpu(), dbias_u.double().cpu()
+    tol = (1.1 * u + 2 * gamma(r["M"])) * du.reshape(-1, Cin).sum(0) + 2 * r["M"] * 2.0 ** -ACC_GRAD_BITS
+    assert bool(((db - dbu).abs() * 2.0 ** -ACC_GRAD_BITS <= tol).all()), what + ": rb_dbias vs unfused"
+
+
+RB_BLOCKS = {"block35": (2, 17, 17, 256, [32, 32, 32], 0.17), "block17": (2, 8, 8, 896, [128, 128], 0.10),
+             "block8": (5, 3, 3, 1792, [192, 192], 0.2)}      # block8: N*H*W = 45 rows, ragged in every tile
+RB_CASES = [(b, n) for b, v in RB_BLOCKS.items() for n in range(1, len(v[4]) + 1)]
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("tile", [0, 128064, 64064, 32032, 32128])
+@pytest.mark.parametrize("block,nsrc", RB_CASES)
+def test_dgrad_fused_residual_backward_production_flags(lib, block, nsrc, tile, dt):
+    """The residual backward in the epilogue of the merged sibling data gradient (engine._fuse_residual) with the flags
+    production sets (rb_prev, rb_out, rb_accumulate = 0): 1-3 sources at the widths of Block35 / Block17 / Block8."""
+    N, H, W, Cin, couts, scale = RB_BLOCKS[block]
+    L = _dgrad_layer(lib, dt, (N, H, W, Cin, couts[0], 1, 1, 1, 0, 0), 300, _Buf((N, H, W, Cin), dt), tile=tile, siblings=couts[1:nsrc],
+                     rb=dict(prev=True, mask=True, acc=0, scale=scale))
+    _run_rb(lib, L, dt, f"{block} x{nsrc} tile {tile}")
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+def test_dgrad_fused_residual_backward_all_flags(lib, dt):
+    """Every combination of rb_out (NULL: no activation), rb_prev (NULL: nothing carried) and rb_accumulate (1 leaves the
+    dedicated epilogue path for the generic one), on a two-source Block17 data gradient; with rb_prev = NULL, rb_out > 0
+    everywhere and no accumulation, rb_dtrunk is the plain data gradient of the same tile bit for bit."""
+    geo, sib = (2, 8, 8, 896, 128, 1, 1, 1, 0, 0), [128]
+    for prev in (True, False):
+        for mask in (True, False):
+            for acc in (0, 1):
+                L = _dgrad_layer(lib, dt, geo, 400, _Buf((2, 8, 8, 896), dt), siblings=sib, rb=dict(prev=prev, mask=mask, acc=acc, scale=0.1))
+                _run_rb(lib, L, dt, f"prev {prev} mask {mask} acc {acc}")
+    L = _dgrad_layer(lib, dt, geo, 400, _Buf((2, 8, 8, 896), dt), siblings=sib, rb=dict(prev=False, mask=True, acc=0, scale=0.1, positive=True))
+    _run_rb(lib, L, dt, "rb_out > 0")
+    plain = _lib.ConvDesc.from_buffer_copy(L.d)
+    plain.rb_prev = plain.rb_out = plain.rb_dtrunk = plain.rb_dup = plain.rb_dbias = None
+    dx = torch.full((2, 8, 8, 896), float("nan"), dtype=lp_dtype(dt), device="cuda")
+    plain.dx = ptr(dx)
+    _lib.check(lib.fn_conv2d_dgrad(C.byref(plain), stream()))
+    torch.cuda.synchronize()
+    assert same_bits(dx, L.rb["dtr"].t)
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("layer", ["stride2", "halo"])
+def test_dgrad_fused_residual_backward_single_source_layers(lib, layer, dt):
+    """rb_* on the single-source data gradients the ABI allows besides the 1x1 siblings: a 3x3 stride-2 layer (parity classes,
+    row table) and a 3x3 layer on the halo-tile kernel; dx a channel slice of a wider buffer."""
+    geo, tile = {"stride2": ((2, 17, 17, 64, 64, 3, 3, 2, 0, 0), 0), "halo": ((1, 37, 37, 32, 32, 3, 3, 1, 1, 1), HALO)}[layer]
+    for acc in (0, 1):
+        N, H, W, Cin = geo[:4]
+        L = _dgrad_layer(lib, dt, geo, 500, _Buf((N, H, W, Cin + 16), dt), c0=8, tile=tile, rb=dict(prev=True, mask=True, acc=acc, scale=0.2))
+        assert (lib.fn_conv2d_variant(C.byref(L.d), 1) >= 9000000) == (layer == "halo")
+        _run_rb(lib, L, dt, f"{layer} acc {acc}")
+        L = _dgrad_layer(lib, dt, geo, 500, _Buf((N, H, W, Cin), dt), tile=tile, rb=dict(prev=True, mask=True, acc=acc, scale=0.2))
+        _run_rb(lib, L, dt, f"{layer} acc {acc}, contiguous")
+
+
+SPLITK = [  # (BM, BN, KS), the layer: 3x3 'same' with Cin == Cout on 9x9 maps (M = 162: ragged row tiles), forward == dgrad GEMM shape
+    (32, 128, 2, 128), (32, 64, 2, 64), (32, 64, 4, 128), (32, 32, 2, 64), (32, 32, 4, 128), (64, 64, 2, 64), (64, 32, 2, 64)]
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("bm,bn,ks,c", SPLITK)
+def test_conv_split_k_variants(lib, bm, bn, ks, c, dt):
+    """Every in-launch split-K variant the library heuristic picks for a pinned tile (the autotuner pins tiles; the ks choice is
+    the heuristic's): fn_conv2d_variant must name exactly this variant -- a heuristic change cannot drop the coverage silently --
+    then forward + BatchNorm statistics and the data gradient + fused BatchNorm reduction, element by element against fp64.
+    (64x64 / 64x32 four-way split-K are reachable only through FN_CONV_KS64_4, read once per process: not covered here.)"""
+    geo, tile = (2, 9, 9, c, c, 3, 3, 1, 1, 1), bm * 1000 + bn
+    st, bn_acc = _Acc(2, c), _Acc(3, c)
+    f = _fwd_layer(lib, dt, geo, 600, _Buf((2, 9, 9, c), dt), stats=(st, 0, 2), tile=tile)
+    g = _dgrad_layer(lib, dt, geo, 610, _Buf((2, 9, 9, c), dt), bn=(bn_acc, 0, 3, 1), tile=tile)
+    for L in (f, g):
+        assert lib.fn_conv2d_variant(C.byref(L.d), L.op) == ks * 1000000 + tile
+        for b in L.bufs:
+            b.reset()
+        L.launch(lib)
+        torch.cuda.synchronize()
+        L.check(f"{bm}x{bn} ks {ks} op {L.op}")
+        for b in L.bufs:
+            b.check_untouched(f"{bm}x{bn} ks {ks} op {L.op}")

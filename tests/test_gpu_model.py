@@ -266,3 +266,40 @@ def test_autotuned_plan_matches_heuristic_plan(monkeypatch, tmp_path):
     d = (_rel(results[2][0], results[0][0]), _rel(results[2][1], results[0][1]))
     # other tiles = another summation order; a batch-6 BatchNorm network amplifies the last-bit differences to a few per cent
     assert d[0] <= 5e-3 and d[1] <= 8e-2, d
+
+
+GROUPED_STEP_GRAD_BOUND = 1e-2      # measured 3.6e-3 (the Block17 `up` biases); rb_scale off by 5 % in the fusion gives 7e-2
+
+
+def test_grouped_and_fused_step_matches_the_unfused_step(monkeypatch):
+    """The launches Trainer.step issues -- grouped forward / data-gradient convolutions (train.group_convs), merged sibling data
+    gradients and the residual backward fused into their epilogue (engine._fuse_residual) -- against the plain lowering
+    (FACENET_FUSE_RESIDUAL_BWD=0, FACENET_MERGE_SIBLINGS=0, Trainer(group_wgrad=False)), one f16 step at batch 6.  Grouping
+    changes no forward bit and the fusion is backward only, so loss and embeddings are identical; the gradients differ by
+    summation order and one rounding of the fused data gradients."""
+    E, N = 128, 6
+    params, _, _ = fo.build_params(E, seed=0)
+    from tests.util import structured_images
+    x = torch.from_numpy(structured_images(N, seed=7))
+    results = []
+    for prod in (True, False):
+        monkeypatch.setenv("FACENET_FUSE_RESIDUAL_BWD", "1" if prod else "0")
+        monkeypatch.setenv("FACENET_MERGE_SIBLINGS", "1" if prod else "0")
+        net = Network(embedding_size=E, device="cuda:0", train_dtype=torch.float16)
+        net.load_keras_params(params)
+        tr = Trainer(net, batch=N, loss="triplet", alpha=0.2, lr=0.01, group_wgrad=prod)
+        tr.set_images(x)
+        names = [op.name for op in tr.step_ops]
+        # 21 residual blocks; fused: every block whose output feeds merged sibling 1x1 data gradients (the next block's towers,
+        # Reduction-B's three 1x1 towers); left: the last Block35 (Reduction-A has one 1x1 tower) and the last Block8 (avg pool)
+        assert sum(n.startswith("residual_bwd") for n in names) == (2 if prod else 21)
+        grouped = sum(n.startswith(("conv_fwd_grouped", "conv_dgrad_grouped")) for n in names)
+        assert (grouped > 0) == prod, grouped
+        tr.step_eager()
+        torch.cuda.synchronize()
+        results.append((tr.loss_value(), tr.emb.clone(), net.export_keras_grads(tr.G)))
+    assert results[0][0] == results[1][0] and torch.equal(results[0][1], results[1][1])
+    diffs = sorted(((_rel(results[0][2][k], results[1][2][k]), k) for k in results[1][2] if float(results[1][2][k].norm()) > 0), reverse=True)
+    worst = diffs[0]
+    print("largest per-variable gradient differences (relative L2):", diffs[:5])
+    assert worst[0] <= GROUPED_STEP_GRAD_BOUND, worst
