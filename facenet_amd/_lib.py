@@ -99,6 +99,7 @@ _SIGNATURES = {
     "fn_select_triplets": [_p, _p, _i, _f, _i, _u, _i, _p, _p, _p],
     "fn_triplet_loss_fwd_bwd": [_p, _p, _p, _i, _i, _f, _p],
     "fn_confidence_counts": [_p, _p, _i, _i, _p, _i, _i, _p, _p, _p],
+    "fn_confidence_counts_folds": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_softmax_xent_fwd_bwd": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _f, _i, _p],
     "fn_center_loss_fwd_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p],
     "fn_center_update": [_p, _i, _i, _i, _p, _i, C.c_double, _p],

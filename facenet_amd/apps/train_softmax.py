@@ -54,10 +54,11 @@ def init_distributed():
 
 
 def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 512, device: str = "cuda", use_graph: bool = True,
-                  world_size: int = 1, process_group=None, rank: int = 0, log=print):
+                  world_size: int = 1, process_group=None, rank: int = 0, log=print, validation=None):
     """``cfg.batch_size`` is the GLOBAL batch: MirroredStrategy splits it across the replicas
     (apps/train_softmax_tf2_gpus.py:49-108), so every rank trains ``cfg.batch_size // world_size`` images per step with
-    per-replica BatchNorm, gradients are averaged over the global batch, and ``batches`` must yield this rank's shard."""
+    per-replica BatchNorm, gradients are averaged over the global batch, and ``batches`` must yield this rank's shard.
+    ``validation``: a facenet_amd.callbacks.ValidateCallback (:41-45,85-88), called after every epoch on every rank."""
     if cfg.batch_size % world_size:
         raise ValueError(f"batch_size {cfg.batch_size} is not divisible by the {world_size} replicas")
     local_batch = cfg.batch_size // world_size
@@ -73,6 +74,8 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
                       **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p")})
     if rank == 0 and optimizer != "ADAM":                        # once; an Adam run logs exactly what it always did
         log(f"optimizer: {optimizer}")
+    if validation is not None and validation.model is None:      # ValidateCallback(model=network, ...) of :85-88
+        validation.attach(trainer, path=cfg.model.path if cfg.model.path else None, rank=rank, world=world_size, process_group=process_group)
     first_epoch = 0
     if cfg.model.checkpoint:                                      # network.load_weights(checkpoint) before fit (:68-71)
         ckpt = Path(cfg.model.checkpoint).expanduser()
@@ -113,6 +116,8 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
                 if rank == 0:
                     (path / "averaged").mkdir(exist_ok=True)
                 trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
+        if validation is not None:                                # after ModelCheckpoint, as in the reference's callback list
+            validation.on_epoch_end(epoch)
     return net, trainer
 
 
@@ -149,6 +154,8 @@ def main(**options):
     cfg = config_mod.load_config(options["config"])
     rank, world, pg, device = init_distributed()                  # python -m torch.distributed.run --nproc-per-node N -m facenet_amd.apps.train_softmax
     kw = dict(device=device, world_size=world, process_group=pg, rank=rank)
+    from facenet_amd import callbacks
+    kw["validation"] = callbacks.from_config(cfg, rank=rank)     # None unless validate.dataset.path is set
     if cfg.dataset.path:
         train_dbase, batches = dataset_batches(cfg, rank, world)
         train_softmax(cfg, train_dbase.nrof_classes, batches, **kw)

@@ -24,7 +24,9 @@ from facenet_amd.schedule import make_events
 
 
 def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 4, nrof_triplets: int = 30, embedding_size: int = 128,
-                      pools=None, device: str = "cuda", use_graph: bool = True, world_size: int = 1, process_group=None, log=print):
+                      pools=None, device: str = "cuda", use_graph: bool = True, world_size: int = 1, process_group=None, log=print,
+                      validation=None):
+    """``validation``: a facenet_amd.callbacks.ValidateCallback, called after every epoch on every rank."""
     alpha = cfg.loss.alpha if cfg.loss.alpha else 0.2
     optimizer = optimizer_name(cfg)                               # train.optimizer: checked before any GPU work
     # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
@@ -35,6 +37,9 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
                       process_group=process_group, moving_average_decay=moving_average_decay(cfg), optimizer=optimizer)
     if trainer.rank == 0 and optimizer != "ADAM":                # once; an Adam run logs exactly what it always did
         log(f"optimizer: {optimizer}")
+    if validation is not None and validation.model is None:
+        validation.attach(trainer, path=cfg.model.path if cfg.model.path else None, rank=trainer.rank, world=world_size,
+                          process_group=process_group)
     n = people_per_batch * images_per_person
     miner = TripletMiner(net, n, np.repeat(np.arange(people_per_batch), images_per_person), nrof_triplets, alpha=alpha, seed=cfg.seed)
     miner.build(trainer.plan.images)
@@ -65,6 +70,8 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
             if trainer.rank == 0:
                 (path / "averaged").mkdir(parents=True, exist_ok=True)
             trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
+        if validation is not None:
+            validation.on_epoch_end(epoch)
     return net, trainer
 
 
@@ -85,12 +92,14 @@ def dataset_pools(cfg, log=print, **kw):
 @click.option("--config", default=None, type=Path, help="Path to yaml config file with used options of the application.")
 def main(**options):
     cfg = config_mod.load_config(options["config"])
+    from facenet_amd import callbacks
+    validation = callbacks.from_config(cfg)                      # None unless validate.dataset.path is set
     if cfg.dataset.path:
         pipe = dataset_pools(cfg)
         train_tripletloss(cfg, people_per_batch=cfg.nrof_classes_per_batch, images_per_person=cfg.nrof_examples_per_class,
-                          pools=(images for images, _ in pipe))
+                          pools=(images for images, _ in pipe), validation=validation)
     else:
-        train_tripletloss(cfg)
+        train_tripletloss(cfg, validation=validation)
 
 
 if __name__ == "__main__":

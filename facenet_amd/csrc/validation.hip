@@ -105,8 +105,220 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
     }
 }
 
+// ---- the count tables of all F training parts of a k-fold validation in ONE pass over the pairs ------------------------
+// A pair of rows held out in folds fa and fb belongs to the training part of every fold except fa and fb, so per class
+// pair   hist(training part f) = total - touch_f   with touch_f the histogram of the pairs with fa == f or fb == f.
+// Every pair adds 1 to touch[fa] and 1 to touch[fb] (fa != fb) or to touch[fa] and `same` (fa == fb): two LDS atomics
+// spread over the folds' rows, and total = (sum_f touch_f + same) / 2 comes out in the epilogue.
+//
+// Dot products run on v_mfma_f32_16x16x4_f32, which is bit for bit the ascending-k fmaf chain of confidence_kernel (a
+// zero-padded k adds fma(0, 0, acc) = acc), so both kernels bin identical distances.  One workgroup walks class pairs
+// with a stride (diagonal pairs and off-diagonal pairs in separate workgroups), covers each pair with 64x64 super-tiles
+// (wave w: rows 16w..16w+15 against four 16x16 column tiles, empty tiles skipped) and keeps the weighted fp64 tables in
+// LDS until it has seen all its pairs: the global fp64 atomics happen once per workgroup, not once per class pair.
+constexpr int OT = 64;          // rows / columns of a super-tile
+constexpr int OE = 32;          // embedding chunk
+constexpr int OLD = OE + 4;     // LDS row stride in floats: 16-byte aligned rows, conflict-free ds_read_b128 per 16 lanes
+constexpr int OMAXF = 16;       // folds
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Column c of a chunk goes to LDS position opos(c): inside each block of 16 the 4x4 (step, lane group) index is
+// transposed, so that the float4 a lane of group g reads holds k = 4s + g for the four MFMA steps s = 0..3 in order.
+__device__ __forceinline__ int opos(int c) { return (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3); }
+
+__device__ __forceinline__ void stage_rows(float (*dst)[OLD], const float* __restrict__ src, int rows, int E, int e0, bool vec, int tid) {
+    if (vec) {                                            // E % 4 == 0: rows are 16-byte aligned
+        for (int t = tid; t < OT * (OE / 4); t += 256) {
+            const int r = t >> 3, c = (t & 7) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < rows && e0 + c < E) v = *reinterpret_cast<const float4*>(src + (long)r * E + e0 + c);
+            const int p = opos(c);                        // c % 4 == 0: the four elements are lane groups 0..3 of one step
+            dst[r][p] = v.x; dst[r][p + 4] = v.y; dst[r][p + 8] = v.z; dst[r][p + 12] = v.w;
+        }
+    } else {
+        for (int t = tid; t < OT * OE; t += 256) {
+            const int r = t >> 5, c = t & 31;
+            dst[r][opos(c)] = (r < rows && e0 + c < E) ? src[(long)r * E + e0 + c] : 0.f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __restrict__ emb, const int* __restrict__ cls_start,
+                                                               const int* __restrict__ fold, const int* __restrict__ train_rows,
+                                                               const int* __restrict__ train_classes, int C, int E, int F,
+                                                               const float* __restrict__ thr, int T, int metric, double* __restrict__ out,
+                                                               int* __restrict__ range, int diag_groups, int off_groups) {
+    extern __shared__ __align__(16) unsigned char dyn[];
+    __shared__ __align__(16) float sA[OT][OLD], sB[OT][OLD];
+    __shared__ float sThr[VMAXT];
+    __shared__ double sP[OMAXF], sW[OMAXF];
+    const int HS = T + 1;
+    int* sHist = reinterpret_cast<int*>(dyn);                                          // [F + 1][T + 1]; row F: `same`, then total
+    double* sAcc = reinterpret_cast<double*>(dyn + ((((F + 1) * HS * 4) + 15) & ~15));  // [F][2][T]: count / w, (P - count) / w
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int t = tid; t < T; t += 256) sThr[t] = thr[t];
+    for (int t = tid; t < F * 2 * T; t += 256) sAcc[t] = 0.0;
+    const bool diag = (int)blockIdx.x < diag_groups;
+    const long npairs = diag ? (long)C : (long)C * (C - 1) / 2;
+    const long stride = diag ? diag_groups : off_groups;
+    const bool vec = (E & 3) == 0;
+    const int lr = lane & 15, lg = lane >> 4;
+    float lo = 3e38f, hi = -3e38f;
+    for (long b = diag ? (long)blockIdx.x : (long)blockIdx.x - diag_groups; b < npairs; b += stride) {
+        int i, k;
+        if (diag) {
+            i = k = (int)b;
+        } else {                                          // b = j (j + 1) / 2 + k with k <= j, i = j + 1 > k
+            int j = (int)((sqrtf(8.f * (float)b + 1.f) - 1.f) * 0.5f);
+            while ((long)j * (j + 1) / 2 > b) --j;
+            while ((long)(j + 1) * (j + 2) / 2 <= b) ++j;
+            k = (int)(b - (long)j * (j + 1) / 2);
+            i = j + 1;
+        }
+        const int a0 = cls_start[i], na = cls_start[i + 1] - a0;
+        const int b0 = cls_start[k], nb = cls_start[k + 1] - b0;
+        if (diag && na < 2) continue;                     // no pair at all
+        __syncthreads();                                  // the previous pair's epilogue has read the histograms
+        for (int t = tid; t < (F + 1) * HS; t += 256) sHist[t] = 0;
+        if (tid < F) {                                    // statistics.py:91-101,126-127 for the training part of fold tid
+            const long ma = train_rows[(long)i * F + tid], mb = train_rows[(long)k * F + tid];
+            const long P = diag ? ma * (ma - 1) / 2 : ma * mb;
+            const int Cf = train_classes[tid];
+            sP[tid] = (double)P;
+            sW[tid] = (double)P * (diag ? (double)Cf : (double)Cf * (Cf - 1) * 0.5);
+        }
+        for (int ta = 0; ta < na; ta += OT)
+            for (int tb = 0; tb < nb; tb += OT) {
+                if (diag && tb + OT - 1 <= ta) continue;  // super-tile entirely on/below the diagonal
+                const int r0 = ta + wave * 16;            // this wave's 16 rows
+                bool live[4];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    const int c0 = tb + ct * 16;
+                    live[ct] = r0 < na && c0 < nb && !(diag && c0 + 15 <= r0);
+                }
+                f32x4 acc[4];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int e0 = 0; e0 < E; e0 += OE) {
+                    __syncthreads();
+                    stage_rows(sA, emb + (long)(a0 + ta) * E, na - ta, E, e0, vec, tid);
+                    stage_rows(sB, emb + (long)(b0 + tb) * E, nb - tb, E, e0, vec, tid);
+                    __syncthreads();
+#pragma unroll
+                    for (int blk = 0; blk < OE / 16; ++blk) {
+                        const f32x4 av = *reinterpret_cast<const f32x4*>(&sA[wave * 16 + lr][blk * 16 + lg * 4]);
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct) {
+                            if (!live[ct]) continue;      // wave-uniform
+                            const f32x4 bv = *reinterpret_cast<const f32x4*>(&sB[ct * 16 + lr][blk * 16 + lg * 4]);
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc[ct], 0, 0, 0);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    if (!live[ct]) continue;
+                    const int ib = tb + ct * 16 + lr;     // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register
+                    const int fb = ib < nb ? fold[b0 + ib] : 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ia = r0 + lg * 4 + r;
+                        if (ia >= na || ib >= nb || (diag && ib <= ia)) continue;      // strict upper triangle (:32-34)
+                        const int fa = fold[a0 + ia];
+                        const float s = acc[ct][r];
+                        if (F >= 3 || fa == fb) {         // the pair is in at least one training part
+                            lo = fminf(lo, s);
+                            hi = fmaxf(hi, s);
+                        }
+                        const float sc = fminf(fmaxf(s, -1.f), 1.f);                    // :45-46
+                        const float d = (metric == 0) ? 2.f * (1.f - sc) : acosf(sc);   // :48-53
+                        int l = 0, h = T;                                               // first n with thr[n] > d
+                        while (l < h) {
+                            const int m = (l + h) >> 1;
+                            if (sThr[m] > d) h = m; else l = m + 1;
+                        }
+                        atomicAdd(&sHist[fa * HS + l], 1);
+                        atomicAdd(&sHist[(fa == fb ? F : fb) * HS + l], 1);
+                    }
+                }
+            }
+        __syncthreads();
+        for (int l = tid; l <= T; l += 256) {             // total = (sum of the touch rows + same) / 2
+            int s = sHist[F * HS + l];
+            for (int f = 0; f < F; ++f) s += sHist[f * HS + l];
+            sHist[F * HS + l] = s >> 1;
+        }
+        __syncthreads();
+        for (int row = wave; row <= F; row += 4) {        // inclusive prefix over the bins: count(sims < thr[n])
+            int carry = 0;
+            for (int base = 0; base < T; base += 64) {
+                const int l = base + lane;
+                int v = l < T ? sHist[row * HS + l] : 0;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int u = __shfl_up(v, o);
+                    if (lane >= o) v += u;
+                }
+                v += carry;
+                if (l < T) sHist[row * HS + l] = v;
+                carry = __shfl(v, 63);
+            }
+        }
+        __syncthreads();
+        for (int t = tid; t < F * T; t += 256) {          // entry t belongs to this thread for every pair: no race on sAcc
+            const int f = t / T, n = t - f * T;
+            const double P = sP[f];
+            if (P < 1.0) continue;                        // statistics.py:126-127
+            const double c = (double)(sHist[F * HS + n] - sHist[f * HS + n]);
+            sAcc[(f * 2 + 0) * T + n] += c / sW[f];
+            sAcc[(f * 2 + 1) * T + n] += (P - c) / sW[f];
+        }
+    }
+    lo = -wave_max(-lo);
+    hi = wave_max(hi);
+    if (lane == 0 && range) {
+        atomicMin(&range[0], f2ord_i2(lo));
+        atomicMax(&range[1], f2ord_i2(hi));
+    }
+    __syncthreads();                                      // a workgroup whose pairs were all empty reads the zeros others wrote
+    for (int t = tid; t < F * T; t += 256) {
+        const int f = t / T, n = t - f * T;
+        const double c = sAcc[(f * 2 + 0) * T + n], r = sAcc[(f * 2 + 1) * T + n];
+        double* o = out + (long)f * 4 * T + n;
+        if (c != 0.0) atomicAdd(o + (diag ? 0 : 2) * T, c);      // tp | fp
+        if (r != 0.0) atomicAdd(o + (diag ? 3 : 1) * T, r);      // fn | tn
+    }
+}
+
 }  // namespace fn
 using namespace fn;
+
+extern "C" int fn_confidence_counts_folds(const float* emb, const int32_t* cls_start, const int32_t* fold, const int32_t* train_rows,
+                                          const int32_t* train_classes, int C, int E, int F, const float* thresholds, int T, int metric,
+                                          double* out, int32_t* range, void* stream) {
+    FN_REQUIRE(emb && cls_start && fold && train_rows && train_classes && thresholds && out && C > 0 && E > 0 && T > 0 && T <= VMAXT &&
+                   F >= 2 && F <= OMAXF,
+               "confidence_counts_folds: bad arguments (T <= 256, 2 <= folds <= 16)");
+    FN_REQUIRE(metric == 0 || metric == 1, "Undefined similarity metric %d", metric);   // statistics.py:258-260
+    FN_REQUIRE(C < 65536, "confidence_counts_folds: too many classes");
+    hipStream_t st = (hipStream_t)stream;
+    fill_words(out, 0u, 0u, 2 * F * 4 * T, st);
+    if (range) fill_words(range, 0x7f7fffffu, 0x80800000u, 2, st);
+    const long off_pairs = (long)C * (C - 1) / 2;
+    const int diag_groups = C < 256 ? C : 256;
+    const int off_groups = (int)(off_pairs < 2048 ? off_pairs : 2048);
+    const size_t dyn = (size_t)((((F + 1) * (T + 1) * 4) + 15) & ~15) + (size_t)F * 2 * T * sizeof(double);
+    if (dyn > 40 * 1024) {   // beyond the default 64 KiB per workgroup together with the static tiles
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(confidence_folds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        FN_REQUIRE(e == hipSuccess, "confidence_counts_folds: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(confidence_folds_kernel, dim3((unsigned)(diag_groups + off_groups)), dim3(256), dyn, st, emb, cls_start, fold, train_rows,
+                       train_classes, C, E, F, thresholds, T, metric, out, (int*)range, diag_groups, off_groups);
+    return check_launch("confidence_counts_folds");
+}
 
 extern "C" int fn_confidence_counts(const float* emb, const int32_t* cls_start, int C, int E, const float* thresholds, int T, int metric,
                                     double* out, int32_t* range, void* stream) {

@@ -113,6 +113,14 @@ class ConfidenceMatrix:
         if hi >= lo and (lo < -(1 + atol) or hi > 1 + atol):   # some pair was evaluated and left [-1, 1]: statistics.py:40-42
             raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
 
+    @classmethod
+    def from_counts(cls, counts, threshold):
+        """A matrix over an existing [4, T] table (rows tp / tn / fp / fn), e.g. one fold of fn_confidence_counts_folds."""
+        self = cls.__new__(cls)
+        self.threshold = np.array(threshold, ndmin=1)
+        self.counts = np.asarray(counts, dtype=np.float64).reshape(4, self.threshold.size)
+        return self
+
     def __getattr__(self, name):        # tp, tn, fp, fn are views of the count table
         row = ConfidenceMatrix._ROWS.get(name)
         if row is None or "counts" not in self.__dict__:
@@ -217,14 +225,76 @@ class Report:
         return head + body + '\n'
 
 
+ONE_PASS_MAX_FOLDS = 16            # fn_confidence_counts_folds: 2 <= folds <= 16, thresholds <= 256
+ONE_PASS_MAX_THRESHOLDS = 256
+
+
+def kfold_assignment(nrof_images: int, nrof_folds: int):
+    """(fold [n]: the fold of KFold(nrof_folds, shuffle=True, random_state=0) each image index is held out in, the list of
+    (train, test) index arrays of that split)."""
+    from sklearn.model_selection import KFold
+    splits = list(KFold(n_splits=nrof_folds, shuffle=True, random_state=0).split(np.arange(nrof_images)))
+    fold = np.empty(nrof_images, dtype=np.int32)
+    for f, (_, test_set) in enumerate(splits):
+        fold[test_set] = f
+    return fold, splits
+
+
+def fold_tables(labels, fold, nrof_folds: int):
+    """Host tables of fn_confidence_counts_folds for rows sorted by label (stable): (order, class_start [C+1], fold of the
+    sorted rows [n], train_rows [C, F] = rows of class c not held out in fold f, train_classes [F] = classes with such a row)."""
+    labels, fold = np.asarray(labels), np.asarray(fold)
+    if fold.shape != labels.shape or (fold.size and (fold.min() < 0 or fold.max() >= nrof_folds)):
+        raise ValueError("fold must hold one index in [0, {}) per label".format(nrof_folds))
+    order = np.argsort(labels, kind="stable")
+    _, cls, counts = np.unique(labels[order], return_inverse=True, return_counts=True)
+    held_out = np.zeros((len(counts), nrof_folds), dtype=np.int64)
+    np.add.at(held_out, (cls, fold[order]), 1)
+    train_rows = counts[:, None] - held_out
+    class_start = np.concatenate([[0], np.cumsum(counts)])
+    return (order, class_start.astype(np.int32), fold[order].astype(np.int32), train_rows.astype(np.int32),
+            (train_rows > 0).sum(axis=0).astype(np.int32))
+
+
+def confidence_counts_folds(calculator: SimilarityCalculator, fold_sorted, train_rows, train_classes, thresholds, atol: float = 1.e-5):
+    """[F, 4, T] count tables (tp / tn / fp / fn) of the F training parts from ONE fn_confidence_counts_folds launch over the
+    calculator's rows (sorted by class); raises the reference's ValueError when a pair of some training part leaves [-1, 1]."""
+    lib = _lib.load()
+    thr = np.array(thresholds, ndmin=1).astype(np.float32)
+    if thr.size > 1 and not np.all(np.diff(thr) >= 0):
+        raise ValueError("thresholds must be ascending")
+    F = int(len(train_classes))
+    n, E = calculator.emb.shape
+    if np.shape(train_rows) != (calculator.nrof_classes, F) or np.shape(fold_sorted) != (n,):
+        raise ValueError("fold tables do not match the calculator's rows and classes")
+    dev = calculator.emb.device
+    as_dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+    t_dev, fold_dev = as_dev(thr, np.float32), as_dev(fold_sorted, np.int32)
+    rows_dev, classes_dev = as_dev(train_rows, np.int32), as_dev(train_classes, np.int32)
+    out = torch.zeros(F * 4 * thr.size, dtype=torch.float64, device=dev)
+    rng = torch.zeros(2, dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.fn_confidence_counts_folds(_ptr(calculator.emb), _ptr(calculator._cls), _ptr(fold_dev), _ptr(rows_dev), _ptr(classes_dev),
+                                              calculator.nrof_classes, E, F, _ptr(t_dev), thr.size, calculator.metric, _ptr(out), _ptr(rng), st),
+               "confidence_counts_folds")
+    counts = out.cpu().numpy().reshape(F, 4, thr.size)
+    lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
+    if hi >= lo and (lo < -(1 + atol) or hi > 1 + atol):        # statistics.py:40-42
+        raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+    return counts
+
+
 class FaceToFaceValidation:
     """Interface of statistics.py:237-331: k-fold (KFold(shuffle=True, random_state=0) over image indices); per fold the
     max-accuracy and the FAR-target thresholds are chosen on the training part and scored on the held-out part.
-    ``config``: .metric, .nrof_folds, .far_target.  Embeddings stay on the device; every matrix is one kernel launch."""
+    ``config``: .metric, .nrof_folds, .far_target.  Embeddings stay on the device.  The count tables of all training parts
+    come from one fn_confidence_counts_folds launch over all rows; the held-out matrices are one
+    fn_confidence_counts launch each.  Outside the kernel's range (folds > 16) every training part is a launch of its own,
+    which is also what ``one_pass=False`` selects: the reference path of the tests and of tools/bench_validation.py."""
 
     _UPPER = {0: 4, 1: np.pi}       # largest possible similarity value per metric (statistics.py:253-258)
 
-    def __init__(self, embeddings, labels, config, device: str = "cuda"):
+    def __init__(self, embeddings, labels, config, device: str = "cuda", one_pass: bool = True):
         import time
         t0 = time.monotonic()
         self.config = config
@@ -237,6 +307,7 @@ class FaceToFaceValidation:
         self.thresholds = np.linspace(0, self._UPPER[config.metric], 100)
         self.reports = (Report(criterion='MaximumAccuracy'),
                         Report(criterion='FalseAlarmRate(FAR = {})'.format(config.far_target)))
+        self.one_pass = bool(one_pass) and 2 <= config.nrof_folds <= ONE_PASS_MAX_FOLDS and len(self.thresholds) <= ONE_PASS_MAX_THRESHOLDS
         self._evaluate()
         self.elapsed_time = time.monotonic() - t0
 
@@ -253,10 +324,16 @@ class FaceToFaceValidation:
         return best, far
 
     def _evaluate(self):
-        from sklearn.model_selection import KFold
-        folds = KFold(n_splits=self.config.nrof_folds, shuffle=True, random_state=0)
-        for train_set, test_set in folds.split(np.arange(len(self.labels))):
-            fitted = ConfidenceMatrix(self._calculator(train_set), self.thresholds)
+        fold, splits = kfold_assignment(len(self.labels), self.config.nrof_folds)
+        if self.one_pass:
+            _, _, fold_sorted, train_rows, train_classes = fold_tables(self.labels, fold, self.config.nrof_folds)
+            everything = SimilarityCalculator(self.embeddings, self.labels, metric=self.config.metric, device=str(self.embeddings.device))
+            tables = confidence_counts_folds(everything, fold_sorted, train_rows, train_classes, self.thresholds)
+        for f, (train_set, test_set) in enumerate(splits):
+            if self.one_pass:
+                fitted = ConfidenceMatrix.from_counts(tables[f], self.thresholds)
+            else:
+                fitted = ConfidenceMatrix(self._calculator(train_set), self.thresholds)
             held_out = self._calculator(test_set)
             for report, thr in zip(self.reports, self._fold_thresholds(fitted)):
                 report.append_fold('train', fitted)

@@ -19,6 +19,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import os
@@ -465,6 +466,7 @@ class Trainer:
         self._graph = None
         self._exchange_events: Optional[dict] = None     # set by exchange_profile() around a step
         self._eval_plans: Dict[int, Tuple[Lowering, torch.Tensor]] = {}   # evaluate(): inference plan + output per batch size
+        self._average_in_place = False      # inside averaged_weights(): P holds the moving average
 
     def _op(self, lst, name, fn, *args, keep=(), r=(), w=()):
         lst.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
@@ -801,6 +803,26 @@ class Trainer:
         if self.rank == 0:
             np.savez(path, **{k: v.numpy() for k, v in variables.items()})
 
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block ``P`` holds the moving average: ``evaluate(..., averaged=True)`` calls swap and refold ONCE for the
+        whole block instead of once per call (a validation pass over many batches).  ``P`` is restored bit for bit on exit and
+        the fold is left to be redone; no training step may run inside the block."""
+        self._require_average()
+        if self._average_in_place:
+            raise RuntimeError("averaged_weights() blocks do not nest")
+        net = self.net
+        saved = net.P.clone()
+        net.P.copy_(self.shadow)
+        net.folded_valid = False
+        self._average_in_place = True
+        try:
+            yield self
+        finally:
+            self._average_in_place = False
+            net.P.copy_(saved)
+            net.folded_valid = False           # the fold holds the average: the next raw inference refolds
+
     def evaluate(self, images, averaged: bool = False) -> torch.Tensor:
         """L2-normalised inference embeddings [N, E] of uint8 NHWC images through the network's inference plan, from the raw
         weights or (``averaged``) from the moving average with this replica's moving statistics.  The inference plans read
@@ -812,6 +834,8 @@ class Trainer:
             raise ValueError(f"expected uint8 images [N,{S},{S},3], got {x.dtype} {tuple(x.shape)}")
         if averaged:
             self._require_average()
+        elif self._average_in_place:
+            raise RuntimeError("inside averaged_weights() the raw weights are swapped out: evaluate with averaged=True")
         n = x.shape[0]
         if n > 256:      # the per-plan batch limit of inference (InceptionResnetV1.MAX_PLAN_BATCH)
             return torch.cat([self.evaluate(x[i:i + 256], averaged) for i in range(0, n, 256)])
@@ -822,7 +846,7 @@ class Trainer:
         plan.images.copy_(x.to(net.device))
         saved = None
         try:
-            if averaged:
+            if averaged and not self._average_in_place:
                 saved = net.P.clone()
                 net.P.copy_(self.shadow)
                 net.folded_valid = False

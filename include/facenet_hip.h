@@ -321,6 +321,15 @@ int fn_triplet_loss_fwd_bwd(const float* emb, float* demb, float* loss, int T, i
 int fn_confidence_counts(const float* emb, const int32_t* cls_start, int C, int E, const float* thresholds, int T, int metric,
                          double* out, int32_t* range, void* stream);
 
+/* The tables of all F training parts of a k-fold validation in one pass over the pairs.  fold int32 [n]: the fold a row
+ * is held out in (0 <= fold < F, 2 <= F <= 16); train_rows int32 [C*F]: rows of class c that are NOT held out in fold f;
+ * train_classes int32 [F]: classes with at least one such row.  out fp64 [F*4*T]: out[f] is what fn_confidence_counts
+ * gives for the rows with fold != f (classes without such a row removed); range covers the pairs that belong to at
+ * least one training part.  Dot products are the same fp32 fmaf chains as fn_confidence_counts (exact fp32 MFMA). */
+int fn_confidence_counts_folds(const float* emb, const int32_t* cls_start, const int32_t* fold, const int32_t* train_rows,
+                               const int32_t* train_classes, int C, int E, int F, const float* thresholds, int T, int metric,
+                               double* out, int32_t* range, void* stream);
+
 /* ---- softmax classifier loss: apps/train_softmax.py:91 (SparseCategoricalCrossentropy(from_logits)); loss: fp32[4] as above;
  * dbias (optional): fixed point, FN_ACC_GRAD_BITS, += column sums of dlogits */
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
