@@ -125,11 +125,9 @@ __global__ __launch_bounds__(256) void gather_images_kernel(const uint8_t* __res
     const int i = blockIdx.y;
     const uint8_t* s = pool + (long)idx[i] * bytes;
     uint8_t* d = out + (long)i * bytes;
-    const int nvec = bytes >> 4;
+    const int nvec = bytes >> 4;        // the host requires bytes % 16 == 0: whole 16-byte vectors, no byte tail
     for (int k = blockIdx.x * 256 + threadIdx.x; k < nvec; k += gridDim.x * 256)
         reinterpret_cast<u32x4*>(d)[k] = reinterpret_cast<const u32x4*>(s)[k];
-    if (blockIdx.x == 0)
-        for (int k = (nvec << 4) + threadIdx.x; k < bytes; k += 256) d[k] = s[k];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -889,7 +887,9 @@ extern "C" int fn_crop_or_pad_u8(const uint8_t* src, const long long* offsets, c
 }
 
 extern "C" int fn_gather_images(const uint8_t* pool, const int32_t* idx, uint8_t* out, int n_out, int bytes, void* stream) {
-    FN_REQUIRE(pool && idx && out && n_out > 0 && bytes > 0 && bytes % 16 == 0, "gather_images: bad arguments");
+    FN_REQUIRE(pool && idx && out && n_out > 0 && bytes > 0, "gather_images: bad arguments");
+    FN_REQUIRE(bytes % 16 == 0, "gather_images: %d bytes per image is not a multiple of 16 (images are copied as 16-byte vectors; "
+               "an odd image size such as 299 x 299 x 3 is not supported)", bytes);
     hipLaunchKernelGGL(gather_images_kernel, dim3(8, n_out), dim3(256), 0, (hipStream_t)stream, pool, idx, out, bytes);
     return check_launch("gather_images");
 }
@@ -941,6 +941,7 @@ extern "C" int fn_bn_relu_train_bwd(void* dz, int ld_d, const void* y, int ld_y,
     DT_CHECK(dtype);
     FN_REQUIRE(dz && y && beta && save_scale && save_shift && dbeta && acc && M > 0 && C > 0 && C % 8 == 0 && ld_d % 8 == 0 &&
                    ld_y % 8 == 0 && C <= 4096, "bn_bwd: bad arguments");
+    FN_REQUIRE(ld_d >= C && ld_y >= C, "bn_bwd: row strides ld_d = %d, ld_y = %d must be >= C = %d", ld_d, ld_y, C);
     FN_REQUIRE((long)M * ld_d * 2 < (1L << 31), "bn_bwd: dz exceeds the 2 GiB range of the 32-bit byte offsets its stores use");
     hipStream_t st = (hipStream_t)stream;
     const int reps = acc_replicas > 0 ? acc_replicas : 1;

@@ -907,6 +907,14 @@ class Trainer:
         return {"xent": xent, "center_loss": center, "prelogits_norm": norm, "loss": total}
 
 
+def check_gather_bytes(bytes_per_image: int) -> int:
+    """fn_gather_images copies whole 16-byte vectors; say so when the miner is built, not in the middle of a step."""
+    if bytes_per_image <= 0 or bytes_per_image % 16 != 0:
+        raise ValueError(f"{bytes_per_image} bytes per image is not a multiple of 16: the triplet batch is gathered as 16-byte vectors "
+                         "(an odd image size such as 299 x 299 x 3 is not supported)")
+    return bytes_per_image
+
+
 class TripletMiner:
     """Embeds a PxK pool with the inference path, selects triplets on device and assembles the train batch."""
 
@@ -945,7 +953,7 @@ class TripletMiner:
         """train_images: the uint8 [3T,H,W,3] input buffer of the training plan (filled by the gather)."""
         net, lib, n, E = self.net, self.net.lib, self.n, self.net.E
         o = self.ops
-        bytes_per = train_images[0].numel()
+        bytes_per = check_gather_bytes(train_images[0].numel() * train_images.element_size())
         o.append(Op("fold_bn", lambda st: (net.refresh_folded(st), 0)[1], (),
                     reads=(region(net.P), region(net.S_mean), region(net.S_var)), writes=(region(net.W_infer), region(net.fold_bias))))
         net.refresh_folded(net.stream())          # the inference pack must exist before launches are timed

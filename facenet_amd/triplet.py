@@ -21,9 +21,16 @@ def squared_distances(emb: torch.Tensor) -> torch.Tensor:
 
 def select_triplets(dist: torch.Tensor, labels, alpha: float, nrof_triplets: int, seed: int = 0, semi_hard: bool = False):
     """Returns (triplets int32 [T,3] on device, info dict).  Raises ValueError when the pool has too few positive pairs."""
-    lib = _lib.load()
+    lab_host = np.asarray(labels)
     n = dist.shape[0]
-    lab = torch.as_tensor(np.asarray(labels), dtype=torch.int32).to(dist.device)
+    if lab_host.shape != (n,):
+        raise ValueError(f"labels must have one entry per row of dist ({n}), got {lab_host.shape}")
+    # a pool of one identity has anchor-positive pairs but no negative for any of them: the kernel would leave every triplet slot
+    # unwritten and the zero-filled buffer below would pass for a selection
+    if len(np.unique(lab_host)) < 2:
+        raise ValueError("triplet selection needs at least two identities in the pool: every row carries the same label, so no pair has a negative")
+    lib = _lib.load()
+    lab = torch.as_tensor(lab_host, dtype=torch.int32).to(dist.device)
     trip = torch.zeros(nrof_triplets, 3, dtype=torch.int32, device=dist.device)
     info = torch.zeros(8 + 5 * (n * (n - 1) // 2), dtype=torch.int32, device=dist.device)
     _lib.check(lib.fn_select_triplets(_ptr(dist.contiguous()), _ptr(lab), n, float(alpha), nrof_triplets, int(seed) & 0xFFFFFFFF,

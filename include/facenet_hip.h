@@ -205,7 +205,9 @@ typedef struct fn_augment_param {
  * one launch; S must be even.  Sizes are not checked against the src allocation: the caller owns the packing. */
 int fn_augment_u8(const uint8_t* src, const long long* offsets, const int32_t* hw, const fn_augment_param* params, uint8_t* dst, int N,
                   int S, void* stream);
-/* gather rows of a u8 image pool by index (triplet batch assembly): out[i] = pool[idx[i]] */
+/* gather rows of a u8 image pool by index (triplet batch assembly): out[i] = pool[idx[i]].  bytes_per_image must be a multiple
+ * of 16 (the images are copied as 16-byte vectors; fn_crop_or_pad_u8 / fn_augment_u8 refuse odd sizes likewise, so a 299 x 299 x 3
+ * pool is not supported); anything else is rejected before the launch. */
 int fn_gather_images(const uint8_t* pool, const int32_t* idx, uint8_t* out, int n_out, int bytes_per_image, void* stream);
 
 /* Batched finalisation for the layers consumed through nrm_* (no fn_bn_relu_train_fwd launch): for every channel c < CB with
@@ -235,7 +237,11 @@ int fn_bn_relu_train_bwd(void* dz, int ld_d, const void* y, int ld_y, int M, int
 
 /* ---- pooling: MaxPool2D(3, strides=2, 'valid') :301,369,409 ; AvgPool2D([3,3]) + Flatten :460-461 */
 /* argmax (optional, u8 [N,OH,OW,C]): scan position 0..8 of the FIRST maximum of every window; when given to the backward it
- * replaces the recomputation from x (x may then be NULL). */
+ * replaces the recomputation from x (x may then be NULL).
+ * Precondition: every window holds a value > -3.0e38 (the running maximum starts there): a window made only of -Inf, or of
+ * finite values below -3.0e38 (bf16 can hold them), yields -3.0e38 rounded to the storage type and argmax 0.  The network
+ * pools post-ReLU maps; ordinary negative values are handled exactly.  H == 4 / W == 4 and other sizes where (H - 3) is odd
+ * leave the last row / column outside every window: the backward writes 0 there (or keeps the value under accumulate). */
 int fn_maxpool3x3s2_fwd(const void* x, int ld_x, void* y, int ld_y, int N, int H, int W, int C, uint8_t* argmax, int dtype, void* stream);
 int fn_maxpool3x3s2_bwd(const void* x, int ld_x, const void* dy, int ld_dy, void* dx, int ld_dx, int N, int H, int W, int C,
                         const uint8_t* argmax, int accumulate, int dtype, void* stream);
@@ -309,6 +315,10 @@ int fn_cast_f32_to_lp(const float* x, void* y, long n, int dtype, void* stream);
  * range[2] receives min/max of the raw dot products (the reference's +-(1+atol) check is done by the caller).
  * Triplet selection / loss are build-defined (arXiv 1503.03832 sec. 3). */
 int fn_pairwise_sqdist(const float* xa, const float* xb, float* out, float* range, int n, int m, int E, int metric, void* stream);
+/* fn_select_triplets: labels must hold at least two different values.  A pair whose anchor has no row of another label has no
+ * negative; its triplet slot is left unwritten.  facenet_amd.triplet.select_triplets and TripletMiner reject such pools on the
+ * host.  info (int32 [8 + 5 n(n-1)/2], zeroed once by the caller): [0] pairs, [1] pairs with a candidate, [2] 1 if fewer pairs
+ * than nrof_triplets, [3] call counter (the effective seed is seed + info[3]). */
 int fn_select_triplets(const float* dist, const int32_t* labels, int n, float alpha, int nrof_triplets, uint32_t seed,
                        int semi_hard, int32_t* triplets, int32_t* info, void* stream);
 /* loss: fp32[4] -- word 0 receives the loss; words 2-3 are the launch's own fixed-point accumulator (FN_ACC_GRAD_BITS) */
