@@ -19,6 +19,40 @@ FN_BF16, FN_F16 = 0, 1
 FN_OPT_ADAGRAD, FN_OPT_ADADELTA, FN_OPT_RMSPROP, FN_OPT_MOM = 1, 2, 3, 4     # fn_opt_keras rule codes
 
 
+# fn_conv2d_variant codes (include/facenet_hip.h; csrc/conv_igemm.hip variant_code, csrc/wgrad_taps.h), decoded here only
+VARIANT_FLAG = 1000000     # fwd / dgrad: + KS * 1000000 (in-launch split-K); grouped wgrad: + 1000000 = members normalise on load
+VARIANT_TAPS = 5000000     # wgrad: 5000000 + BMW * 1000 + taps * 10 + (stride 2): the tap-sharing kernel
+VARIANT_HALO = 9000000     # fwd / dgrad: 9000000 + BN: the halo-tile kernel (never grouped, never re-tiled)
+
+
+def variant_tile(code: int) -> int:
+    """BM * 1000 + BN of an implicit-GEMM variant, whatever flags it carries."""
+    return code % VARIANT_FLAG
+
+
+def variant_flag(code: int) -> int:
+    """KS of a forward / data-gradient variant (0: no split), 1 for a normalise-on-load weight-gradient group."""
+    return code // VARIANT_FLAG
+
+
+def variant_is_halo(code: int) -> bool:
+    return code >= VARIANT_HALO
+
+
+def variant_is_taps(code: int) -> bool:
+    """Weight-gradient variants (op 2) only."""
+    return code >= VARIANT_TAPS
+
+
+def variant_name(code: int, wgrad: bool = False) -> str:
+    """How launch names spell a variant: '64x32', '64x64k2' (split-K), '64x64:norm' (wgrad, normalise on load), '64x9s2' (taps)."""
+    if wgrad and variant_is_taps(code):
+        code -= VARIANT_TAPS
+        return f"{code // 1000}x{code % 1000 // 10}" + ("s2" if code % 10 else "")
+    flag = variant_flag(code)
+    return f"{variant_tile(code) // 1000}x{code % 1000}" + ((":norm" if wgrad else f"k{flag}") if flag else "")
+
+
 class ConvDesc(C.Structure):
     _fields_ = [
         ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32),

@@ -9,7 +9,7 @@ batch size, into a flat list of C-ABI kernel launches over pre-allocated HBM buf
     re-allocated); towers write straight into channel slices of their concat buffer;
   * parameters, gradients and Adam state are single flat fp32 buffers (one fused optimiser launch,
     contiguous all-reduce buckets); the MFMA kernels read low-precision packs of the same layout;
-  * the launch list is replayed eagerly or captured into one HIP graph (engine.GraphRunner) -
+  * the launch list is replayed eagerly or captured into one HIP graph (train.GraphRunner) -
     HIP streams and graphs instead of a tracing compiler;
   * backward is derived here, op by op, in reverse order of the forward records (no autograd).
 
@@ -18,18 +18,18 @@ PyTorch supplies device memory, streams and torch.distributed only.
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, keras_names, params as _params
 from ._lib import ConvDesc
-from .schedule import Op, Region, region
+from .params import Layer, _pad8
+from .schedule import Op, Region, emit, region, stats_region
 
 BN_EPS = 1e-3        # Keras default (inception_resnet_v1.py:57-58 commented out)
 BN_MOMENTUM = 0.99   # Keras default
@@ -47,69 +47,53 @@ DEFAULT_CONFIG = {   # inception_resnet_v1.py:13-43
 }
 
 
-# tower declarations (name, filters, kernel[, stride, padding]) of the residual and reduction blocks
-# (inception_resnet_v1.py:83-259 and :262-377); shared by the full network and by BlockNetwork
+class TowerOp(NamedTuple):
+    """One step of an inception tower: a convolution (+ BN + ReLU), or -- no filters -- the 3x3 / stride 1 / SAME average pool
+    a tower of ``Lowering.mixed`` may open with."""
+    name: str
+    cout: int = 0
+    k: Tuple[int, int] = (1, 1)
+    stride: int = 1
+    padding: str = "same"
+
+
+def towers(*specs):
+    """Tower declarations [(name, filters, kernel[, stride, padding]), ...] -> [[TowerOp]]."""
+    return [[TowerOp(*s) for s in t] for t in specs]
+
+
+# the residual blocks (inception_resnet_v1.py:83-259): (towers, trunk width); shared by the full network and by BlockNetwork
 BLOCK_TOWERS = {
-    "block35": ([[("Conv2d_1x1", 32, (1, 1))],
-                 [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3))],
-                 [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3)), ("Conv2d_0c_3x3", 32, (3, 3))]], 256),
-    "block17": ([[("Conv2d_1x1", 128, (1, 1))],
-                 [("Conv2d_0a_1x1", 128, (1, 1)), ("Conv2d_0b_1x7", 128, (1, 7)), ("Conv2d_0c_7x1", 128, (7, 1))]], 896),
-    "block8": ([[("Conv2d_1x1", 192, (1, 1))],
-                [("Conv2d_0a_1x1", 192, (1, 1)), ("Conv2d_0b_1x3", 192, (1, 3)), ("Conv2d_0c_3x1", 192, (3, 1))]], 1792),
+    "block35": (towers([("Conv2d_1x1", 32, (1, 1))],
+                       [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3))],
+                       [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3)), ("Conv2d_0c_3x3", 32, (3, 3))]), 256),
+    "block17": (towers([("Conv2d_1x1", 128, (1, 1))],
+                       [("Conv2d_0a_1x1", 128, (1, 1)), ("Conv2d_0b_1x7", 128, (1, 7)), ("Conv2d_0c_7x1", 128, (7, 1))]), 896),
+    "block8": (towers([("Conv2d_1x1", 192, (1, 1))],
+                      [("Conv2d_0a_1x1", 192, (1, 1)), ("Conv2d_0b_1x3", 192, (1, 3)), ("Conv2d_0c_3x1", 192, (3, 1))]), 1792),
+}
+
+# Residual blocks that inference plans run as ONE launch with the tower activations in LDS (csrc/block_fused.hip; DESIGN.md
+# section 8a): kind -> (H, W, trunk width, BN-folded layers in the kernel's argument order; `up` follows them)
+FUSED_BLOCKS = {
+    "block17": (8, 8, 896, ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv1/Conv2d_0b_1x7", "tower_conv1/Conv2d_0c_7x1")),
+    "block35": (17, 17, 256, ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv2/Conv2d_0a_1x1",
+                              "tower_conv1/Conv2d_0b_3x3", "tower_conv2/Conv2d_0b_3x3", "tower_conv2/Conv2d_0c_3x3")),
 }
 
 
 def reduction_towers(kind: str, filters):
+    """ReductionA / ReductionB (inception_resnet_v1.py:262-377)."""
+    f = filters
     if kind == "reduction_a":
-        fa = filters
-        return [[("Conv2d_1a_3x3", fa[0][0], (3, 3), 2, "valid")],
-                [("Conv2d_0a_1x1", fa[1][0], (1, 1), 1, "same"), ("Conv2d_0b_3x3", fa[1][1], (3, 3), 1, "same"),
-                 ("Conv2d_1a_3x3", fa[1][2], (3, 3), 2, "valid")]]
-    fb = filters
-    return [[("Conv2d_0a_1x1", fb[0][0], (1, 1), 1, "same"), ("Conv2d_1a_3x3", fb[0][1], (3, 3), 2, "valid")],
-            [("Conv2d_0a_1x1", fb[1][0], (1, 1), 1, "same"), ("Conv2d_1a_3x3", fb[1][1], (3, 3), 2, "valid")],
-            [("Conv2d_0a_1x1", fb[2][0], (1, 1), 1, "same"), ("Conv2d_0b_3x3", fb[2][1], (3, 3), 1, "same"),
-             ("Conv2d_1a_3x3", fb[2][2], (3, 3), 2, "valid")]]
+        return towers([("Conv2d_1a_3x3", f[0][0], (3, 3), 2, "valid")],
+                      [("Conv2d_0a_1x1", f[1][0]), ("Conv2d_0b_3x3", f[1][1], (3, 3)), ("Conv2d_1a_3x3", f[1][2], (3, 3), 2, "valid")])
+    return towers([("Conv2d_0a_1x1", f[0][0]), ("Conv2d_1a_3x3", f[0][1], (3, 3), 2, "valid")],
+                  [("Conv2d_0a_1x1", f[1][0]), ("Conv2d_1a_3x3", f[1][1], (3, 3), 2, "valid")],
+                  [("Conv2d_0a_1x1", f[2][0]), ("Conv2d_0b_3x3", f[2][1], (3, 3)), ("Conv2d_1a_3x3", f[2][2], (3, 3), 2, "valid")])
 
 
-
-def _pad8(c: int) -> int:
-    return (c + 7) // 8 * 8
-
-
-# ------------------------------------------------------------------------------------------------
-# declarations
-# ------------------------------------------------------------------------------------------------
-@dataclass
-class Layer:
-    name: str
-    cin: int          # padded to a multiple of 8
-    cin_real: int
-    cout: int
-    kh: int
-    kw: int
-    stride: int
-    pad_h: int
-    pad_w: int
-    has_bn: bool
-    has_bias: bool
-    dense: bool = False
-    cout_real: int = -1   # un-padded output channels (classifier only differs)
-    w_off: int = -1       # element offset of [cout][kh][kw][cin] in the flat parameter buffer
-    bias_off: int = -1    # element offset of the bias in the flat parameter buffer
-    bn_off: int = -1      # offset in the global BatchNorm channel space
-    index: int = -1
-
-    @property
-    def ktot(self) -> int:
-        return self.kh * self.kw * self.cin
-
-    @property
-    def numel(self) -> int:
-        return self.cout * self.ktot
-
-
+# ---- declarations ----
 class Buf:
     """One NHWC activation tensor: raw conv output, activated output and (training) gradient."""
 
@@ -153,9 +137,16 @@ def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
     return t.data_ptr() + elem_off * t.element_size()
 
 
-# ------------------------------------------------------------------------------------------------
-# the network
-# ------------------------------------------------------------------------------------------------
+def weight_region(pack: torch.Tensor, L: Layer) -> Region:
+    """Layer L's kernel in a buffer laid out like the parameters (P, G, the low-precision packs)."""
+    return region(pack, L.w_off, L.w_off + L.numel)
+
+
+def bias_region(P: torch.Tensor, L: Layer) -> Region:
+    return region(P, L.bias_off, L.bias_off + L.cout)
+
+
+# ---- the network ----
 class Network:
     """Parameters + topology of Inception-ResNet-v1; ``plan()`` lowers it for one batch size."""
 
@@ -234,21 +225,9 @@ class Network:
         return L
 
     def _layout(self):
-        off = 0
-        for L in self.layers.values():
-            L.w_off = off
-            off += L.numel
-            assert L.numel % 8 == 0
-        self.n_kernel = off
-        self.n_decay = (off + 3) // 4 * 4            # coupled-L2 region of the flat buffer
+        self.n_kernel, self.n_decay, self.n_params = _params._layout(self.layers.values(), self.CB)
         self.beta_base = self.n_decay
-        off = self.beta_base + self.CB
-        for L in self.layers.values():
-            if L.has_bias:
-                L.bias_off = off
-                off += L.cout
-        self.n_params = (off + 3) // 4 * 4
-        self.bias_lo = self.beta_base + self.CB          # [bias_lo, n_params): the biases
+        self.bias_lo = self.n_decay + self.CB          # [bias_lo, n_params): the biases
         self.max_layer_elems = max(L.numel for L in self.layers.values())
 
     def _alloc_params(self, seed: int):
@@ -268,59 +247,23 @@ class Network:
         self.G = None  # gradient / optimiser state are created by the Trainer
         self.load_keras_params(self.init_keras_params(seed))
 
-    # ---- Keras-layout import / export (HWIO kernels, [in,out] dense; apps/train_softmax.py:68-78) ----
+    # ---- Keras-layout import / export (HWIO kernels, [in,out] dense; the conversions themselves: params.py) ----
     def init_keras_params(self, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
-        """Glorot-uniform kernels (inception_resnet_v1.py:66), zero biases / beta, moving stats (0, 1),
-        drawn in declaration order from torch.Generator(seed) on the CPU."""
-        gen = torch.Generator().manual_seed(seed)
-        out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-        for L in self.layers.values():
-            if L.dense:
-                w = torch.empty(L.cin_real, L.cout_real)
-                lim = math.sqrt(6.0 / (L.cin_real + L.cout_real))
-            else:
-                w = torch.empty(L.kh, L.kw, L.cin_real, L.cout)
-                lim = math.sqrt(6.0 / (L.kh * L.kw * (L.cin_real + L.cout)))
-            w.uniform_(-lim, lim, generator=gen)
-            out[L.name + "/kernel"] = w
-            if L.has_bias:
-                out[L.name + "/bias"] = torch.zeros(L.cout_real)
-            if L.has_bn:
-                pre = self._bn_prefix(L)
-                out[pre + "/beta"] = torch.zeros(L.cout)
-                out[pre + "/moving_mean"] = torch.zeros(L.cout)
-                out[pre + "/moving_variance"] = torch.ones(L.cout)
-        return out
+        """Freshly initialised variables (params.init_keras_params) under the engine's keys."""
+        return _params.init_keras_params(self.layers.values(), self._bn_prefix, seed)
 
     @staticmethod
     def _bn_prefix(L: Layer) -> str:
         return "features/bn" if L.name == "features/logits" else L.name + "/bn"
 
-    def _flat(self, params: Dict[str, torch.Tensor], with_stats: bool):
+    def _flat(self, keras: Dict[str, torch.Tensor], with_stats: bool):
         """Engine-keyed Keras-layout tensors -> the flat fp32 layout [kernels OHWI | pad | betas | biases] (+ moving statistics)."""
-        P = torch.zeros(self.n_params, dtype=torch.float32)
-        mean = torch.zeros(self.CB)
-        var = torch.ones(self.CB)
-        for L in self.layers.values():
-            w = torch.as_tensor(params[L.name + "/kernel"]).to(torch.float32)
-            if L.dense:
-                w = w.t().reshape(L.cout_real, 1, 1, L.cin_real)
-                if L.cout != L.cout_real:
-                    w = torch.cat([w, torch.zeros(L.cout - L.cout_real, 1, 1, L.cin_real)], 0)
-            else:
-                w = w.permute(3, 0, 1, 2)                      # HWIO -> O,H,W,I
-            if L.cin != L.cin_real:
-                w = torch.nn.functional.pad(w, (0, L.cin - L.cin_real))
-            P[L.w_off:L.w_off + L.numel] = w.reshape(-1)
-            if L.has_bias:
-                P[L.bias_off:L.bias_off + L.cout_real] = torch.as_tensor(params[L.name + "/bias"]).to(torch.float32)
-            if L.has_bn:
-                pre = self._bn_prefix(L)
-                P[self.beta_base + L.bn_off:self.beta_base + L.bn_off + L.cout] = torch.as_tensor(params[pre + "/beta"])
-                if with_stats:
-                    mean[L.bn_off:L.bn_off + L.cout] = torch.as_tensor(params[pre + "/moving_mean"])
-                    var[L.bn_off:L.bn_off + L.cout] = torch.as_tensor(params[pre + "/moving_variance"])
-        return P, mean, var
+        return _params.pack(self.layers.values(), self.n_params, self.beta_base, self.CB, self._bn_prefix, keras, with_stats)
+
+    def _keras(self, flat: torch.Tensor, stats=None) -> "OrderedDict[str, torch.Tensor]":
+        """The inverse: a flat buffer laid out like ``P`` (+ moving statistics) -> engine-keyed Keras-layout tensors."""
+        return _params.unpack(self.layers.values(), self.beta_base, self._bn_prefix, flat.detach().cpu(),
+                             None if stats is None else (stats[0].cpu(), stats[1].cpu()))
 
     def flat_from_keras(self, params: Dict[str, torch.Tensor]) -> torch.Tensor:
         """Per-variable tensors (engine keys, Keras layouts; no moving statistics) -> one flat buffer laid out like ``P``
@@ -338,19 +281,16 @@ class Network:
         self.refresh_packs()
 
     def _engine_keys(self, params: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        from . import keras_names
         return keras_names.from_keras(params, self.layers, int(self.cfg["block8_1"]["repeat"]))
 
     def variable_table(self) -> List[Tuple[str, str]]:
         """[(file variable name, engine key)] in save order: what checkpoints (and their optimiser slots) are keyed by."""
-        from . import keras_names
         return keras_names.keras_variable_table(self.layers, int(self.cfg["block8_1"]["repeat"]))
 
     def keras_variables(self, moving_stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                         params: Optional[torch.Tensor] = None) -> "OrderedDict[str, torch.Tensor]":
         """``model.weights`` of the reference model: Keras variable names, Keras layouts, Keras order (keras_names.py).
         ``params``: a flat buffer laid out like ``P`` to export instead of ``P`` (the Trainer's moving average)."""
-        from . import keras_names
         return keras_names.to_keras(self.export_keras_params(moving_stats, params), self.layers, int(self.cfg["block8_1"]["repeat"]))
 
     def export_folded_params(self) -> "OrderedDict[str, torch.Tensor]":
@@ -364,8 +304,7 @@ class Network:
         P = self.P.detach().cpu()
         out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         for L in self.layers.values():
-            w = W[L.w_off:L.w_off + L.numel].reshape(L.cout, L.kh, L.kw, L.cin)[:L.cout_real, ..., :L.cin_real]
-            out[L.name + "/weights"] = (w.reshape(L.cout_real, L.cin_real).t() if L.dense else w.permute(1, 2, 3, 0)).contiguous()
+            out[L.name + "/weights"] = _params.kernel_to_keras(L, W)
             if L.has_bn:
                 out[L.name + "/biases"] = fb[L.bn_off:L.bn_off + L.cout].clone()
             elif L.has_bias:
@@ -376,32 +315,11 @@ class Network:
                             params: Optional[torch.Tensor] = None) -> "OrderedDict[str, torch.Tensor]":
         """Keras-layout tensors under the engine's keys.  ``moving_stats``: (mean, var) to export instead of this replica's
         (data parallelism: the cross-replica average, Trainer.averaged_moving_stats); ``params``: flat buffer instead of ``P``."""
-        P = (self.P if params is None else params).detach().cpu()
-        mean, var = (self.S_mean.cpu(), self.S_var.cpu()) if moving_stats is None else (moving_stats[0].cpu(), moving_stats[1].cpu())
-        out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-        for L in self.layers.values():
-            w = P[L.w_off:L.w_off + L.numel].reshape(L.cout, L.kh, L.kw, L.cin)[:L.cout_real, ..., :L.cin_real]
-            out[L.name + "/kernel"] = (w.reshape(L.cout_real, L.cin_real).t() if L.dense else w.permute(1, 2, 3, 0)).contiguous()
-            if L.has_bias:
-                out[L.name + "/bias"] = P[L.bias_off:L.bias_off + L.cout_real].clone()
-            if L.has_bn:
-                pre = self._bn_prefix(L)
-                out[pre + "/beta"] = P[self.beta_base + L.bn_off:self.beta_base + L.bn_off + L.cout].clone()
-                out[pre + "/moving_mean"] = mean[L.bn_off:L.bn_off + L.cout].clone()
-                out[pre + "/moving_variance"] = var[L.bn_off:L.bn_off + L.cout].clone()
-        return out
+        return self._keras(self.P if params is None else params, (self.S_mean, self.S_var) if moving_stats is None else moving_stats)
 
     def export_keras_grads(self, G: torch.Tensor) -> Dict[str, torch.Tensor]:
-        Gc = G.detach().cpu()
-        out = {}
-        for L in self.layers.values():
-            w = Gc[L.w_off:L.w_off + L.numel].reshape(L.cout, L.kh, L.kw, L.cin)[:L.cout_real, ..., :L.cin_real]
-            out[L.name + "/kernel"] = (w.reshape(L.cout_real, L.cin_real).t() if L.dense else w.permute(1, 2, 3, 0)).contiguous()
-            if L.has_bias:
-                out[L.name + "/bias"] = Gc[L.bias_off:L.bias_off + L.cout_real].clone()
-            if L.has_bn:
-                out[self._bn_prefix(L) + "/beta"] = Gc[self.beta_base + L.bn_off:self.beta_base + L.bn_off + L.cout].clone()
-        return out
+        """A flat buffer laid out like ``P`` (gradients, optimizer slots, the moving average) per trainable variable."""
+        return dict(self._keras(G))
 
     # ---- weight packs ---------------------------------------------------------------------------
     def stream(self) -> int:
@@ -440,12 +358,7 @@ class Network:
 
     def count_variables(self) -> Tuple[int, int]:
         """(total, trainable) counted on the UN-padded Keras shapes (SURVEY.md shape table)."""
-        tot = tr = 0
-        for L in self.layers.values():
-            k = L.cout_real * L.kh * L.kw * L.cin_real
-            tr += k + (L.cout_real if L.has_bias else 0) + (L.cout if L.has_bn else 0)
-            tot += k + (L.cout_real if L.has_bias else 0) + (3 * L.cout if L.has_bn else 0)
-        return tot, tr
+        return _params.count_variables(self.layers.values())
 
     def plan(self, N: int, training: bool, loss: Optional[str] = None, step_word: Optional[torch.Tensor] = None,
              rank: int = 0) -> "Lowering":
@@ -488,45 +401,32 @@ class BlockNetwork(Network):
         return params          # a lone block has no place in the reference model's variable naming: engine keys only
 
 
-# ------------------------------------------------------------------------------------------------
-# lowering: topology -> buffers + forward records -> launch lists
-# ------------------------------------------------------------------------------------------------
+# ---- lowering: topology -> buffers + forward records -> launch lists ----
+class Options(NamedTuple):
+    """What a lowering may do differently: field <name> is the integer in FACENET_<NAME>, read when a plan is constructed
+    (DESIGN.md sections 8 and 8a describe each option and what it measured; INTEGRATION.md lists the variables)."""
+    norm_on_load: int = 0              # FACENET_NORM_ON_LOAD: BN+ReLU outputs that only convolutions read are normalised by their readers, never written
+    lazy_bn_maxhw: int = 0             # FACENET_LAZY_BN_MAXHW: largest map on which a BN+ReLU output is materialised by its single reader (0: off) ...
+    lazy_bn_kmax: int = 1024           # FACENET_LAZY_BN_KMAX: ... k x k readers only up to this many K columns
+    merge_siblings: int = 1            # FACENET_MERGE_SIBLINGS: sibling 1x1 data gradients as one multi-source launch
+    fuse_residual_bwd: int = 1         # FACENET_FUSE_RESIDUAL_BWD: residual backward in the epilogue of the launch that completes the block output's gradient
+    fuse_blocks: int = 1               # FACENET_FUSE_BLOCKS: inference plans run FUSED_BLOCKS as one launch ...
+    fuse_blocks_min_batch: int = 32    # FACENET_FUSE_BLOCKS_MIN_BATCH: ... from this batch size up
+    warm_ahead: int = 1                # FACENET_WARM_AHEAD: a fused block launch warms the L2 with the next block's weights
+
+    @classmethod
+    def from_env(cls) -> "Options":
+        return cls(*(int(os.environ.get("FACENET_" + name.upper(), default)) for name, default in cls._field_defaults.items()))
+
+
 class Lowering:
     def __init__(self, net: Network, N: int, training: bool, declare: bool, loss: Optional[str] = None,
                  step_word: Optional[torch.Tensor] = None, rank: int = 0):
         self.net, self.N, self.training, self.declare, self.loss = net, N, training, declare, loss
         self.step_word, self.rank = step_word, int(rank)     # dropout: where the step count lives, data-parallel replica
-        self.fuse_bn_bwd = True     # BN-backward reduction inside the producing dgrad's epilogue where it is the sole producer
-        # Optional: BN+ReLU outputs that only convolutions read are never written; the consumers (forward and weight
-        # gradient) normalise the raw tensor while staging their operand tile (fn_conv_desc.nrm_*) and fn_bn_finalize
-        # publishes scale / shift for the backward pass and the moving statistics in one launch.  Saves 78 of 82 bn_relu_fwd
-        # launches and the activated copies, but every tap and every N tile repeats the per-element affine+ReLU, which makes
-        # the staging VALU-bound: measured 9.52 ms vs 9.11 ms per step on MI355X -> off by default.
-        self.norm_on_load = bool(int(os.environ.get("FACENET_NORM_ON_LOAD", "0")))
-        # Optional (FACENET_LAZY_BN_MAXHW=17; default 0 = off): on maps up to that size a BN+ReLU output with exactly ONE reader, a
-        # stride-1 convolution whose output map has the input's size, is materialised BY that reader -- it normalises the raw
-        # tensor while staging its operand and the workgroups of its first column tile write the activated tensor once, at the
-        # centre tap (fn_conv_desc.nrm_z); the weight gradient and the backward pass read the same buffers as before.  68 of the
-        # 82 fn_bn_relu_train_fwd launches disappear, but the step does not get faster (MI355X, batch 90: 7.58-7.60 ms with,
-        # 7.54 ms without): normalise-on-load costs each reader 2.5-4.5 us (tools/dev_normcost.py: a dependent statistics round
-        # trip in the prologue plus ~40 VALU instructions per 16-byte chunk on the load -> LDS path of a latency-bound k loop,
-        # repeated per tap and per column tile), which is what the removed launch and its boundary cost.  Kept as an option.
-        self.lazy_bn_maxhw = int(os.environ.get("FACENET_LAZY_BN_MAXHW", "0"))
-        self.lazy_bn_kmax = int(os.environ.get("FACENET_LAZY_BN_KMAX", "1024"))      # k x k readers only up to this many K columns
+        self.opt = Options.from_env()
+        self.fuse_blocks = self.opt.fuse_blocks and (declare or N >= self.opt.fuse_blocks_min_batch)
         self.lazy: Dict[str, List[Tuple[int, int]]] = {}        # buffer -> [(c0, C)] BN ranges materialised by their reader
-        self.merge_sibling_dgrads = bool(int(os.environ.get("FACENET_MERGE_SIBLINGS", "1")))
-        # The residual backward of block i (ReLU mask, scaled copy for its `up` branch, bias gradient, pass-through to its
-        # trunk) runs in the epilogue of the launch that completes the gradient of block i's output: the merged sibling data
-        # gradient of block i+1 (fn_conv_desc.rb_*).  18 of the 21 fn_residual_bwd launches and one read-modify-write pass over
-        # every block output's gradient disappear.
-        self.fuse_residual_bwd = bool(int(os.environ.get("FACENET_FUSE_RESIDUAL_BWD", "1")))
-        # Inference / mining plans: a whole Block17 (five convolution launches) runs as ONE launch with its tower activations in
-        # LDS (fn_block17_infer, csrc/block_fused.hip).  BatchNorm is folded there, so nothing couples the images of a batch.
-        # One workgroup per image: below ~32 images the fused kernels leave most of the chip idle and the layer-wise launches win
-        # (tools/bench_inference.py, batch 1 / 8 / 32: 0.91 / 0.97 / 1.09 ms fused against 0.80 / 0.86 / 1.06 ms layer-wise);
-        # FACENET_FUSE_BLOCKS = 0 never, 1 from FACENET_FUSE_BLOCKS_MIN_BATCH (32) images up.
-        self.fuse_blocks = bool(int(os.environ.get("FACENET_FUSE_BLOCKS", "1"))) and \
-            (declare or N >= int(os.environ.get("FACENET_FUSE_BLOCKS_MIN_BATCH", "32")))
         self.virtual: Dict[str, List[Tuple[int, int]]] = {}     # buffer -> [(c0, C)] BN ranges that are not materialised
         self.dtype = net.train_dtype if training else net.infer_dtype
         self.dt = None if declare else _lib.dtype_code(self.dtype)
@@ -563,18 +463,19 @@ class Lowering:
         self.bufs[name] = b
         return b
 
+    def _reads(self, s: Slice):
+        self.readers[s.buf.name] = self.readers.get(s.buf.name, 0) + 1
+
     def input(self, H: int, W: int) -> Slice:
         self.images = None if self.declare else torch.zeros(self.N, H, W, 3, dtype=torch.uint8, device=self.net.device)
         self.norm_work = None if self.declare else torch.zeros(8 * self.N, dtype=torch.float32, device=self.net.device)
-        b = self.buf("input", H, W, 8)
-        return b.full()
+        return self.buf("input", H, W, 8).full()
 
     def feature_input(self, H: int, W: int, Cc: int) -> Slice:
         """A low-precision NHWC feature map as the plan's input (BlockNetwork): no image normalisation, and -- unlike the image
         input -- it receives a data gradient."""
         self.images = None
-        b = self.buf("trunk", H, W, Cc)
-        return b.full()
+        return self.buf("trunk", H, W, Cc).full()
 
     @staticmethod
     def _geom(H, W, k, stride, padding):
@@ -590,15 +491,13 @@ class Lowering:
         L = self.net._declare_layer(name, x.C, cin_real or x.C, cout, kh, kw, stride, ph, pw, has_bn, has_bias) \
             if self.declare else self.net.layers[name]
         if out is None:
-            ob = self.buf(name, OH, OW, cout, bn_channels=cout if has_bn else 0, need_raw=has_bn)
-            out = ob.full()
+            out = self.buf(name, OH, OW, cout, bn_channels=cout if has_bn else 0, need_raw=has_bn).full()
         if self.declare and has_bn:
             L.bn_off = out.buf.bn_off + out.c0
         assert out.buf.H == OH and out.buf.W == OW and out.C == cout, name
-        self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
+        self._reads(x)
         if "trunk" in extra:
-            t = extra["trunk"]
-            self.readers[t.buf.name] = self.readers.get(t.buf.name, 0) + 1
+            self._reads(extra["trunk"])
         self.recs.append(Rec("conv", L, x, out, dict(kind=kind, **extra)))
         return out
 
@@ -615,51 +514,46 @@ class Lowering:
         OH, OW = (x.buf.H - 3) // 2 + 1, (x.buf.W - 3) // 2 + 1
         if out is None:
             out = self.buf(name, OH, OW, x.C).full()
-        self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
+        self._reads(x)
         self.recs.append(Rec("maxpool", None, x, out))
         return out
 
     def avgpool3(self, name: str, x: Slice) -> Slice:
         """AvgPool 3x3 / stride 1 / SAME (TF: divisor = in-map taps) into a buffer of its own."""
         out = self.buf(name, x.buf.H, x.buf.W, x.C).full()
-        self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
+        self._reads(x)
         self.recs.append(Rec("avgpool3", None, x, out))
         return out
 
-    def _tower(self, prefix: str, x: Slice, tower, last_out: Slice) -> None:
-        for j, spec in enumerate(tower):
-            nm, cout, k = spec[0], spec[1], spec[2]
-            stride = spec[3] if len(spec) > 3 else 1
-            padding = spec[4] if len(spec) > 4 else "same"
-            name = f"{prefix}/{nm}"
-            if j == len(tower) - 1:
-                self.conv(name, x, cout, k, stride, padding, out=last_out)
-            else:
-                x = self.cbr(name, x, cout, k, stride, padding)
+    def _towers(self, prefix: str, branch: str, trunk: Slice, towers, out: Buf) -> None:
+        """Every tower reads the trunk (through a 3x3 / stride 1 / SAME average pool where it opens with a TowerOp without filters)
+        and its last convolution writes the tower's channel slice of ``out``; ONE BN + ReLU pass covers the whole concatenation."""
+        c0 = 0
+        for i, tower in enumerate(towers):
+            x, pre = trunk, f"{prefix}/{branch.format(i)}"
+            if not tower[0].cout:
+                x, tower = self.avgpool3(f"{pre}/{tower[0].name}", trunk), tower[1:]
+            for op in tower[:-1]:
+                x = self.cbr(f"{pre}/{op.name}", x, op.cout, op.k, op.stride, op.padding)
+            op = tower[-1]
+            self.conv(f"{pre}/{op.name}", x, op.cout, op.k, op.stride, op.padding, out=out.sl(c0, op.cout))
+            c0 += op.cout
+        self.bn_apply(out, 0, c0)
 
     def block(self, prefix: str, trunk: Slice, towers, up: int, scale: float, relu: bool, branch: str = "tower_conv{}",
               up_name: str = "up") -> Slice:
         """Block35/17/8 (:83-259): towers -> concat -> up 1x1 (+bias) -> act(trunk + scale*up)."""
         H, W = trunk.buf.H, trunk.buf.W
-        cm = sum(t[-1][1] for t in towers)
-        if (not self.declare and not self.training and self.fuse_blocks and (H, W, up) == (8, 8, 896) and towers == BLOCK_TOWERS["block17"][0]
-                and trunk.c0 == 0 and trunk.C == trunk.buf.C == 896):
-            out = self.buf(prefix + "/out", H, W, up)
-            self.readers[trunk.buf.name] = self.readers.get(trunk.buf.name, 0) + 1
-            self.recs.append(Rec("block17", None, trunk, out.full(), dict(prefix=prefix, scale=float(scale), relu=bool(relu))))
-            return out.full()
-        if (not self.declare and not self.training and self.fuse_blocks and (H, W, up) == (17, 17, 256) and towers == BLOCK_TOWERS["block35"][0]
-                and trunk.c0 == 0 and trunk.C == trunk.buf.C == 256):
-            out = self.buf(prefix + "/out", H, W, up)
-            self.readers[trunk.buf.name] = self.readers.get(trunk.buf.name, 0) + 1
-            self.recs.append(Rec("block35", None, trunk, out.full(), dict(prefix=prefix, scale=float(scale), relu=bool(relu))))
-            return out.full()
+        cm = sum(t[-1].cout for t in towers)
+        for kind, (fh, fw, fc, _) in FUSED_BLOCKS.items():
+            if (not self.declare and not self.training and self.fuse_blocks and (H, W, up) == (fh, fw, fc)
+                    and towers == BLOCK_TOWERS[kind][0] and trunk.c0 == 0 and trunk.C == trunk.buf.C == fc):
+                out = self.buf(prefix + "/out", H, W, up)
+                self._reads(trunk)
+                self.recs.append(Rec("fused_block", None, trunk, out.full(), dict(kind=kind, prefix=prefix, scale=float(scale), relu=bool(relu))))
+                return out.full()
         mixed = self.buf(prefix + "/mixed", H, W, cm, bn_channels=cm, need_raw=True)
-        c0 = 0
-        for i, t in enumerate(towers):
-            self._tower(f"{prefix}/{branch.format(i)}", trunk, t, mixed.sl(c0, t[-1][1]))
-            c0 += t[-1][1]
-        self.bn_apply(mixed, 0, cm)                      # one pass over the whole concat buffer
+        self._towers(prefix, branch, trunk, towers, mixed)
         out = self.buf(prefix + "/out", H, W, up)
         self.conv(f"{prefix}/{up_name}", mixed.full(), up, (1, 1), 1, "same", out=out.full(), has_bn=False, has_bias=True,
                   kind="resid", trunk=trunk, scale=float(scale), relu=bool(relu))
@@ -669,31 +563,17 @@ class Lowering:
         """ReductionA/B (:262-377): strided towers + MaxPool, concatenated."""
         H, W = trunk.buf.H, trunk.buf.W
         OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
-        cbn = sum(t[-1][1] for t in towers)
+        cbn = sum(t[-1].cout for t in towers)
         out = self.buf(prefix + "/out", OH, OW, cbn + trunk.C, bn_channels=cbn, need_raw=True)
-        c0 = 0
-        for i, t in enumerate(towers):
-            self._tower(f"{prefix}/{branch.format(i)}", trunk, t, out.sl(c0, t[-1][1]))
-            c0 += t[-1][1]
-        self.bn_apply(out, 0, cbn)
+        self._towers(prefix, branch, trunk, towers, out)
         self.maxpool(prefix + "/MaxPool_1a_3x3", trunk, out=out.sl(cbn, trunk.C))
         return out.full()
 
     def mixed(self, prefix: str, trunk: Slice, towers, branch: str = "Branch_{}") -> Slice:
-        """Stride-1 concat block (Inception-ResNet-v2 Mixed_5a): every tower ends in a convolution + BN + ReLU and writes its
-        channel slice of one buffer; a tower may open with ("AvgPool_...",), a 3x3 / stride 1 / SAME average pool of the trunk."""
-        H, W = trunk.buf.H, trunk.buf.W
-        cm = sum(t[-1][1] for t in towers)
-        out = self.buf(prefix + "/out", H, W, cm, bn_channels=cm, need_raw=True)
-        c0 = 0
-        for i, t in enumerate(towers):
-            x = trunk
-            if len(t[0]) == 1:
-                x = self.avgpool3(f"{prefix}/{branch.format(i)}/{t[0][0]}", trunk)
-                t = t[1:]
-            self._tower(f"{prefix}/{branch.format(i)}", x, t, out.sl(c0, t[-1][1]))
-            c0 += t[-1][1]
-        self.bn_apply(out, 0, cm)
+        """Stride-1 concat block (Inception-ResNet-v2 Mixed_5a): the towers (one may open with an average pool), concatenated."""
+        cm = sum(t[-1].cout for t in towers)
+        out = self.buf(prefix + "/out", trunk.buf.H, trunk.buf.W, cm, bn_channels=cm, need_raw=True)
+        self._towers(prefix, branch, trunk, towers, out)
         return out.full()
 
     def head(self, x: Slice, E: int, dense: str = "features/logits", pool: str = "features/avgpool", out: str = "features/bn",
@@ -707,11 +587,11 @@ class Lowering:
             # its own (hazard 11): the whole-map average of fn_avgpool_* is the reference's result for 3x3 maps exactly
             raise ValueError(f"head expects a 3x3 final map (image sizes 139..170; the reference uses 160), got {H}x{W}")
         pooled = self.buf(pool, 1, 1, x.C)
-        self.readers[x.buf.name] = self.readers.get(x.buf.name, 0) + 1
+        self._reads(x)
         self.recs.append(Rec("avgpool", None, x, pooled.full()))
         if self.training and keep < 1.0:
             dropped = self.buf(pool + "/Dropout", 1, 1, x.C)
-            self.readers[pooled.name] = self.readers.get(pooled.name, 0) + 1
+            self._reads(pooled.full())
             if self.step_word is None:       # no Trainer: the plan owns its step counter (bumped by the caller after each step)
                 self.step_word = torch.zeros(1, dtype=torch.int32, device=self.net.device)
             self.recs.append(Rec("dropout", None, pooled.full(), dropped.full(), dict(keep=float(keep))))
@@ -743,6 +623,21 @@ class Lowering:
     def _rg(s: Slice) -> Region:
         return (s.buf.grad.data_ptr(), s.c0, s.c0 + s.C)
 
+    def _rbeta(self, o: int, Cc: int) -> Region:
+        """The betas of BN channels [o, o + Cc)."""
+        return region(self.net.P, self.net.beta_base + o, self.net.beta_base + o + Cc)
+
+    def _rfold(self, L: Layer) -> Region:
+        """Layer L's bias after BN folding (inference)."""
+        return region(self.net.fold_bias, L.bn_off, L.bn_off + L.cout)
+
+    def _rsaved(self, o: int, Cc: int) -> List[Region]:
+        """scale / shift the forward pass saved for the backward pass of BN channels [o, o + Cc)."""
+        return [region(self.save_scale, o, o + Cc), region(self.save_shift, o, o + Cc)]
+
+    def _rmoving(self, o: int, Cc: int) -> List[Region]:
+        return [region(self.net.S_mean, o, o + Cc), region(self.net.S_var, o, o + Cc)]
+
     def _desc(self, L: Layer, x: Slice, y: Slice) -> ConvDesc:
         d = ConvDesc()
         d.N, d.H, d.W, d.Cin = self.N, x.buf.H, x.buf.W, L.cin
@@ -762,9 +657,6 @@ class Lowering:
             r *= 2
         return r
 
-    def _emit(self, lst: List[Op], name: str, fn, *args, keep=(), r=(), w=()):
-        lst.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
-
     def _grad_mode(self, s: Slice) -> int:
         """0 = first writer of this channel range (overwrite), 1 = accumulate."""
         rng = (s.c0, s.c0 + s.C)
@@ -775,10 +667,7 @@ class Lowering:
         return 0
 
     def finish(self):
-        net, lib = self.net, self.net.lib
-        dev = net.device
-        CB = net.CB
-        N = self.N
+        net, lib, dev, CB, N = self.net, self.net.lib, self.net.device, self.net.CB, self.N
         if self.training:
             # BN workspaces: STAT_REPLICAS x (sum | sumsq) accumulator replicas of fixed-point fn_acc_t (int64): integer atomics,
             # so the totals -- and with them every training step -- have the same bits whatever order the workgroups arrive in
@@ -794,67 +683,59 @@ class Lowering:
             self.fin_count = torch.ones(CB, dtype=torch.int32)
         inp = self.bufs.get("input")
         if inp is not None:
-            self._emit(self.fwd, "image_normalize", lib.fn_image_normalize, _ptr(self.images), _ptr(inp.act), _ptr(self.norm_work),
-                       N, self.images.shape[1] * self.images.shape[2], net.normalization, self.dt,
-                       r=[region(self.images)], w=[self._ra(inp.full()), region(self.norm_work)])
+            emit(self.fwd, "image_normalize", lib.fn_image_normalize, _ptr(self.images), _ptr(inp.act), _ptr(self.norm_work),
+                 N, self.images.shape[1] * self.images.shape[2], net.normalization, self.dt,
+                 r=[region(self.images)], w=[self._ra(inp.full()), region(self.norm_work)])
         for r in self.recs:
             getattr(self, "_fwd_" + r.kind)(r)
         if self.training and (self.virtual or self.lazy):
             self.fin_reps, self.fin_count = self.fin_reps.to(dev), self.fin_count.to(dev)
-            self._emit(self.fwd, "bn_finalize", lib.fn_bn_finalize, _ptr(self.ws), CB, 2 * CB, _ptr(self.fin_reps), _ptr(self.fin_count),
-                       _ptr(net.P, net.beta_base), _ptr(self.save_scale), _ptr(self.save_shift), _ptr(net.S_mean), _ptr(net.S_var),
-                       net.bn_momentum, BN_EPS, CB,
-                       r=[(self.ws.data_ptr() + 1, 0, CB), region(net.P, net.beta_base, net.beta_base + CB)],
-                       w=[region(self.save_scale), region(self.save_shift), region(net.S_mean), region(net.S_var)])
+            emit(self.fwd, "bn_finalize", lib.fn_bn_finalize, _ptr(self.ws), CB, 2 * CB, _ptr(self.fin_reps), _ptr(self.fin_count),
+                 _ptr(net.P, net.beta_base), _ptr(self.save_scale), _ptr(self.save_shift), _ptr(net.S_mean), _ptr(net.S_var),
+                 net.bn_momentum, BN_EPS, CB, r=[stats_region(self.ws, 0, CB), self._rbeta(0, CB)], w=self._rsaved(0, CB) + self._rmoving(0, CB))
+
+    @staticmethod
+    def _overlaps(s: Optional[Slice], y: Slice) -> bool:
+        return s is not None and s.buf is y.buf and s.c0 < y.c0 + y.C and y.c0 < s.c0 + s.C
+
+    def _readers_of(self, y: Slice) -> Iterator[Tuple[Rec, bool, bool]]:
+        """(record, reads it as x, reads it as the residual trunk of an `up` convolution) of every forward record, other than
+        the BatchNorms themselves, that reads channels of y."""
+        for r in self.recs:
+            if r.kind != "bn":
+                as_x, as_trunk = self._overlaps(r.x, y), self._overlaps(r.extra.get("trunk"), y)
+                if as_x or as_trunk:
+                    yield r, as_x, as_trunk
+
+    def _bn_relu_outputs(self) -> Iterator[Slice]:
+        return (rec.y for rec in self.recs if rec.kind == "bn" and rec.extra["relu"] and rec.y.buf.raw is not None)
 
     def _find_virtual(self):
-        """A BN(+ReLU) range is virtual when every reader is the x operand of a convolution that can normalise on load."""
-        if not self.norm_on_load:
+        """A BN(+ReLU) range is virtual when every reader is the x operand of a convolution that can normalise on load (pools,
+        the head and the residual operand of an `up` convolution read the activated tensor)."""
+        if not self.opt.norm_on_load:
             return
-        for rec in self.recs:
-            if rec.kind != "bn" or not rec.extra["relu"]:
-                continue
-            b, c0, Cc = rec.y.buf, rec.y.c0, rec.y.C
-            ok = b.raw is not None
-            for r2 in self.recs:
-                if r2.kind == "conv":
-                    t = r2.extra.get("trunk")
-                    if t is not None and t.buf is b and t.c0 < c0 + Cc and c0 < t.c0 + t.C:
-                        ok = False                      # residual operand of an `up` convolution
-                    if r2.x.buf is b and r2.x.c0 < c0 + Cc and c0 < r2.x.c0 + r2.x.C:
-                        inside = c0 <= r2.x.c0 and r2.x.c0 + r2.x.C <= c0 + Cc
-                        ok = ok and inside and r2.layer.cin <= 512
-                elif r2.kind != "bn" and r2.x is not None and r2.x.buf is b and r2.x.c0 < c0 + Cc and c0 < r2.x.c0 + r2.x.C:
-                    ok = False                          # pools and the head read the activated tensor
-            if ok:
-                self.virtual.setdefault(b.name, []).append((c0, Cc))
+        for y in self._bn_relu_outputs():
+            if all(r.kind == "conv" and not as_trunk and y.c0 <= r.x.c0 and r.x.c0 + r.x.C <= y.c0 + y.C and r.layer.cin <= 512
+                   for r, _, as_trunk in self._readers_of(y)):
+                self.virtual.setdefault(y.buf.name, []).append((y.c0, y.C))
 
     def _find_lazy(self):
-        """BN(+ReLU) ranges that their single reader materialises (see __init__)."""
-        if self.lazy_bn_maxhw <= 0:
+        """BN(+ReLU) ranges that their single reader materialises: a stride-1 convolution of exactly that range whose output
+        map has the input's size."""
+        if self.opt.lazy_bn_maxhw <= 0:
             return
-        for rec in self.recs:
-            if rec.kind != "bn" or not rec.extra["relu"]:
+        for y in self._bn_relu_outputs():
+            b = y.buf
+            if max(b.H, b.W) > self.opt.lazy_bn_maxhw or self._is_virtual(y):
                 continue
-            b, c0, Cc = rec.y.buf, rec.y.c0, rec.y.C
-            if b.raw is None or max(b.H, b.W) > self.lazy_bn_maxhw or self._is_virtual(rec.y):
-                continue
-            readers = []
-            for r2 in self.recs:
-                if r2.kind == "bn":
-                    continue
-                t = r2.extra.get("trunk") if r2.kind == "conv" else None
-                touches = (r2.x is not None and r2.x.buf is b and r2.x.c0 < c0 + Cc and c0 < r2.x.c0 + r2.x.C) or \
-                          (t is not None and t.buf is b and t.c0 < c0 + Cc and c0 < t.c0 + t.C)
-                if touches:
-                    readers.append(r2)
+            readers = list(self._readers_of(y))
             if len(readers) != 1:
                 continue
-            r2 = readers[0]
-            L = r2.layer
-            if (r2.kind == "conv" and r2.x.buf is b and r2.x.c0 == c0 and r2.x.C == Cc and L.stride == 1 and L.cin <= 512
-                    and r2.y.buf.H == b.H and r2.y.buf.W == b.W and (L.kh * L.kw == 1 or L.ktot <= self.lazy_bn_kmax)):
-                self.lazy.setdefault(b.name, []).append((c0, Cc))
+            r, L = readers[0][0], readers[0][0].layer
+            if (r.kind == "conv" and r.x.buf is b and r.x.c0 == y.c0 and r.x.C == y.C and L.stride == 1 and L.cin <= 512
+                    and r.y.buf.H == b.H and r.y.buf.W == b.W and (L.kh * L.kw == 1 or L.ktot <= self.opt.lazy_bn_kmax)):
+                self.lazy.setdefault(b.name, []).append((y.c0, y.C))
 
     def _is_lazy(self, s: Slice) -> bool:
         return any(c0 == s.c0 and Cc == s.C for (c0, Cc) in self.lazy.get(s.buf.name, []))
@@ -871,41 +752,38 @@ class Lowering:
         d.nrm_beta = _ptr(net.P, net.beta_base + o)
         d.nrm_sq_off, d.nrm_replicas, d.nrm_rep_stride = net.CB, self._replicas(x.buf.M), 2 * net.CB
         d.nrm_count, d.nrm_eps = x.buf.M, BN_EPS
-        reads += [self._rr(x), (self.ws.data_ptr() + 1, o, o + x.C), region(net.P, net.beta_base + o, net.beta_base + o + x.C)]
+        reads += [self._rr(x), stats_region(self.ws, o, o + x.C), self._rbeta(o, x.C)]
 
     # forward emitters
     def _fwd_conv(self, r: Rec):
         net, lib, L = self.net, self.net.lib, r.layer
         kind = r.extra["kind"]
         d = self._desc(L, r.x, r.y)
-        if self.training and self._is_virtual(r.x):
-            reads, writes = [], []
+        reads, writes = [], []
+        if self.training and (self._is_virtual(r.x) or self._is_lazy(r.x)):
             self._norm_operand(d, r.x, reads)
-        elif self.training and self._is_lazy(r.x):
-            reads, writes = [], [self._ra(r.x)]
-            self._norm_operand(d, r.x, reads)
-            d.nrm_z = _ptr(r.x.buf.act, r.x.c0)        # this launch writes the activated tensor it normalises
+            if not self._is_virtual(r.x):                  # lazy: this launch writes the activated tensor it normalises
+                d.nrm_z = _ptr(r.x.buf.act, r.x.c0)
+                writes.append(self._ra(r.x))
         else:
             d.x = _ptr(r.x.buf.act, r.x.c0)
-            reads, writes = [self._ra(r.x)], []
+            reads.append(self._ra(r.x))
         if self.training:
             d.w = _ptr(net.W_train, L.w_off)
-            reads.append(region(net.W_train, L.w_off, L.w_off + L.numel))
+            reads.append(weight_region(net.W_train, L))
             if kind == "bn":
                 d.y = _ptr(r.y.buf.raw, r.y.c0)
                 d.stats = _ptr(self.ws, L.bn_off)
-                d.stats_sq_off = net.CB
-                d.stats_replicas = self._replicas(r.y.buf.M)
-                d.stats_rep_stride = 2 * net.CB
-                writes += [self._rr(r.y), (self.ws.data_ptr() + 1, L.bn_off, L.bn_off + L.cout)]
+                d.stats_sq_off, d.stats_replicas, d.stats_rep_stride = net.CB, self._replicas(r.y.buf.M), 2 * net.CB
+                writes += [self._rr(r.y), stats_region(self.ws, L.bn_off, L.bn_off + L.cout)]
         else:
             d.w = _ptr(net.W_infer, L.w_off)
-            reads.append(region(net.W_infer, L.w_off, L.w_off + L.numel))
+            reads.append(weight_region(net.W_infer, L))
             if kind == "bn":
                 d.y = _ptr(r.y.buf.act, r.y.c0)
                 d.bias = _ptr(net.fold_bias, L.bn_off)
                 d.relu = 1
-                reads.append(region(net.fold_bias, L.bn_off, L.bn_off + L.cout))
+                reads.append(self._rfold(L))
                 writes.append(self._ra(r.y))
         if kind == "resid":
             t: Slice = r.extra["trunk"]
@@ -915,43 +793,45 @@ class Lowering:
             d.ld_res = t.buf.C
             d.scale = r.extra["scale"]
             d.relu = 1 if r.extra["relu"] else 0
-            reads += [self._ra(t), region(net.P, L.bias_off, L.bias_off + L.cout)]
+            reads += [self._ra(t), bias_region(net.P, L)]
             writes.append(self._ra(r.y))
         elif kind == "f32":
             tgt = r.y.buf
             if L.has_bn and not self.training:       # inference: BN folded, write the embedding buffer directly
                 tgt = self.bufs[self.head_out]
                 d.bias = _ptr(net.fold_bias, L.bn_off)
-                reads.append(region(net.fold_bias, L.bn_off, L.bn_off + L.cout))
+                reads.append(self._rfold(L))
             d.y = _ptr(tgt.act, r.y.c0)
             d.out_f32 = 1
             if L.has_bias:
                 d.bias = _ptr(net.P, L.bias_off)
             writes.append((tgt.act.data_ptr(), r.y.c0, r.y.c0 + r.y.C))
-        self._emit(self.fwd, "conv_fwd:" + L.name, lib.fn_conv2d_fwd, C.byref(d), keep=(d,), r=reads, w=writes)
+        emit(self.fwd, "conv_fwd:" + L.name, lib.fn_conv2d_fwd, C.byref(d), keep=(d,), r=reads, w=writes)
 
-    def _fwd_block35(self, r: Rec):
-        net, pre = self.net, r.extra["prefix"]
-        L1 = [net.layers[f"{pre}/{n}"] for n in ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv2/Conv2d_0a_1x1")]
-        L3 = [net.layers[f"{pre}/{n}"] for n in ("tower_conv1/Conv2d_0b_3x3", "tower_conv2/Conv2d_0b_3x3", "tower_conv2/Conv2d_0c_3x3")]
-        Lu = net.layers[f"{pre}/up"]
-        arr = lambda ptrs: (C.c_void_p * 3)(*ptrs)
-        w1, w3 = arr([_ptr(net.W_infer, L.w_off) for L in L1]), arr([_ptr(net.W_infer, L.w_off) for L in L3])
-        b1, b3 = arr([_ptr(net.fold_bias, L.bn_off) for L in L1]), arr([_ptr(net.fold_bias, L.bn_off) for L in L3])
-        reads = [self._ra(r.x)] + [region(net.W_infer, L.w_off, L.w_off + L.numel) for L in L1 + L3 + [Lu]] + \
-                [region(net.fold_bias, L.bn_off, L.bn_off + L.cout) for L in L1 + L3] + [region(net.P, Lu.bias_off, Lu.bias_off + Lu.cout)]
-        warm, warm_bytes = self._warm_next_block(pre, ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv2/Conv2d_0a_1x1",
-                                                       "tower_conv1/Conv2d_0b_3x3", "tower_conv2/Conv2d_0b_3x3", "tower_conv2/Conv2d_0c_3x3", "up"), reads)
-        self._emit(self.fwd, "block35_fused:" + pre, net.lib.fn_block35_infer_warm, _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, w1, w3,
-                   _ptr(net.W_infer, Lu.w_off), b1, b3, _ptr(net.P, Lu.bias_off), r.extra["scale"], 1 if r.extra["relu"] else 0,
-                   warm, warm_bytes, self.dt, keep=(w1, w3, b1, b3), r=reads, w=[self._ra(r.y)])
+    def _fwd_fused_block(self, r: Rec):
+        net, kind, pre = self.net, r.extra["kind"], r.extra["prefix"]
+        names = FUSED_BLOCKS[kind][3]
+        Ls, Lu = [net.layers[f"{pre}/{n}"] for n in names], net.layers[f"{pre}/up"]
+        ws, up_w = [_ptr(net.W_infer, L.w_off) for L in Ls], _ptr(net.W_infer, Lu.w_off)
+        bs, up_b = [_ptr(net.fold_bias, L.bn_off) for L in Ls], _ptr(net.P, Lu.bias_off)
+        reads = [self._ra(r.x)] + [weight_region(net.W_infer, L) for L in Ls + [Lu]] + [self._rfold(L) for L in Ls] + [bias_region(net.P, Lu)]
+        warm, warm_bytes = self._warm_next_block(pre, names + ("up",), reads)
+        if kind == "block35":      # fn_block35_infer_warm takes its three 1x1 and its three 3x3 layers as pointer arrays
+            arr = lambda ptrs: (C.c_void_p * 3)(*ptrs)
+            keep = w1, w3, b1, b3 = arr(ws[:3]), arr(ws[3:]), arr(bs[:3]), arr(bs[3:])
+            layers = (w1, w3, up_w, b1, b3, up_b)
+        else:
+            keep, layers = (), (*ws, up_w, *bs, up_b)
+        emit(self.fwd, f"{kind}_fused:{pre}", getattr(net.lib, f"fn_{kind}_infer_warm"), _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, *layers,
+             r.extra["scale"], 1 if r.extra["relu"] else 0, warm, warm_bytes, self.dt, keep=keep, r=reads, w=[self._ra(r.y)])
 
     def _warm_next_block(self, pre: str, names, reads: list):
-        """Warm-ahead range of a fused block launch: the inference weight packs of the NEXT block of the same kind (the launch's spare
-        workgroups read them into every XCD's L2: fn_block17_infer_warm).  (None, 0) for the last block or FACENET_WARM_AHEAD=0."""
+        """Warm-ahead range of a fused block launch: the inference weight packs of the NEXT block of the same kind.  The launch's
+        spare workgroups (180 images on 256 CUs) read them into every XCD's L2 (fn_block17_infer_warm): from memory the next
+        block's weight stream costs 50 us per launch, from a warm L2 ~40.  (None, 0) for the last block or FACENET_WARM_AHEAD=0."""
         net = self.net
         head, _, idx = pre.rpartition("/")
-        if not (idx.isdigit() and f"{head}/{int(idx) + 1}/up" in net.layers and int(os.environ.get("FACENET_WARM_AHEAD", "1"))):
+        if not (idx.isdigit() and f"{head}/{int(idx) + 1}/up" in net.layers and self.opt.warm_ahead):
             return None, 0
         nxt = [net.layers[f"{head}/{int(idx) + 1}/{n}"] for n in names]
         lo, hi = min(L.w_off for L in nxt), max(L.w_off + L.numel for L in nxt)
@@ -963,21 +843,6 @@ class Lowering:
         reads.append(region(net.W_infer, lo, hi))
         return _ptr(net.W_infer, lo), nbytes
 
-    def _fwd_block17(self, r: Rec):
-        net, pre = self.net, r.extra["prefix"]
-        Ls = [net.layers[f"{pre}/{n}"] for n in ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv1/Conv2d_0b_1x7",
-                                                 "tower_conv1/Conv2d_0c_7x1", "up")]
-        ws = [_ptr(net.W_infer, L.w_off) for L in Ls]
-        bs = [_ptr(net.fold_bias, L.bn_off) for L in Ls[:4]] + [_ptr(net.P, Ls[4].bias_off)]
-        reads = [self._ra(r.x)] + [region(net.W_infer, L.w_off, L.w_off + L.numel) for L in Ls] + \
-                [region(net.fold_bias, L.bn_off, L.bn_off + L.cout) for L in Ls[:4]] + [region(net.P, Ls[4].bias_off, Ls[4].bias_off + Ls[4].cout)]
-        # warm-ahead: the launch's spare workgroups (180 images on 256 CUs) read the NEXT block's weight packs into every XCD's L2
-        # (fn_block17_infer_warm): from memory the next block's weight stream costs 50 us per launch, from a warm L2 ~40
-        warm, warm_bytes = self._warm_next_block(pre, ("tower_conv0/Conv2d_1x1", "tower_conv1/Conv2d_0a_1x1", "tower_conv1/Conv2d_0b_1x7",
-                                                       "tower_conv1/Conv2d_0c_7x1", "up"), reads)
-        self._emit(self.fwd, "block17_fused:" + pre, net.lib.fn_block17_infer_warm, _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, *ws, *bs,
-                   r.extra["scale"], 1 if r.extra["relu"] else 0, warm, warm_bytes, self.dt, r=reads, w=[self._ra(r.y)])
-
     def _fwd_bn(self, r: Rec):
         if not self.training:
             return  # folded into the convolution epilogue (facenet/tfutils.py:244-250)
@@ -988,12 +853,11 @@ class Lowering:
             self.fin_reps[o:o + Cc] = self._replicas(b.M)
             self.fin_count[o:o + Cc] = b.M
             return
-        self._emit(self.fwd, "bn_relu_fwd:" + b.name, lib.fn_bn_relu_train_fwd, _ptr(b.raw, c0), b.C, _ptr(b.act, c0), b.C, b.M, Cc,
-                   _ptr(self.ws, o), net.CB, self._replicas(b.M), 2 * net.CB, _ptr(net.P, net.beta_base + o), _ptr(self.save_scale, o),
-                   _ptr(self.save_shift, o), _ptr(net.S_mean, o), _ptr(net.S_var, o), net.bn_momentum, BN_EPS, 1 if r.extra["relu"] else 0, self.dt,
-                   r=[self._rr(r.y), (self.ws.data_ptr() + 1, o, o + Cc), region(net.P, net.beta_base + o, net.beta_base + o + Cc)],
-                   w=[self._ra(r.y), region(self.save_scale, o, o + Cc), region(self.save_shift, o, o + Cc),
-                      region(net.S_mean, o, o + Cc), region(net.S_var, o, o + Cc)])
+        emit(self.fwd, "bn_relu_fwd:" + b.name, lib.fn_bn_relu_train_fwd, _ptr(b.raw, c0), b.C, _ptr(b.act, c0), b.C, b.M, Cc,
+             _ptr(self.ws, o), net.CB, self._replicas(b.M), 2 * net.CB, _ptr(net.P, net.beta_base + o), _ptr(self.save_scale, o),
+             _ptr(self.save_shift, o), _ptr(net.S_mean, o), _ptr(net.S_var, o), net.bn_momentum, BN_EPS, 1 if r.extra["relu"] else 0, self.dt,
+             r=[self._rr(r.y), stats_region(self.ws, o, o + Cc), self._rbeta(o, Cc)],
+             w=[self._ra(r.y)] + self._rsaved(o, Cc) + self._rmoving(o, Cc))
 
     def _fwd_maxpool(self, r: Rec):
         x, y = r.x, r.y
@@ -1001,39 +865,37 @@ class Lowering:
         if self.training and x.buf.name != "input":   # 1-byte argmax map for the backward (first maximum of every window)
             am = torch.zeros(self.N, y.buf.H, y.buf.W, x.C, dtype=torch.uint8, device=self.net.device)
             r.extra["argmax"] = am
-        self._emit(self.fwd, "maxpool_fwd", self.net.lib.fn_maxpool3x3s2_fwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.act, y.c0), y.buf.C,
-                   self.N, x.buf.H, x.buf.W, x.C, _ptr(am) if am is not None else None, self.dt,
-                   r=[self._ra(x)], w=[self._ra(y)] + ([region(am)] if am is not None else []))
+        emit(self.fwd, "maxpool_fwd", self.net.lib.fn_maxpool3x3s2_fwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.act, y.c0), y.buf.C,
+             self.N, x.buf.H, x.buf.W, x.C, _ptr(am) if am is not None else None, self.dt,
+             r=[self._ra(x)], w=[self._ra(y)] + ([region(am)] if am is not None else []))
 
     def _fwd_avgpool(self, r: Rec):
         x, y = r.x, r.y
-        self._emit(self.fwd, "avgpool_fwd", self.net.lib.fn_avgpool_fwd, _ptr(x.buf.act), _ptr(y.buf.act), self.N, x.buf.H * x.buf.W, x.C, self.dt,
-                   r=[self._ra(x)], w=[self._ra(y)])
+        emit(self.fwd, "avgpool_fwd", self.net.lib.fn_avgpool_fwd, _ptr(x.buf.act), _ptr(y.buf.act), self.N, x.buf.H * x.buf.W, x.C, self.dt,
+             r=[self._ra(x)], w=[self._ra(y)])
 
     def _fwd_avgpool3(self, r: Rec):
         x, y = r.x, r.y
-        self._emit(self.fwd, "avgpool3x3s1_fwd", self.net.lib.fn_avgpool3x3s1_fwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.act, y.c0),
-                   y.buf.C, self.N, x.buf.H, x.buf.W, x.C, self.dt, r=[self._ra(x)], w=[self._ra(y)])
+        emit(self.fwd, "avgpool3x3s1_fwd", self.net.lib.fn_avgpool3x3s1_fwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.act, y.c0),
+             y.buf.C, self.N, x.buf.H, x.buf.W, x.C, self.dt, r=[self._ra(x)], w=[self._ra(y)])
 
     def _dropout_args(self, r: Rec):
         return (self.N, r.x.C, r.extra["keep"], self.net.seed & 0xFFFFFFFF, self.rank, _ptr(self.step_word), self.dt)
 
     def _fwd_dropout(self, r: Rec):
         x, y = r.x, r.y
-        self._emit(self.fwd, "dropout_fwd", self.net.lib.fn_dropout_fwd, _ptr(x.buf.act), _ptr(y.buf.act), *self._dropout_args(r),
-                   r=[self._ra(x), region(self.step_word)], w=[self._ra(y)])
+        emit(self.fwd, "dropout_fwd", self.net.lib.fn_dropout_fwd, _ptr(x.buf.act), _ptr(y.buf.act), *self._dropout_args(r),
+             r=[self._ra(x), region(self.step_word)], w=[self._ra(y)])
 
     def _fwd_head_bn(self, r: Rec):
         if not self.training:
             return  # folded into the Dense epilogue
         net, L = self.net, r.layer
         o = L.bn_off
-        self._emit(self.fwd, "head_bn_fwd", net.lib.fn_head_bn_fwd, _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, net.E,
-                   _ptr(net.P, net.beta_base + o), _ptr(net.S_mean, o), _ptr(net.S_var, o), _ptr(self.head_mean), _ptr(self.head_rstd), 1,
-                   net.bn_momentum, BN_EPS,
-                   r=[self._ra(r.x), region(net.P, net.beta_base + o, net.beta_base + o + net.E)],
-                   w=[self._ra(r.y), region(self.head_mean), region(self.head_rstd), region(net.S_mean, o, o + net.E),
-                      region(net.S_var, o, o + net.E)])
+        emit(self.fwd, "head_bn_fwd", net.lib.fn_head_bn_fwd, _ptr(r.x.buf.act), _ptr(r.y.buf.act), self.N, net.E,
+             _ptr(net.P, net.beta_base + o), _ptr(net.S_mean, o), _ptr(net.S_var, o), _ptr(self.head_mean), _ptr(self.head_rstd), 1,
+             net.bn_momentum, BN_EPS, r=[self._ra(r.x), self._rbeta(o, net.E)],
+             w=[self._ra(r.y), region(self.head_mean), region(self.head_rstd)] + self._rmoving(o, net.E))
 
     # ---- backward (training plans only); demb = fp32 gradient wrt the un-normalised embedding ----
     def build_backward(self, demb: torch.Tensor):
@@ -1046,7 +908,7 @@ class Lowering:
         # gradients all accumulate into that slice -- emitted as ONE multi-source launch when the last of them is reached
         self._siblings: Dict[Tuple[str, int, int], List[Rec]] = {}
         self._sib_pending: Dict[Tuple[str, int, int], list] = {}
-        if self.merge_sibling_dgrads:
+        if self.opt.merge_siblings:
             for r in self.recs:
                 L = r.layer
                 if (r.kind == "conv" and r.extra.get("kind") == "bn" and L.kh == 1 and L.kw == 1 and L.stride == 1 and L.pad_h == 0
@@ -1066,20 +928,17 @@ class Lowering:
         net = self.net
         n = net.n_params - net.bias_lo
         if n > 0:
-            self._emit(lst, "grad_finalize", net.lib.fn_acc_to_float, _ptr(net.Gacc), _ptr(net.G, net.bias_lo), n, 40,
-                       r=[region(net.Gacc)], w=[region(net.G, net.bias_lo, net.n_params)])
-
-    def _mark(self, L: Layer):
-        self.bwd_marks.append((len(self.bwd), L.index))
+            emit(lst, "grad_finalize", net.lib.fn_acc_to_float, _ptr(net.Gacc), _ptr(net.G, net.bias_lo), n, 40,
+                 r=[region(net.Gacc)], w=[region(net.G, net.bias_lo, net.n_params)])
 
     def _bwd_head_bn(self, r: Rec):
         net, L = self.net, r.layer
         self.head_dy = torch.zeros(self.N, net.E, dtype=self.dtype, device=net.device)
         gb = net.beta_base + L.bn_off
-        self._emit(self.bwd, "head_bn_bwd", net.lib.fn_head_bn_bwd, _ptr(self._demb), _ptr(r.x.buf.act), _ptr(self.head_mean),
-                   _ptr(self.head_rstd), _ptr(net.G, gb), _ptr(self.head_dy), self.N, net.E, self.dt,
-                   r=[region(self._demb), self._ra(r.x), region(self.head_mean), region(self.head_rstd)],
-                   w=[region(self.head_dy), region(net.G, gb, gb + net.E)])
+        emit(self.bwd, "head_bn_bwd", net.lib.fn_head_bn_bwd, _ptr(self._demb), _ptr(r.x.buf.act), _ptr(self.head_mean),
+             _ptr(self.head_rstd), _ptr(net.G, gb), _ptr(self.head_dy), self.N, net.E, self.dt,
+             r=[region(self._demb), self._ra(r.x), region(self.head_mean), region(self.head_rstd)],
+             w=[region(self.head_dy), region(net.G, gb, gb + net.E)])
 
     def _bias_acc(self, L: Layer) -> Tuple[int, Region]:
         """(pointer, region) of the fixed-point accumulator that receives the bias gradient of layer L (net.Gacc mirrors the
@@ -1103,9 +962,9 @@ class Lowering:
                 self._dup[L.name] = dup
                 acc = self._grad_mode(t)
                 bptr, breg = self._bias_acc(L)
-                self._emit(self.bwd, "residual_bwd:" + L.name, lib.fn_residual_bwd, _ptr(y.buf.grad), _ptr(y.buf.act), _ptr(t.buf.grad),
-                           _ptr(dup), bptr, y.buf.M, y.buf.C, r.extra["scale"], 1 if r.extra["relu"] else 0, acc, self.dt,
-                           r=[self._rg(y), self._ra(y)], w=[self._rg(t), region(dup), breg])
+                emit(self.bwd, "residual_bwd:" + L.name, lib.fn_residual_bwd, _ptr(y.buf.grad), _ptr(y.buf.act), _ptr(t.buf.grad),
+                     _ptr(dup), bptr, y.buf.M, y.buf.C, r.extra["scale"], 1 if r.extra["relu"] else 0, acc, self.dt,
+                     r=[self._rg(y), self._ra(y)], w=[self._rg(t), region(dup), breg])
             dy_ptr, ld_dy, dy_reg = _ptr(dup), y.buf.C, region(dup)
         elif kind == "f32":
             dy_ptr, ld_dy, dy_reg = _ptr(self.head_dy), net.E, region(self.head_dy)
@@ -1121,42 +980,24 @@ class Lowering:
             wreads.append(self._ra(x))
         d.y = dy_ptr
         d.dw = _ptr(net.G, L.w_off)
-        self._emit(self.bwd, "conv_wgrad:" + L.name, lib.fn_conv2d_wgrad, C.byref(d), keep=(d,),
-                   r=wreads, w=[region(net.G, L.w_off, L.w_off + L.numel)])
+        emit(self.bwd, "conv_wgrad:" + L.name, lib.fn_conv2d_wgrad, C.byref(d), keep=(d,), r=wreads, w=[weight_region(net.G, L)])
         sib_key = (x.buf.name, x.c0, x.C)
         if sib_key in self._siblings and any(r is m for m in self._siblings[sib_key]):
             pend = self._sib_pending.setdefault(sib_key, [])
             pend.append((L, dy_ptr, ld_dy, dy_reg))
             if len(pend) == len(self._siblings[sib_key]):
-                (L0, p0, ld0, reg0), rest = pend[0], pend[1:]
-                g = self._desc(L0, x, y)
-                g.Cout, g.ld_y, g.y = L0.cout, ld0, p0
-                g.w = _ptr(net.Wt_train, L0.w_off)
-                g.dx = _ptr(x.buf.grad, x.c0)
-                g.accumulate = self._grad_mode(x)
-                rd = [reg0, region(net.Wt_train, L0.w_off, L0.w_off + L0.numel)]
-                wr = [self._rg(x)]
+                g, rd, wr = self._dgrad_desc(x, y, *pend[0])
                 self._fuse_residual(g, x, rd, wr)
-                for i, (Li, pi, ldi, regi) in enumerate(rest):
-                    setattr(g, ("dy2", "dy3")[i], pi)
-                    setattr(g, ("w2", "w3")[i], _ptr(net.Wt_train, Li.w_off))
-                    setattr(g, ("Cout2", "Cout3")[i], Li.cout)
-                    setattr(g, ("ld_y2", "ld_y3")[i], ldi)
-                    rd += [regi, region(net.Wt_train, Li.w_off, Li.w_off + Li.numel)]
-                self._emit(self.bwd, "conv_dgrad:" + "+".join(p[0].name for p in pend), lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
-                           r=rd, w=wr)
+                for i, (Li, pi, ldi, regi) in enumerate(pend[1:], 2):      # the other sources: fn_conv_desc.dy2 / w2 / ..., dy3 / ...
+                    for field, v in (("dy", pi), ("w", _ptr(net.Wt_train, Li.w_off)), ("Cout", Li.cout), ("ld_y", ldi)):
+                        setattr(g, f"{field}{i}", v)
+                    rd += [regi, weight_region(net.Wt_train, Li)]
+                emit(self.bwd, "conv_dgrad:" + "+".join(p[0].name for p in pend), lib.fn_conv2d_dgrad, C.byref(g), keep=(g,), r=rd, w=wr)
         elif x.buf.name != "input":
-            g = self._desc(L, x, y)
-            g.ld_y = ld_dy
-            g.y = dy_ptr
-            g.w = _ptr(net.Wt_train, L.w_off)
-            g.dx = _ptr(x.buf.grad, x.c0)
-            g.accumulate = self._grad_mode(x)
-            rd = [dy_reg, region(net.Wt_train, L.w_off, L.w_off + L.numel)]
-            wr = [self._rg(x)]
+            g, rd, wr = self._dgrad_desc(x, y, L, dy_ptr, ld_dy, dy_reg)
             bnr = [r_ for r_ in self.bn_ranges.get(x.buf.name, []) if r_[0] == x.c0 and r_[1] == x.C]
-            if self.fuse_bn_bwd and bnr and g.accumulate == 0 and self.readers.get(x.buf.name, 0) == 1 and x.buf.raw is not None:
-                o = x.buf.bn_off + x.c0            # this dgrad is the only producer of d(BN output): reduce in its epilogue
+            if bnr and g.accumulate == 0 and self.readers.get(x.buf.name, 0) == 1 and x.buf.raw is not None:
+                o = x.buf.bn_off + x.c0            # this dgrad is the only producer of d(BN output): reduce BN-backward in its epilogue
                 reps = self._replicas(x.buf.M)
                 g.bn_y = _ptr(x.buf.raw, x.c0)
                 g.ld_bn_y = x.buf.C
@@ -1165,10 +1006,19 @@ class Lowering:
                 g.bn_acc, g.bn_sq_off, g.bn_replicas, g.bn_rep_stride = _ptr(self.ws_b, o), net.CB, reps, 2 * net.CB
                 g.bn_relu = 1 if bnr[0][2] else 0
                 self.bn_reduced[(x.buf.name, x.c0, x.C)] = reps
-                rd += [self._rr(x), region(self.save_scale, o, o + x.C), region(self.save_shift, o, o + x.C)]
-                wr.append((self.ws_b.data_ptr() + 1, o, o + x.C))
-            self._emit(self.bwd, "conv_dgrad:" + L.name, lib.fn_conv2d_dgrad, C.byref(g), keep=(g,), r=rd, w=wr)
-        self._mark(L)
+                rd += [self._rr(x)] + self._rsaved(o, x.C)
+                wr.append(stats_region(self.ws_b, o, o + x.C))
+            emit(self.bwd, "conv_dgrad:" + L.name, lib.fn_conv2d_dgrad, C.byref(g), keep=(g,), r=rd, w=wr)
+        self.bwd_marks.append((len(self.bwd), L.index))
+
+    def _dgrad_desc(self, x: Slice, y: Slice, L: Layer, dy_ptr: int, ld_dy: int, dy_reg: Region):
+        """(descriptor, reads, writes) of the data gradient of layer L into x; y gives the output map, dy_* where its gradient lies."""
+        g = self._desc(L, x, y)
+        g.ld_y, g.y = ld_dy, dy_ptr
+        g.w = _ptr(self.net.Wt_train, L.w_off)
+        g.dx = _ptr(x.buf.grad, x.c0)
+        g.accumulate = self._grad_mode(x)
+        return g, [dy_reg, weight_region(self.net.Wt_train, L)], [self._rg(x)]
 
     def _fuse_residual(self, g: ConvDesc, x: Slice, rd: list, wr: list):
         """`g` is the launch that completes the gradient of x.  When x is the whole output of a residual block and `g` only adds
@@ -1176,7 +1026,7 @@ class Lowering:
         (fn_conv_desc.rb_*): nothing else ever reads the completed gradient of x, so it is not even written."""
         net = self.net
         prev = self._resid_of.get(x.buf.name)
-        if not (self.fuse_residual_bwd and prev is not None and g.accumulate == 1 and x.c0 == 0 and x.C == x.buf.C):
+        if not (self.opt.fuse_residual_bwd and prev is not None and g.accumulate == 1 and x.c0 == 0 and x.C == x.buf.C):
             return
         Lp, t = prev.layer, prev.extra["trunk"]
         if not (t.c0 == 0 and t.C == t.buf.C == x.buf.C):
@@ -1201,11 +1051,11 @@ class Lowering:
         o = b.bn_off + c0
         gb = net.beta_base + o
         reps = self.bn_reduced.get((b.name, c0, Cc), 0)
-        self._emit(self.bwd, "bn_relu_bwd:" + b.name, net.lib.fn_bn_relu_train_bwd, _ptr(b.grad, c0), b.C, _ptr(b.raw, c0), b.C, b.M, Cc,
-                   _ptr(net.P, gb), _ptr(self.save_scale, o), _ptr(self.save_shift, o), _ptr(net.G, gb),
-                   _ptr(self.ws_b, o), net.CB, max(1, reps), 2 * net.CB, 1 if reps else 0, 1 if r.extra["relu"] else 0, self.dt,
-                   r=[self._rr(r.y), region(net.P, gb, gb + Cc), region(self.save_scale, o, o + Cc), region(self.save_shift, o, o + Cc)],
-                   w=[self._rg(r.y), region(net.G, gb, gb + Cc), (self.ws_b.data_ptr() + 1, o, o + Cc)])
+        emit(self.bwd, "bn_relu_bwd:" + b.name, net.lib.fn_bn_relu_train_bwd, _ptr(b.grad, c0), b.C, _ptr(b.raw, c0), b.C, b.M, Cc,
+             _ptr(net.P, gb), _ptr(self.save_scale, o), _ptr(self.save_shift, o), _ptr(net.G, gb),
+             _ptr(self.ws_b, o), net.CB, max(1, reps), 2 * net.CB, 1 if reps else 0, 1 if r.extra["relu"] else 0, self.dt,
+             r=[self._rr(r.y), self._rbeta(o, Cc)] + self._rsaved(o, Cc),
+             w=[self._rg(r.y), region(net.G, gb, gb + Cc), stats_region(self.ws_b, o, o + Cc)])
 
     def _bwd_maxpool(self, r: Rec):
         x, y = r.x, r.y
@@ -1213,27 +1063,27 @@ class Lowering:
             return
         acc = self._grad_mode(x)
         am = r.extra.get("argmax")
-        self._emit(self.bwd, "maxpool_bwd", self.net.lib.fn_maxpool3x3s2_bwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.grad, y.c0), y.buf.C,
-                   _ptr(x.buf.grad, x.c0), x.buf.C, self.N, x.buf.H, x.buf.W, x.C, _ptr(am) if am is not None else None, acc, self.dt,
-                   r=[self._ra(x), self._rg(y)] + ([region(am)] if am is not None else []), w=[self._rg(x)])
+        emit(self.bwd, "maxpool_bwd", self.net.lib.fn_maxpool3x3s2_bwd, _ptr(x.buf.act, x.c0), x.buf.C, _ptr(y.buf.grad, y.c0), y.buf.C,
+             _ptr(x.buf.grad, x.c0), x.buf.C, self.N, x.buf.H, x.buf.W, x.C, _ptr(am) if am is not None else None, acc, self.dt,
+             r=[self._ra(x), self._rg(y)] + ([region(am)] if am is not None else []), w=[self._rg(x)])
 
     def _bwd_avgpool(self, r: Rec):
         x, y = r.x, r.y
         assert self._grad_mode(x) == 0
-        self._emit(self.bwd, "avgpool_bwd", self.net.lib.fn_avgpool_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), self.N, x.buf.H * x.buf.W, x.C, self.dt,
-                   r=[self._rg(y)], w=[self._rg(x)])
+        emit(self.bwd, "avgpool_bwd", self.net.lib.fn_avgpool_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), self.N, x.buf.H * x.buf.W, x.C, self.dt,
+             r=[self._rg(y)], w=[self._rg(x)])
 
     def _bwd_avgpool3(self, r: Rec):
         x, y = r.x, r.y
         acc = self._grad_mode(x)
-        self._emit(self.bwd, "avgpool3x3s1_bwd", self.net.lib.fn_avgpool3x3s1_bwd, _ptr(y.buf.grad, y.c0), y.buf.C, _ptr(x.buf.grad, x.c0),
-                   x.buf.C, self.N, x.buf.H, x.buf.W, x.C, acc, self.dt, r=[self._rg(y)] + ([self._rg(x)] if acc else []), w=[self._rg(x)])
+        emit(self.bwd, "avgpool3x3s1_bwd", self.net.lib.fn_avgpool3x3s1_bwd, _ptr(y.buf.grad, y.c0), y.buf.C, _ptr(x.buf.grad, x.c0),
+             x.buf.C, self.N, x.buf.H, x.buf.W, x.C, acc, self.dt, r=[self._rg(y)] + ([self._rg(x)] if acc else []), w=[self._rg(x)])
 
     def _bwd_dropout(self, r: Rec):
         x, y = r.x, r.y
         assert self._grad_mode(x) == 0
-        self._emit(self.bwd, "dropout_bwd", self.net.lib.fn_dropout_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), *self._dropout_args(r),
-                   r=[self._rg(y), region(self.step_word)], w=[self._rg(x)])
+        emit(self.bwd, "dropout_bwd", self.net.lib.fn_dropout_bwd, _ptr(y.buf.grad), _ptr(x.buf.grad), *self._dropout_args(r),
+             r=[self._rg(y), region(self.step_word)], w=[self._rg(x)])
 
     # ---- execution -----------------------------------------------------------------------------
     @staticmethod

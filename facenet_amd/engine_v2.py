@@ -22,7 +22,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from .engine import Lowering, Network
+from .engine import Lowering, Network, towers
 
 SCOPE = "InceptionResnetV2"
 BN_MOMENTUM_V2 = 0.995          # inception_resnet_v2.py:232 (slim batch_norm decay)
@@ -39,35 +39,35 @@ DEFAULT_CONFIG_V2 = {           # models/configs/inception_resnet_v2.yaml
 
 # residual blocks (inception_resnet_v2.py:40-100): towers and the scale of `up`; up's width is the trunk's
 V2_BLOCKS = {
-    "block35": [[("Conv2d_1x1", 32, (1, 1))],
-                [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3))],
-                [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 48, (3, 3)), ("Conv2d_0c_3x3", 64, (3, 3))]],
-    "block17": [[("Conv2d_1x1", 192, (1, 1))],
-                [("Conv2d_0a_1x1", 128, (1, 1)), ("Conv2d_0b_1x7", 160, (1, 7)), ("Conv2d_0c_7x1", 192, (7, 1))]],
-    "block8": [[("Conv2d_1x1", 192, (1, 1))],
-               [("Conv2d_0a_1x1", 192, (1, 1)), ("Conv2d_0b_1x3", 224, (1, 3)), ("Conv2d_0c_3x1", 256, (3, 1))]],
+    "block35": towers([("Conv2d_1x1", 32, (1, 1))],
+                      [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 32, (3, 3))],
+                      [("Conv2d_0a_1x1", 32, (1, 1)), ("Conv2d_0b_3x3", 48, (3, 3)), ("Conv2d_0c_3x3", 64, (3, 3))]),
+    "block17": towers([("Conv2d_1x1", 192, (1, 1))],
+                      [("Conv2d_0a_1x1", 128, (1, 1)), ("Conv2d_0b_1x7", 160, (1, 7)), ("Conv2d_0c_7x1", 192, (7, 1))]),
+    "block8": towers([("Conv2d_1x1", 192, (1, 1))],
+                     [("Conv2d_0a_1x1", 192, (1, 1)), ("Conv2d_0b_1x3", 224, (1, 3)), ("Conv2d_0c_3x1", 256, (3, 1))]),
 }
 
 
 def mixed_5a_towers(branch):
     b = branch
-    return [[("Conv2d_1x1", b[0][0], (1, 1))],
-            [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_0b_5x5", b[1][1], (5, 5))],
-            [("Conv2d_0a_1x1", b[2][0], (1, 1)), ("Conv2d_0b_3x3", b[2][1], (3, 3)), ("Conv2d_0c_3x3", b[2][2], (3, 3))],
-            [("AvgPool_0a_3x3",), ("Conv2d_0b_1x1", b[3][0], (1, 1))]]
+    return towers([("Conv2d_1x1", b[0][0], (1, 1))],
+                  [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_0b_5x5", b[1][1], (5, 5))],
+                  [("Conv2d_0a_1x1", b[2][0], (1, 1)), ("Conv2d_0b_3x3", b[2][1], (3, 3)), ("Conv2d_0c_3x3", b[2][2], (3, 3))],
+                  [("AvgPool_0a_3x3",), ("Conv2d_0b_1x1", b[3][0], (1, 1))])
 
 
 def mixed_6a_towers(branch):
     b = branch
-    return [[("Conv2d_1a_3x3", b[0][0], (3, 3), 2, "valid")],
-            [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_0b_3x3", b[1][1], (3, 3)), ("Conv2d_1a_3x3", b[1][2], (3, 3), 2, "valid")]]
+    return towers([("Conv2d_1a_3x3", b[0][0], (3, 3), 2, "valid")],
+                  [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_0b_3x3", b[1][1], (3, 3)), ("Conv2d_1a_3x3", b[1][2], (3, 3), 2, "valid")])
 
 
 def mixed_7a_towers(branch):
     b = branch
-    return [[("Conv2d_0a_1x1", b[0][0], (1, 1)), ("Conv2d_1a_3x3", b[0][1], (3, 3), 2, "valid")],
-            [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_1a_3x3", b[1][1], (3, 3), 2, "valid")],
-            [("Conv2d_0a_1x1", b[2][0], (1, 1)), ("Conv2d_0b_3x3", b[2][1], (3, 3)), ("Conv2d_1a_3x3", b[2][2], (3, 3), 2, "valid")]]
+    return towers([("Conv2d_0a_1x1", b[0][0], (1, 1)), ("Conv2d_1a_3x3", b[0][1], (3, 3), 2, "valid")],
+                  [("Conv2d_0a_1x1", b[1][0], (1, 1)), ("Conv2d_1a_3x3", b[1][1], (3, 3), 2, "valid")],
+                  [("Conv2d_0a_1x1", b[2][0], (1, 1)), ("Conv2d_0b_3x3", b[2][1], (3, 3)), ("Conv2d_1a_3x3", b[2][2], (3, 3), 2, "valid")])
 
 
 def map_sizes(image_size: int) -> Tuple[int, int, int]:

@@ -36,6 +36,18 @@ def region(t: torch.Tensor, lo: int = 0, hi: Optional[int] = None) -> Region:
     return (t.data_ptr(), lo, t.numel() if hi is None else hi)
 
 
+def stats_region(ws: torch.Tensor, lo: int, hi: int) -> Region:
+    """BatchNorm channels [lo, hi) of a statistics workspace (the plans' ``ws`` / ``ws_b``).  The workspace holds replicas x
+    (sum | sum of squares) x channels, so a channel range is no element interval of it: data_ptr() + 1 is a second base id of the
+    same tensor whose intervals are channel ranges (whoever touches the whole tensor, like the zeroing launch, names both)."""
+    return (ws.data_ptr() + 1, lo, hi)
+
+
+def emit(ops: List[Op], name: str, fn: Callable, *args, keep=(), r=(), w=()):
+    """Append the launch ``fn(*args, stream)`` that reads regions ``r`` and writes regions ``w`` to a launch list."""
+    ops.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
+
+
 class _Tracker:
     """last writer / readers-since per (base, interval); intervals of one base are identical, nested or disjoint."""
 

@@ -31,8 +31,8 @@ import torch
 
 from . import _lib, parallel
 from .config import Config
-from .engine import BN_EPS, L2_WEIGHT, Lowering, Network, _pad8, _ptr
-from .schedule import Op, Schedule, StreamSet, levelize, make_events, region, run_schedule, torch_op
+from .engine import BN_EPS, L2_WEIGHT, Lowering, Network, _pad8, _ptr, bias_region, weight_region
+from .schedule import Op, Schedule, StreamSet, emit, levelize, make_events, region, run_schedule, stats_region, torch_op
 
 
 class GraphRunner:
@@ -55,6 +55,21 @@ class GraphRunner:
         return g
 
 
+def _group_host(members: List[Op], nbytes: int):
+    """Host tables of ONE grouped launch over ``members``: their descriptors, n opaque records of ``nbytes`` and the n + 1
+    workgroup offsets, for the library's group-build call to fill."""
+    n = len(members)
+    return (_lib.ConvDesc * n)(*[m.keep[0] for m in members]), (C.c_uint8 * (nbytes * n))(), (C.c_int32 * (n + 1))()
+
+
+def _group_upload(net: Network, members: List[Op], host_args, host_prefix):
+    """Upload the filled tables once; the grouped launch reads and writes what its members did.
+    -> (device records, device offsets, reads, writes)"""
+    dev_args = torch.frombuffer(bytearray(host_args), dtype=torch.uint8).to(net.device)
+    dev_prefix = torch.tensor(list(host_prefix), dtype=torch.int32, device=net.device)
+    return dev_args, dev_prefix, tuple(r for m in members for r in m.reads), tuple(w for m in members for w in m.writes)
+
+
 def group_wgrads(ops: List[Op], net: Network) -> List[Op]:
     """Weight gradients have no consumer before the optimiser (or the bucket all-reduce): pull every ``conv_wgrad`` launch
     out of ``ops`` and append ONE grouped launch per tile variant at the end (fn_conv2d_wgrad_grouped), planned once on the
@@ -63,43 +78,30 @@ def group_wgrads(ops: List[Op], net: Network) -> List[Op]:
     singles = [op for op in ops if op.name.startswith("conv_wgrad:") and op.keep]
     if len(singles) < 2:
         return list(ops)
-    rest = [op for op in ops if not (op.name.startswith("conv_wgrad:") and op.keep)]
+    out = [op for op in ops if not (op.name.startswith("conv_wgrad:") and op.keep)]
     groups = {}
     for op in singles:
         d = op.keep[0]
         v = lib.fn_conv2d_variant(C.byref(d), 2)
-        groups.setdefault((v + (1000000 if d.nrm_stats and v < 5000000 else 0), d.dtype), []).append(op)
+        norm = _lib.VARIANT_FLAG if d.nrm_stats and not _lib.variant_is_taps(v) else 0      # normalise-on-load members: their own groups
+        groups.setdefault((v + norm, d.dtype), []).append(op)
     nbytes = lib.fn_conv2d_wgrad_arg_bytes()
-    out = list(rest)
     split_tables, split_keep, split_writes = [], [], []
     for (variant, dt), members in sorted(groups.items()):
         n = len(members)
-        descs = (_lib.ConvDesc * n)(*[m.keep[0] for m in members])
-        host_args = (C.c_uint8 * (nbytes * n))()
-        host_prefix = (C.c_int32 * (n + 1))()
+        descs, host_args, host_prefix = _group_host(members, nbytes)
         ws_elems = C.c_int64(0)
-        total = lib.fn_conv2d_wgrad_group_build(descs, n, variant, host_args, host_prefix, None, C.byref(ws_elems))   # sizing call
-        if total < 0:
-            _lib.check(total, "wgrad_group_build")
+        _lib.check(min(0, lib.fn_conv2d_wgrad_group_build(descs, n, variant, host_args, host_prefix, None, C.byref(ws_elems))),
+                   "wgrad_group_build")                                                                     # sizing call
         # split layers write one fp32 slab per pixel split, summed in order by fn_conv2d_wgrad_reduce: no atomics, same bits every run
         ws = torch.empty(max(1, ws_elems.value), dtype=torch.float32, device=net.device)
         total = lib.fn_conv2d_wgrad_group_build(descs, n, variant, host_args, host_prefix, _ptr(ws), C.byref(ws_elems))
-        if total < 0:
-            _lib.check(total, "wgrad_group_build")
-        dev_args = torch.frombuffer(bytearray(host_args), dtype=torch.uint8).to(net.device)
-        dev_prefix = torch.tensor(list(host_prefix), dtype=torch.int32, device=net.device)
-        reads, writes = [], []
-        for m in members:
-            reads.extend(m.reads)
-            writes.extend(m.writes)
-        if variant >= 5000000:      # tap-sharing kernel: 5000000 + BMW*1000 + taps*10 + (stride 2)
-            code = variant - 5000000
-            name = f"conv_wgrad_taps:{code // 1000}x{code % 1000 // 10}" + ("s2" if code % 10 else "")
-        else:
-            name = f"conv_wgrad_grouped:{variant % 1000000 // 1000}x{variant % 1000}" + (":norm" if variant >= 1000000 else "")
-        out.append(Op(name, lib.fn_conv2d_wgrad_grouped,
+        _lib.check(min(0, total), "wgrad_group_build")
+        dev_args, dev_prefix, reads, writes = _group_upload(net, members, host_args, host_prefix)
+        kernel = "conv_wgrad_taps" if _lib.variant_is_taps(variant) else "conv_wgrad_grouped"
+        out.append(Op(f"{kernel}:{_lib.variant_name(variant, wgrad=True)}", lib.fn_conv2d_wgrad_grouped,
                       (_ptr(dev_args), _ptr(dev_prefix), n, total, variant, dt), keep=(descs, dev_args, dev_prefix, members, ws),
-                      reads=tuple(reads), writes=tuple(writes) + (region(ws),)))
+                      reads=reads, writes=writes + (region(ws),)))
         if ws_elems.value > 0:
             split_tables.append(dev_args)
             split_keep.append(ws)
@@ -158,9 +160,9 @@ def autotune_convs(ops: Sequence[Op], net: Network, launches: int = 8, rounds: i
             continue
         setattr(d, field, 0)
         base_code = lib.fn_conv2d_variant(C.byref(d), 0 if kind == "conv_fwd" else 1)
-        base = base_code % 1000000
+        base = _lib.variant_tile(base_code)
         timings = {}
-        if base_code >= 9000000:                         # the library's own choice is the halo-tile kernel: it competes as tile 0
+        if _lib.variant_is_halo(base_code):                       # the library's own choice is the halo-tile kernel: it competes as tile 0
             base = 0
             burst(op)
             timings[0] = min(burst(op) for _ in range(rounds))
@@ -201,7 +203,7 @@ def group_convs(ops: List[Op], net: Network) -> List[Op]:
         if kind in ("conv_fwd", "conv_dgrad") and op.keep and isinstance(op.keep[0], _lib.ConvDesc) and not op.keep[0].dy2:
             d = op.keep[0]
             opi = 0 if kind == "conv_fwd" else 1
-            if lib.fn_conv2d_variant(C.byref(d), opi) >= 9000000:
+            if _lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), opi)):
                 continue                             # halo-tile kernel: a launch of its own
             plain = int(d.KH == 1 and d.KW == 1 and d.stride == 1 and d.pad_h == 0 and d.pad_w == 0)
             if opi == 0 and d.nrm_stats:
@@ -213,25 +215,15 @@ def group_convs(ops: List[Op], net: Network) -> List[Op]:
             chunk = idxs[c0:c0 + 8]
             if len(chunk) < 2:
                 continue
-            n = len(chunk)
-            descs = (_lib.ConvDesc * n)(*[ops[i].keep[0] for i in chunk])
-            host_args = (C.c_uint8 * (nbytes * n))()
-            host_prefix = (C.c_int32 * (n + 1))()
-            smem = C.c_int32(0)
-            total = lib.fn_conv2d_group_build(descs, n, opi, variant, host_args, host_prefix, C.byref(smem))
-            if total < 0:
-                _lib.check(total, "conv_group_build")
-            dev_args = torch.frombuffer(bytearray(host_args), dtype=torch.uint8).to(net.device)
-            dev_prefix = torch.tensor(list(host_prefix), dtype=torch.int32, device=net.device)
-            reads, writes = [], []
-            for i in chunk:
-                reads.extend(ops[i].reads)
-                writes.extend(ops[i].writes)
+            members, smem = [ops[i] for i in chunk], C.c_int32(0)
+            descs, host_args, host_prefix = _group_host(members, nbytes)
+            total = lib.fn_conv2d_group_build(descs, len(members), opi, variant, host_args, host_prefix, C.byref(smem))
+            _lib.check(min(0, total), "conv_group_build")
+            dev_args, dev_prefix, reads, writes = _group_upload(net, members, host_args, host_prefix)
             kname = "conv_fwd_grouped" if opi == 0 else "conv_dgrad_grouped"
-            vname = f"{variant % 1000000 // 1000}x{variant % 1000}" + (f"k{variant // 1000000}" if variant >= 1000000 else "")
-            fused_at[chunk[0]] = Op(f"{kname}:{vname}:" + "+".join(ops[i].name.split(":", 1)[1] for i in chunk),
-                                   lib.fn_conv2d_grouped, (_ptr(dev_args), _ptr(dev_prefix), n, total, variant, plain, smem.value, dt),
-                                   keep=(descs, dev_args, dev_prefix, [ops[i] for i in chunk]), reads=tuple(reads), writes=tuple(writes))
+            fused_at[chunk[0]] = Op(f"{kname}:{_lib.variant_name(variant)}:" + "+".join(m.name.split(":", 1)[1] for m in members),
+                                   lib.fn_conv2d_grouped, (_ptr(dev_args), _ptr(dev_prefix), len(members), total, variant, plain, smem.value, dt),
+                                   keep=(descs, dev_args, dev_prefix, members), reads=reads, writes=writes)
             skip.update(chunk[1:])
     out = []
     for i in order:
@@ -304,6 +296,26 @@ def optimizer_name(cfg) -> str:
     return check_optimizer("ADAM" if value is None or (isinstance(value, Config) and not value) else value)
 
 
+def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: float, center_alfa: float, prelogits_norm_factor: float,
+                         prelogits_norm_p: float):
+    """What the Trainer refuses: an unknown loss, a batch or network that does not fit it, regulariser settings out of range
+    (loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p, train_softmax.yaml:73-78)."""
+    if loss not in ("triplet", "softmax"):
+        raise ValueError(f"unknown loss {loss!r}")
+    if loss == "triplet" and batch % 3:
+        raise ValueError("triplet batches are laid out (a,p,n,...): batch must be a multiple of 3")
+    if loss == "softmax" and net.nrof_classes is None:
+        raise ValueError("softmax training needs Network(nrof_classes=...)")
+    if not (center_factor >= 0 and prelogits_norm_factor >= 0):
+        raise ValueError(f"center_factor and prelogits_norm_factor must be >= 0, got {center_factor}, {prelogits_norm_factor}")
+    if not 0 <= center_alfa <= 1:
+        raise ValueError(f"center_alfa must be in [0, 1], got {center_alfa}")
+    if not prelogits_norm_p > 0:
+        raise ValueError(f"prelogits_norm_p must be > 0, got {prelogits_norm_p}")
+    if loss == "triplet" and (center_factor > 0 or prelogits_norm_factor > 0):
+        raise ValueError("center loss and prelogits-norm loss need class labels: they belong to softmax training")
+
+
 def _streams_for(net: Network, n_streams: int) -> StreamSet:
     ss = getattr(net, "_stream_set", None)
     if ss is None or len(ss.side) < n_streams - 1:
@@ -329,21 +341,7 @@ class Trainer:
         # the RCCL path is exercised on a one-GPU box (bench.py --exchange-self, tests/test_gpu_dp.py).
         self.exchange = world_size > 1 or process_group is not None
         self.segmented = self.exchange or force_segments
-        if loss not in ("triplet", "softmax"):
-            raise ValueError(f"unknown loss {loss!r}")
-        if loss == "triplet" and batch % 3:
-            raise ValueError("triplet batches are laid out (a,p,n,...): batch must be a multiple of 3")
-        if loss == "softmax" and net.nrof_classes is None:
-            raise ValueError("softmax training needs Network(nrof_classes=...)")
-        # loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p (train_softmax.yaml:73-78)
-        if not (center_factor >= 0 and prelogits_norm_factor >= 0):
-            raise ValueError(f"center_factor and prelogits_norm_factor must be >= 0, got {center_factor}, {prelogits_norm_factor}")
-        if not 0 <= center_alfa <= 1:
-            raise ValueError(f"center_alfa must be in [0, 1], got {center_alfa}")
-        if not prelogits_norm_p > 0:
-            raise ValueError(f"prelogits_norm_p must be > 0, got {prelogits_norm_p}")
-        if loss == "triplet" and (center_factor > 0 or prelogits_norm_factor > 0):
-            raise ValueError("center loss and prelogits-norm loss need class labels: they belong to softmax training")
+        check_loss_arguments(net, batch, loss, center_factor, center_alfa, prelogits_norm_factor, prelogits_norm_p)
         self.center_factor, self.center_alfa = float(center_factor), float(center_alfa)
         self.prelogits_norm_factor, self.prelogits_norm_p = float(prelogits_norm_factor), float(prelogits_norm_p)
         self.regularized = center_factor > 0 or prelogits_norm_factor > 0
@@ -383,80 +381,23 @@ class Trainer:
         self.plan: Lowering = net.plan(batch, training=True, step_word=self.hyper.view(torch.int32)[4:5], rank=rank)
         self.demb = torch.zeros(batch, E, dtype=torch.float32, device=dev)
         self.dt = _lib.dtype_code(net.train_dtype)
-        ebuf = self.plan.embedding.buf
-        emb = ebuf.act
-        r_emb = region(emb)
+        emb = self.plan.embedding.buf.act
         self.emb = emb.view(batch, E)
         self.pre_ops: List[Op] = [
             Op("zero_grads", torch_op(lambda: (self.G.zero_(), net.Gacc.zero_())), (), writes=(region(self.G), region(net.Gacc))),
             Op("zero_bn_workspace", torch_op(lambda: (self.plan.ws.zero_(), self.plan.ws_b.zero_())), (),
-               writes=(region(self.plan.ws), (self.plan.ws.data_ptr() + 1, 0, net.CB), region(self.plan.ws_b),
-                       (self.plan.ws_b.data_ptr() + 1, 0, net.CB))),
+               writes=(region(self.plan.ws), stats_region(self.plan.ws, 0, net.CB), region(self.plan.ws_b), stats_region(self.plan.ws_b, 0, net.CB))),
         ]
         self.loss_ops: List[Op] = []
         if loss == "triplet":
-            self.embn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
-            self.dembn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
-            self._op(self.loss_ops, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(emb), _ptr(self.embn), batch, E, 1e-10,
-                     r=[r_emb], w=[region(self.embn)])
-            self._op(self.loss_ops, "triplet_loss", lib.fn_triplet_loss_fwd_bwd, _ptr(self.embn), _ptr(self.dembn), _ptr(self.loss),
-                     batch // 3, E, alpha, r=[region(self.embn)], w=[region(self.dembn), region(self.loss)])
-            self._op(self.loss_ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(self.dembn), _ptr(self.demb), batch, E, 1e-10,
-                     r=[r_emb, region(self.dembn)], w=[region(self.demb)])
+            self._build_triplet_loss(emb)
         else:
-            L = net.layers["classifier/logits"]
-            Cp, Cr = L.cout, L.cout_real
-            self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
-            self.emb_lp = torch.zeros(batch, E, dtype=net.train_dtype, device=dev)
-            self.logits = torch.zeros(batch, Cp, dtype=torch.float32, device=dev)
-            self.dlogits = torch.zeros(batch, Cp, dtype=net.train_dtype, device=dev)
-            rw = region(net.W_train, L.w_off, L.w_off + L.numel)
-            rwt = region(net.Wt_train, L.w_off, L.w_off + L.numel)
-            rgw = region(self.G, L.w_off, L.w_off + L.numel)
-            rgb = region(net.Gacc, L.bias_off - net.bias_lo, L.bias_off - net.bias_lo + L.cout)
-            d = self._cls_desc(L)
-            d.x, d.w, d.y, d.bias, d.out_f32 = _ptr(self.emb_lp), _ptr(net.W_train, L.w_off), _ptr(self.logits), _ptr(net.P, L.bias_off), 1
-            self._op(self.loss_ops, "cast_emb", lib.fn_cast_f32_to_lp, _ptr(emb), _ptr(self.emb_lp), batch * E, self.dt,
-                     r=[r_emb], w=[region(self.emb_lp)])
-            self._op(self.loss_ops, "conv_fwd:classifier", lib.fn_conv2d_fwd, C.byref(d), keep=(d,),
-                     r=[region(self.emb_lp), rw, region(net.P, L.bias_off, L.bias_off + L.cout)], w=[region(self.logits)])
-            self._op(self.loss_ops, "softmax_xent", lib.fn_softmax_xent_fwd_bwd, _ptr(self.logits), Cp, _ptr(self.labels), _ptr(self.loss),
-                     _ptr(self.dlogits), Cp, _ptr(net.Gacc, L.bias_off - net.bias_lo), batch, Cr, 1.0 / batch, self.dt,
-                     r=[region(self.logits), region(self.labels)], w=[region(self.loss), region(self.dlogits), rgb])
-            w = self._cls_desc(L)
-            w.x, w.y, w.dw = _ptr(self.emb_lp), _ptr(self.dlogits), _ptr(self.G, L.w_off)
-            self._op(self.loss_ops, "conv_wgrad:classifier", lib.fn_conv2d_wgrad, C.byref(w), keep=(w,),
-                     r=[region(self.emb_lp), region(self.dlogits)], w=[rgw])
-            g = self._cls_desc(L)
-            g.y, g.w, g.dx, g.out_f32 = _ptr(self.dlogits), _ptr(net.Wt_train, L.w_off), _ptr(self.demb), 1
-            self._op(self.loss_ops, "conv_dgrad:classifier", lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
-                     r=[region(self.dlogits), rwt], w=[region(self.demb)])
+            self._build_softmax_loss(emb)
             if self.regularized:
-                self._build_regularizers(Cr, rank, r_emb)
+                self._build_regularizers()
         self.plan.build_backward(self.demb)
         self.opt_ops: List[Op] = []
-        self._op(self.opt_ops, "adam_tick", lib.fn_adam_tick, _ptr(self.hyper), beta1, beta2, w=[region(self.hyper)])
-        opt_writes = [region(net.P)] + [region(s) for s in self.slots] + [region(net.W_train)]
-        if self.optimizer == "ADAM":
-            name, fn, fn_ema = "adam_keras", lib.fn_adam_keras, lib.fn_adam_keras_ema
-            opt_args = (_ptr(net.P), _ptr(self.G), _ptr(self.M), _ptr(self.V), _ptr(net.W_train), net.n_kernel, net.n_params,
-                        net.n_decay, _ptr(self.hyper), beta1, beta2, epsilon, l2, self.dt)
-        else:      # one pass of the same shape (fn_opt_keras); a one-slot rule passes no second slot
-            rule = self.rule
-            name, fn, fn_ema = rule.op, lib.fn_opt_keras, lib.fn_opt_keras_ema
-            s2 = _ptr(self.slots[1]) if len(self.slots) > 1 else None
-            opt_args = (rule.code, _ptr(net.P), _ptr(self.G), _ptr(self.slots[0]), s2, _ptr(net.W_train), net.n_kernel, net.n_params,
-                        net.n_decay, _ptr(self.hyper), rule.rho, rule.momentum, rule.epsilon, l2, self.dt)
-        if self.shadow is None:
-            self._op(self.opt_ops, name, fn, *opt_args, r=[region(self.G), region(self.hyper)], w=opt_writes)
-        else:      # the same launch with the moving-average update fused in (one pass, same launch count)
-            self._op(self.opt_ops, name + "_ema", fn_ema, *opt_args, _ptr(self.shadow), self.ema_decay,
-                     r=[region(self.G), region(self.hyper)], w=opt_writes + [region(self.shadow)])
-        self._op(self.opt_ops, "pack_transpose", lib.fn_pack_transpose, _ptr(net.W_train), _ptr(net.Wt_train), _ptr(net.table),
-                 len(net.layers), net.max_layer_elems, self.dt, r=[region(net.W_train)], w=[region(net.Wt_train)])
-        if self.centers is not None:      # the final segment: under data parallelism it reads the gathered global batch
-            self._op(self.opt_ops, "center_update", lib.fn_center_update, _ptr(self.center_rows), E + 1, self.world * batch, E,
-                     _ptr(self.centers), self.centers.shape[0], self.center_alfa, r=[region(self.center_rows)], w=[region(self.centers)])
+        self._build_optimizer()
         n_buckets = int(os.environ.get("FACENET_DP_BUCKETS", n_buckets))      # tuning aid: gradient buckets of the data-parallel step
         self.buckets = self._make_buckets(n_buckets) if self.segmented else []
         self.comm_stream = torch.cuda.Stream(device=dev) if self.exchange else None
@@ -468,31 +409,92 @@ class Trainer:
         self._eval_plans: Dict[int, Tuple[Lowering, torch.Tensor]] = {}   # evaluate(): inference plan + output per batch size
         self._average_in_place = False      # inside averaged_weights(): P holds the moving average
 
-    def _op(self, lst, name, fn, *args, keep=(), r=(), w=()):
-        lst.append(Op(name, fn, args, tuple(keep), tuple(r), tuple(w)))
+    def _build_triplet_loss(self, emb: torch.Tensor):
+        """l2_normalize -> triplet loss over rows (a0,p0,n0,a1,...) -> gradient wrt the un-normalised embedding (demb)."""
+        net, lib, batch, E = self.net, self.lib, self.N, self.net.E
+        self.embn = torch.zeros(batch, E, dtype=torch.float32, device=net.device)
+        self.dembn = torch.zeros(batch, E, dtype=torch.float32, device=net.device)
+        emit(self.loss_ops, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(emb), _ptr(self.embn), batch, E, 1e-10, r=[region(emb)], w=[region(self.embn)])
+        emit(self.loss_ops, "triplet_loss", lib.fn_triplet_loss_fwd_bwd, _ptr(self.embn), _ptr(self.dembn), _ptr(self.loss),
+             batch // 3, E, self.alpha, r=[region(self.embn)], w=[region(self.dembn), region(self.loss)])
+        emit(self.loss_ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(self.dembn), _ptr(self.demb), batch, E, 1e-10,
+             r=[region(emb), region(self.dembn)], w=[region(self.demb)])
 
-    def _build_regularizers(self, n_classes: int, rank: int, r_emb):
+    def _build_softmax_loss(self, emb: torch.Tensor):
+        """The classifier Dense(C) on the (un-normalised) embedding, softmax cross-entropy, and the classifier's own weight and
+        data gradients: its parameters are finished before the network's backward starts."""
+        net, lib, batch, E, dev = self.net, self.lib, self.N, self.net.E, self.net.device
+        L = net.layers["classifier/logits"]
+        Cp, Cr = L.cout, L.cout_real
+        self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.emb_lp = torch.zeros(batch, E, dtype=net.train_dtype, device=dev)
+        self.logits = torch.zeros(batch, Cp, dtype=torch.float32, device=dev)
+        self.dlogits = torch.zeros(batch, Cp, dtype=net.train_dtype, device=dev)
+        bias_acc = L.bias_off - net.bias_lo
+        d = self._cls_desc(L)
+        d.x, d.w, d.y, d.bias, d.out_f32 = _ptr(self.emb_lp), _ptr(net.W_train, L.w_off), _ptr(self.logits), _ptr(net.P, L.bias_off), 1
+        emit(self.loss_ops, "cast_emb", lib.fn_cast_f32_to_lp, _ptr(emb), _ptr(self.emb_lp), batch * E, self.dt, r=[region(emb)], w=[region(self.emb_lp)])
+        emit(self.loss_ops, "conv_fwd:classifier", lib.fn_conv2d_fwd, C.byref(d), keep=(d,),
+             r=[region(self.emb_lp), weight_region(net.W_train, L), bias_region(net.P, L)], w=[region(self.logits)])
+        emit(self.loss_ops, "softmax_xent", lib.fn_softmax_xent_fwd_bwd, _ptr(self.logits), Cp, _ptr(self.labels), _ptr(self.loss),
+             _ptr(self.dlogits), Cp, _ptr(net.Gacc, bias_acc), batch, Cr, 1.0 / batch, self.dt,
+             r=[region(self.logits), region(self.labels)],
+             w=[region(self.loss), region(self.dlogits), region(net.Gacc, bias_acc, bias_acc + L.cout)])
+        w = self._cls_desc(L)
+        w.x, w.y, w.dw = _ptr(self.emb_lp), _ptr(self.dlogits), _ptr(self.G, L.w_off)
+        emit(self.loss_ops, "conv_wgrad:classifier", lib.fn_conv2d_wgrad, C.byref(w), keep=(w,),
+             r=[region(self.emb_lp), region(self.dlogits)], w=[weight_region(self.G, L)])
+        g = self._cls_desc(L)
+        g.y, g.w, g.dx, g.out_f32 = _ptr(self.dlogits), _ptr(net.Wt_train, L.w_off), _ptr(self.demb), 1
+        emit(self.loss_ops, "conv_dgrad:classifier", lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
+             r=[region(self.dlogits), weight_region(net.Wt_train, L)], w=[region(self.demb)])
+
+    def _build_optimizer(self):
+        """Step count and beta powers (fn_adam_tick) -> the update rule in one pass over P, with the moving average fused in when
+        it is kept -> the transposed pack -> the centers (the final segment: under data parallelism it reads the gathered batch)."""
+        net, lib, beta1, beta2, l2 = self.net, self.lib, self.beta1, self.beta2, self.l2
+        emit(self.opt_ops, "adam_tick", lib.fn_adam_tick, _ptr(self.hyper), beta1, beta2, w=[region(self.hyper)])
+        opt_writes = [region(net.P)] + [region(s) for s in self.slots] + [region(net.W_train)]
+        rule, adam = self.rule, self.optimizer == "ADAM"
+        # fn_adam_keras and fn_opt_keras are one pass of the same shape; fn_opt_keras takes its rule first, a one-slot rule no second slot
+        fn, fn_ema = (lib.fn_adam_keras, lib.fn_adam_keras_ema) if adam else (lib.fn_opt_keras, lib.fn_opt_keras_ema)
+        consts = (beta1, beta2, self.eps) if adam else (rule.rho, rule.momentum, rule.epsilon)
+        opt_args = (() if adam else (rule.code,)) + (
+            _ptr(net.P), _ptr(self.G), _ptr(self.slots[0]), _ptr(self.slots[1]) if len(self.slots) > 1 else None, _ptr(net.W_train),
+            net.n_kernel, net.n_params, net.n_decay, _ptr(self.hyper), *consts, l2, self.dt)
+        if self.shadow is None:
+            emit(self.opt_ops, rule.op, fn, *opt_args, r=[region(self.G), region(self.hyper)], w=opt_writes)
+        else:      # the same launch with the moving-average update fused in (one pass, same launch count)
+            emit(self.opt_ops, rule.op + "_ema", fn_ema, *opt_args, _ptr(self.shadow), self.ema_decay,
+                 r=[region(self.G), region(self.hyper)], w=opt_writes + [region(self.shadow)])
+        emit(self.opt_ops, "pack_transpose", lib.fn_pack_transpose, _ptr(net.W_train), _ptr(net.Wt_train), _ptr(net.table),
+             len(net.layers), net.max_layer_elems, self.dt, r=[region(net.W_train)], w=[region(net.Wt_train)])
+        if self.centers is not None:
+            emit(self.opt_ops, "center_update", lib.fn_center_update, _ptr(self.center_rows), net.E + 1, self.world * self.N, net.E,
+                 _ptr(self.centers), self.centers.shape[0], self.center_alfa, r=[region(self.center_rows)], w=[region(self.centers)])
+
+    def _build_regularizers(self):
         """Center loss and prelogits norm: one launch after the classifier's data gradient adds their
         gradient into demb and reports the terms.  With center loss on it also writes this rank's (x, label) rows into
         center_rows [world, N, E+1]; the other ranks' slots arrive by an all-reduce (SUM) of the zeroed buffer -- an exact
         all-gather -- before the final segment's center_update."""
-        net, lib, N, E, dev = self.net, self.net.lib, self.N, self.net.E, self.net.device
+        net, lib, N, E, dev, rank = self.net, self.net.lib, self.N, self.net.E, self.net.device, self.rank
+        n_classes = net.layers["classifier/logits"].cout_real
         self.reg_terms = torch.zeros(8, dtype=torch.float32, device=dev)    # zeroed once: the launch leaves its words zeroed
-        reads, writes = [r_emb, region(self.labels), region(self.demb)], [region(self.demb), region(self.reg_terms)]
-        rows, slot = None, None
+        reads, writes = [region(self.emb), region(self.labels), region(self.demb)], [region(self.demb), region(self.reg_terms)]
+        rows = None
         if self.center_factor > 0:
             self.centers = torch.zeros(n_classes, E, dtype=torch.float32, device=dev)     # tf.constant_initializer(0), not trainable
             self.center_rows = torch.zeros(self.world, N, E + 1, dtype=torch.float32, device=dev)
-            rows, slot = self.center_rows[rank], region(self.center_rows, rank * N * (E + 1), (rank + 1) * N * (E + 1))
+            rows = self.center_rows[rank]
             reads.append(region(self.centers))
-            writes.append(slot)
+            writes.append(region(self.center_rows, rank * N * (E + 1), (rank + 1) * N * (E + 1)))
             if self.world > 1:        # the other ranks' slots must be zero when the all-reduce sums them
-                self.pre_ops.append(Op("zero_center_rows", torch_op(lambda: self.center_rows.zero_()), (),
-                                       writes=(region(self.center_rows),)))
-        self._op(self.loss_ops, "center_loss", lib.fn_center_loss_fwd_bwd, _ptr(self.emb), _ptr(self.labels),
-                 None if self.centers is None else _ptr(self.centers), _ptr(self.demb), _ptr(self.reg_terms),
-                 None if rows is None else _ptr(rows), E + 1, N, E, n_classes, self.center_factor, self.prelogits_norm_factor,
-                 self.prelogits_norm_p, r=reads, w=writes)
+                self.pre_ops.append(Op("zero_center_rows", torch_op(lambda: self.center_rows.zero_()), (), writes=(region(self.center_rows),)))
+        emit(self.loss_ops, "center_loss", lib.fn_center_loss_fwd_bwd, _ptr(self.emb), _ptr(self.labels),
+             None if self.centers is None else _ptr(self.centers), _ptr(self.demb), _ptr(self.reg_terms),
+             None if rows is None else _ptr(rows), E + 1, N, E, n_classes, self.center_factor, self.prelogits_norm_factor,
+             self.prelogits_norm_p, r=reads, w=writes)
 
     def _cls_desc(self, L):
         d = _lib.ConvDesc()
@@ -959,16 +961,14 @@ class TripletMiner:
         net.refresh_folded(net.stream())          # the inference pack must exist before launches are timed
         self.tiles = autotune_convs(self.plan.fwd, net)
         o.extend(self.plan.fwd)
-        o.append(Op("l2norm_fwd", lib.fn_l2norm_fwd, (_ptr(self.emb), _ptr(self.embn), n, E, 1e-10),
-                    reads=(region(self.plan.embedding.buf.act),), writes=(region(self.embn),)))
-        o.append(Op("pairwise_sqdist", lib.fn_pairwise_sqdist, (_ptr(self.embn), _ptr(self.embn), _ptr(self.dist), None, n, n, E, 2),
-                    reads=(region(self.embn),), writes=(region(self.dist),)))
-        o.append(Op("select_triplets", lib.fn_select_triplets, (_ptr(self.dist), _ptr(self.labels), n, self.alpha, self.T, self.seed,
-                                                                 1 if self.semi_hard else 0, _ptr(self.triplets), _ptr(self.info)),
-                    reads=(region(self.dist), region(self.labels)), writes=(region(self.triplets), region(self.info))))
-        o.append(Op("gather_images", lib.fn_gather_images, (_ptr(self.plan.images), _ptr(self.triplets), _ptr(train_images), 3 * self.T,
-                                                             bytes_per),
-                    reads=(region(self.plan.images), region(self.triplets)), writes=(region(train_images),)))
+        emit(o, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(self.emb), _ptr(self.embn), n, E, 1e-10, r=[region(self.emb)], w=[region(self.embn)])
+        emit(o, "pairwise_sqdist", lib.fn_pairwise_sqdist, _ptr(self.embn), _ptr(self.embn), _ptr(self.dist), None, n, n, E, 2,
+             r=[region(self.embn)], w=[region(self.dist)])
+        emit(o, "select_triplets", lib.fn_select_triplets, _ptr(self.dist), _ptr(self.labels), n, self.alpha, self.T, self.seed,
+             1 if self.semi_hard else 0, _ptr(self.triplets), _ptr(self.info),
+             r=[region(self.dist), region(self.labels)], w=[region(self.triplets), region(self.info)])
+        emit(o, "gather_images", lib.fn_gather_images, _ptr(self.plan.images), _ptr(self.triplets), _ptr(train_images), 3 * self.T, bytes_per,
+             r=[region(self.plan.images), region(self.triplets)], w=[region(train_images)])
         self.ops = group_convs(o, net) if self.group else o
         self.sched = Schedule(self.ops, self.n_streams)
 

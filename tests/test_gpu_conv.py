@@ -54,16 +54,16 @@ def test_halo_cases_dispatch_to_the_halo_kernel(lib):
         t = torch.zeros(16, device="cuda")
         d.x = d.w = d.y = d.dx = ptr(t)
         prod = Cin <= 64, Cout <= 64       # the production heuristic: at most 64 SOURCE channels (forward: Cin, data gradient: Cout)
-        assert (lib.fn_conv2d_variant(C.byref(d), 0) >= 9000000) == prod[0] and (lib.fn_conv2d_variant(C.byref(d), 1) >= 9000000) == prod[1]
+        assert (_lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 0))) == prod[0] and (_lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 1))) == prod[1]
         d.tile_fwd = d.tile_dgrad = HALO
-        assert lib.fn_conv2d_variant(C.byref(d), 0) >= 9000000 and lib.fn_conv2d_variant(C.byref(d), 1) >= 9000000
+        assert _lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 0)) and _lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 1))
         d.tile_fwd = d.tile_dgrad = 64064
-        assert lib.fn_conv2d_variant(C.byref(d), 0) % 1000000 == 64064 and lib.fn_conv2d_variant(C.byref(d), 1) % 1000000 == 64064   # (+ 2e6: in-launch split-K)
+        assert _lib.variant_tile(lib.fn_conv2d_variant(C.byref(d), 0)) == 64064 and _lib.variant_tile(lib.fn_conv2d_variant(C.byref(d), 1)) == 64064   # (+ 2e6: in-launch split-K)
     d = conv_desc(2, 17, 17, 32, 32, 3, 3, 1, 1, 1, _lib.FN_BF16)          # small map: implicit GEMM
     d.x = d.w = d.y = d.dx = ptr(torch.zeros(16, device="cuda"))
-    assert lib.fn_conv2d_variant(C.byref(d), 0) < 9000000
+    assert not _lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 0))
     d.tile_fwd = HALO                                                       # an explicit request is honoured on any map size ...
-    assert lib.fn_conv2d_variant(C.byref(d), 0) >= 9000000
+    assert _lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 0))
     d = conv_desc(2, 17, 17, 64, 64, 1, 1, 1, 0, 0, _lib.FN_BF16)           # ... but not for a layer the kernel cannot run
     d.x = d.w = d.y = d.dx = ptr(torch.zeros(16, device="cuda"))
     d.tile_fwd = HALO
@@ -204,7 +204,7 @@ def test_conv_explicit_tiles(lib, case, tile):
     w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=72)
     d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt)
     d.tile_fwd = d.tile_dgrad = tile
-    assert lib.fn_conv2d_variant(C.byref(conv_probe(d)), 0) % 1000000 == tile
+    assert _lib.variant_tile(lib.fn_conv2d_variant(C.byref(conv_probe(d)), 0)) == tile
     y = torch.zeros(N, d.OH, d.OW, Cout, dtype=lp_dtype(dt), device="cuda")
     reps = 4
     stats_r = torch.zeros(reps, 2 * Cout, dtype=torch.int64, device="cuda")
@@ -304,7 +304,7 @@ def test_conv_wgrad_tap_sharing_kernel(lib, case, dt):
     for (hh, cin, k) in ((3, 192, 3), (19, 8, 3), (17, 64, 1)):
         e = conv_desc(2, hh, hh, cin, 64, k, k, 1, k // 2, k // 2, dt)
         e.x = e.y = e.dw = ptr(dw)
-        assert lib.fn_conv2d_variant(C.byref(e), 2) < 5000000
+        assert not _lib.variant_is_taps(lib.fn_conv2d_variant(C.byref(e), 2))
 
 
 def test_conv_rejects_bad_geometry(lib):
@@ -337,7 +337,7 @@ def test_conv_wgrad_grouped_matches_single_launches(lib):
     groups = {}
     for d, k in zip(descs, keep):
         groups.setdefault(lib.fn_conv2d_variant(C.byref(d), 2), []).append((d, k))
-    assert len(groups) >= 1 and [len(m) for v, m in groups.items() if v >= 5000000] == [8]
+    assert len(groups) >= 1 and [len(m) for v, m in groups.items() if _lib.variant_is_taps(v)] == [8]
     nbytes = lib.fn_conv2d_wgrad_arg_bytes()
     for variant, members in groups.items():
         n = len(members)
@@ -400,7 +400,7 @@ def test_dgrad_fused_bn_backward_reduction(lib, dt, H):
     d.y, d.w, d.dx = ptr(dy), ptr(wt), ptr(dx)
     d.bn_y, d.ld_bn_y, d.bn_scale, d.bn_shift, d.bn_beta = ptr(yraw), Cin, ptr(sc), ptr(sh), ptr(beta)
     d.bn_acc, d.bn_sq_off, d.bn_replicas, d.bn_rep_stride, d.bn_relu = ptr(acc), Cin, reps, 2 * Cin, 1
-    assert (lib.fn_conv2d_variant(C.byref(d), 1) >= 9000000) == (H == 37)
+    assert (_lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(d), 1))) == (H == 37)
     _lib.check(lib.fn_conv2d_dgrad(C.byref(d), stream()))
     # reference: standalone reduce on the (rounded) dx
     acc_ref = torch.zeros(2 * Cin, dtype=torch.int64, device="cuda")
@@ -1001,7 +1001,7 @@ def test_dgrad_fused_residual_backward_single_source_layers(lib, layer, dt):
     for acc in (0, 1):
         N, H, W, Cin = geo[:4]
         L = _dgrad_layer(lib, dt, geo, 500, _Buf((N, H, W, Cin + 16), dt), c0=8, tile=tile, rb=dict(prev=True, mask=True, acc=acc, scale=0.2))
-        assert (lib.fn_conv2d_variant(C.byref(L.d), 1) >= 9000000) == (layer == "halo")
+        assert (_lib.variant_is_halo(lib.fn_conv2d_variant(C.byref(L.d), 1))) == (layer == "halo")
         _run_rb(lib, L, dt, f"{layer} acc {acc}")
         L = _dgrad_layer(lib, dt, geo, 500, _Buf((N, H, W, Cin), dt), tile=tile, rb=dict(prev=True, mask=True, acc=acc, scale=0.2))
         _run_rb(lib, L, dt, f"{layer} acc {acc}, contiguous")
