@@ -19,7 +19,7 @@ FN_BF16, FN_F16 = 0, 1
 FN_OPT_ADAGRAD, FN_OPT_ADADELTA, FN_OPT_RMSPROP, FN_OPT_MOM = 1, 2, 3, 4     # fn_opt_keras rule codes
 
 
-# fn_conv2d_variant codes (include/facenet_hip.h; csrc/conv_igemm.hip variant_code, csrc/wgrad_taps.h), decoded here only
+# fn_conv2d_variant codes (include/facenet_hip.h; csrc/conv_args.h variant_encode, csrc/wgrad_taps.h), decoded here only
 VARIANT_FLAG = 1000000     # fwd / dgrad: + KS * 1000000 (in-launch split-K); grouped wgrad: + 1000000 = members normalise on load
 VARIANT_TAPS = 5000000     # wgrad: 5000000 + BMW * 1000 + taps * 10 + (stride 2): the tap-sharing kernel
 VARIANT_HALO = 9000000     # fwd / dgrad: 9000000 + BN: the halo-tile kernel (never grouped, never re-tiled)

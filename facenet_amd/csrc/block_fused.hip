@@ -738,7 +738,7 @@ extern "C" int fn_block17_infer_warm(const void* x, void* y, int N, const void* 
                   scale, relu, N, (const unsigned char*)warm, (long)warm_bytes};
     const int grid = N + (warm ? WARM_WGS : 0);
     constexpr size_t smem = 8 * 64 * 64 + 2 * 4 * 112 * 64 + 3 * 16 * 1024;      // staging: 2 x 20 KB (register ring) or 3 x 16 KB (LDS-DMA)
-    static const int use_dma = getenv("FN_B17_DMA") ? atoi(getenv("FN_B17_DMA")) : 1;   // measured: stages 2+3 12.4 -> 9.6 us per block (tools/dev_block17.py)
+    static const int use_dma = env_int("FN_B17_DMA", 1);   // measured: stages 2+3 12.4 -> 9.6 us per block (tools/dev_block17.py)
     static LdsOptIn ok[4];
     const void* kerns[4] = {reinterpret_cast<const void*>(block17_infer_kernel<__bf16, false>), reinterpret_cast<const void*>(block17_infer_kernel<_Float16, false>),
                             reinterpret_cast<const void*>(block17_infer_kernel<__bf16, true>), reinterpret_cast<const void*>(block17_infer_kernel<_Float16, true>)};

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cstdlib>
 
 namespace fn {
 
@@ -175,6 +176,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// integer tuning aid / switch from the environment; callers keep it in a function-local `static const int`: read once per process
+static inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 
 // Kernels that ask for more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised first.  The
 // attribute is PER DEVICE: one flag per (launch site, device), set once, and a failing call is an error here rather than an

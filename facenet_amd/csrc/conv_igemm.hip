@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution for gfx950 (MI355X): forward, data-gradient and weight-gradient.
+// Implicit-GEMM convolution for gfx950 (MI355X): forward and data gradient (the weight gradient is conv_wgrad.hip).
 //
 // Replaces tf.keras.layers.Conv2D / Dense and the ops Keras wraps around them in
 // facenet/models/inception_resnet_v1.py (Conv2D :90-138,:160-193,:215-248,:269-299,:316-367,
@@ -14,18 +14,15 @@
 //     fragment read is bank-conflict free;
 //   * dgrad is the SAME kernel with a transposed-conv gather (so/sk/div parameters) reading the
 //     [Cin][tap][Cout] weight pack;
-//   * wgrad reduces over pixels (K = N*OH*OW): both operands are k-strided in memory, so fragments
-//     come from LDS through ds_read_b64_tr_b16 (hardware transpose read); split-K over pixels with
-//     fp32 global atomics into dW;
 //   * epilogue through LDS (fp32 C tile) so global stores are full 16-B coalesced rows; fused there:
 //     bias, residual scale-add, ReLU, accumulate, BatchNorm batch statistics (sum / sum of squares),
 //     and channel-slice output (ld_out) which makes tf.concat free.
-#include "common.h"
-#include "../../include/facenet_hip.h"
-#include "wgrad_taps.h"
+//
+// Which kernel instantiation a launch runs is decided in ONE place, resolve_conv(): the single launches, the group builder and
+// fn_conv2d_variant all ask it.
+#include "conv_args.h"
 #include <cstdio>
 #include <type_traits>
-#include <cstdlib>
 
 #ifndef FN_IG_DBG
 #define FN_IG_DBG 0     // developer builds only (-DFN_IG_DBG=n, tools/dev_stemtiles.py / dev_phases.py): ablations 1 no loads, 2 no multiply, 4 no LDS stores,
@@ -62,63 +59,6 @@ extern "C" int fn_debug_phases(unsigned long long* out, int reset) {
 
 namespace fn {
 
-struct ConvArgs {
-    const unsigned short* src;  // gathered activation operand
-    const unsigned short* wp;   // packed weights [NOUT][KTOT]
-    void* out;
-    const float* bias;
-    acc_t* stats;               // BatchNorm batch statistics (fixed point, ACC_STAT): stats[rep*stride + c] += sum y, [.. + sq_off + c] += sum y^2
-    const unsigned short* resid;
-    int M, PH, PW;   // output pixels = N*PH*PW
-    int SH, SW;      // source spatial dims
-    int CS;          // source channels per tap
-    int NOUT, KTOT, KH, KW;
-    int so, sk, offy, offx, dshift;  // t = p*so + k*sk + off ; src = t >> dshift, valid iff t>=0, (t & ((1<<dshift)-1))==0, src < S
-    int ld_src, ld_out, ld_res;
-    int relu, accumulate, out_f32;
-    float scale;
-    int tiles_m, tiles_n;
-    int stats_sq_off, stats_replicas, stats_rep_stride;
-    int plain;  // 1x1 / stride 1 / no padding: source pixel == output pixel, k == channel
-    // dgrad epilogue: reduction of the BatchNorm backward of the layer whose output gradient this launch produces
-    const unsigned short* bn_y;   // raw forward output of that layer (same pixels / channel slice as `out`)
-    const float* bn_scale;
-    const float* bn_shift;
-    const float* bn_beta;
-    acc_t* bn_acc;                // fixed point (ACC_GRAD): acc[rep*stride + c] += sum dyh ; acc[rep*stride + sq_off + c] += sum dyh*xhat
-    int ld_bn_y, bn_sq_off, bn_replicas, bn_rep_stride, bn_relu;
-    // stride-2 dgrad: output pixels are split into 4 parity classes ((iy+pad)&1, (ix+pad)&1); a class only sees the taps
-    // of matching parity, so each class is its own GEMM (M = its pixels, K = its taps) inside one launch.
-    int s2;                 // 1 = class mode
-    int cp1, cp2, cp3;      // first tile of classes 1..3 (class 0 starts at 0)
-    int total_tiles;
-    int src_bytes, w_bytes;   // extents for the buffer resource descriptors (< 2^30)
-    int tile;                 // 0 = heuristic, BM*1000+BN = caller's choice (fn_conv_desc.tile_fwd / tile_dgrad)
-    int nocheck;              // forward, no padding: taps never leave the source, the per-chunk bounds test is skipped
-    // 1x1 data gradient of SIBLING layers that read the same input: dX = sum_s dY_s * Wt_s as ONE GEMM whose K runs through
-    // the sources (k tiles [0,t1) source 1, [t1,t2) source 2, [t2,nt_total) source 3); nt_total == 0: single source
-    const unsigned short* src2; const unsigned short* wp2;
-    const unsigned short* src3; const unsigned short* wp3;
-    int K2, ld2, K3, ld3, t1, t2, nt_total, src2_bytes, w2_bytes, src3_bytes, w3_bytes;
-    // normalise-on-load (forward only): src is the raw output of a BN(center)+ReLU layer, see fn_conv_desc.nrm_*
-    const acc_t* nrm_stats;
-    const float* nrm_beta;
-    int nrm_sq_off, nrm_replicas, nrm_rep_stride, nrm_count;
-    float nrm_eps;
-    unsigned short* nrm_z;    // optional: the normalised operand is also written here (geometry of src), see fn_conv_desc.nrm_z
-    // dgrad epilogue: fused residual backward (fn_conv_desc.rb_*).  `resid` (scale 1) carries rb_prev, `out` is rb_dtrunk.
-    int halo_ty, halo_tx;         // halo kernel: 8x16-pixel output tiles per image (rows, columns)
-    const unsigned short* mask;   // rows of the block's forward output: values <= 0 zero the gradient
-    unsigned short* out2;         // scale2 * (masked gradient), geometry of out
-    acc_t* colsum;                // fixed point (ACC_GRAD): += column sums of what goes to out2
-    float scale2;
-    const float* prelu;           // forward: per-output-channel PReLU slope applied to conv + bias
-};
-
-// q = m / d, r = m % d through the hardware reciprocal (0 <= m < 2^24, d > 0): integer division is a ~40-instruction
-// sequence on this ISA and the prologue of every workgroup needs several
-__device__ __forceinline__ void rcp_divmod(int m, int d, int& q, int& r) { fast_divmod(m, d, __builtin_amdgcn_rcpf((float)d), q, r); }
-
 // class mode: taps ky in {qy, qy+2, ..}, kx in {qx, qx+2, ..}
 __device__ __forceinline__ int ktab_entry_s2(int kgroup, int CS, int KH, int KW, int qy, int qx) {
     const int nky = (KH - qy + 1) >> 1, nkx = (KW - qx + 1) >> 1;
@@ -128,15 +68,6 @@ __device__ __forceinline__ int ktab_entry_s2(int kgroup, int CS, int KH, int KW,
     rcp_divmod(k, CS, tap, c);
     rcp_divmod(tap, nkx, ty, tx);
     return ((qy + 2 * ty) << 24) | ((qx + 2 * tx) << 16) | c;
-}
-
-__device__ __forceinline__ int ktab_entry(int kgroup, int KTOT, int CS, int KW) {
-    const int k = kgroup * 8;
-    if (k >= KTOT) return -1;
-    int tap, c, ky, kx;
-    rcp_divmod(k, CS, tap, c);
-    rcp_divmod(tap, KW, ky, kx);
-    return (ky << 24) | (kx << 16) | c;
 }
 
 // Epilogue of every forward / data-gradient convolution kernel: the fp32 accumulators go through LDS (C tile) so that global
@@ -1120,18 +1051,20 @@ static size_t halo_smem_bytes(int BN, int KH, int KW) {
 // (tools/dev_convbench.py halo, batch 90 / 180): Conv2d_2a 53 -> 35 / 89 -> 55 us, Conv2d_2b 61 -> 54 / 108 -> 93 us; Conv2d_4a
 // (80 -> 192 channels on 35 x 35: 36 % of the 8x16 tile slots fall outside the map and the weights are re-staged per slice) is
 // slower here (79 vs 65 us) and stays on the implicit-GEMM kernel.  FN_CONV_HALO=0 switches the kernel off (A/B measurements).
-enum { TILE_HALO = 9000000 };   // fn_conv_desc.tile_fwd / tile_dgrad: an explicit request for the halo-tile kernel
+enum { TILE_HALO = VARIANT_HALO };   // fn_conv_desc.tile_fwd / tile_dgrad: an explicit request for the halo-tile kernel
 static bool halo_capable(const ConvArgs& a) {   // what the kernel can compute at all
     return !a.s2 && !a.plain && a.so == 1 && a.dshift == 0 && a.KH == 3 && a.KW == 3 && a.CS % 8 == 0 && !a.nrm_stats && a.nt_total == 0;
 }
 static bool halo_eligible(const ConvArgs& a) {
     if (a.tile == TILE_HALO) return halo_capable(a);   // kernel tests cover it beyond the sizes where it wins
-    static const int enabled = getenv("FN_CONV_HALO") ? atoi(getenv("FN_CONV_HALO")) : 1;
-    static const int maxc = getenv("FN_CONV_HALO_MAXC") ? atoi(getenv("FN_CONV_HALO_MAXC")) : 64;
+    static const int enabled = env_int("FN_CONV_HALO", 1);
+    static const int maxc = env_int("FN_CONV_HALO_MAXC", 64);
     return enabled && halo_capable(a) && a.CS <= maxc && a.PH >= 30 && a.PW >= 30 &&
            a.tile == 0;   // an explicit tile (fn_conv_desc.tile_*) asks for the implicit-GEMM kernel
 }
-static int halo_bn(const ConvArgs& a) { return a.NOUT <= 32 ? 32 : (a.NOUT <= 48 || (a.NOUT > 64 && a.NOUT <= 96) ? 32 : 64); }
+static int halo_bn(const ConvArgs& a) {   // column tile of the halo kernel
+    return a.NOUT <= 32 ? 32 : (a.NOUT <= 48 || (a.NOUT > 64 && a.NOUT <= 96) ? 32 : 64);
+}
 
 template <typename T, int BN, int WM, int WN, int KH, int KW> static int launch_halo_p(ConvArgs a, hipStream_t st) {
     a.halo_ty = cdiv(a.PH, 8);
@@ -1149,8 +1082,8 @@ template <typename T, int BN, int WM, int WN, int KH, int KW> static int launch_
     return check_launch("conv_halo");
 }
 
-template <typename T> static int launch_halo(const ConvArgs& a, hipStream_t st) {
-    return halo_bn(a) == 32 ? launch_halo_p<T, 32, 4, 1, 3, 3>(a, st) : launch_halo_p<T, 64, 2, 2, 3, 3>(a, st);
+template <typename T> static int launch_halo(const ConvArgs& a, int bn, hipStream_t st) {
+    return bn == 32 ? launch_halo_p<T, 32, 4, 1, 3, 3>(a, st) : launch_halo_p<T, 64, 2, 2, 3, 3>(a, st);
 }
 
 // tiles of a launch; in class mode (stride-2 dgrad) every parity class has its own row tiles
@@ -1209,14 +1142,19 @@ static int launch_conv_p(const ConvArgs& a0, hipStream_t st) {
     return check_launch("conv_igemm");
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int DEPTH, int KS>
-static int launch_conv(const ConvArgs& a, hipStream_t st) {
+// (plain, mode) -> the PLAIN / MODE template arguments of the kernel, for the single and the grouped launcher alike:
+// launch(std::bool_constant<PLAIN>, std::integral_constant<int, MODE>).  MODE 1 (normalise on load) and MODE 2 (sibling sources: 1x1,
+// single launches only) are instantiated for KS == 1 alone; resolve_conv() asks for no other combination.
+template <int KS, bool SIBLINGS, typename F> static int with_operand(int plain, int mode, F&& launch) {
+    using std::bool_constant;
+    using std::integral_constant;
     if constexpr (KS == 1) {
-        if (a.nt_total > 0) return launch_conv_p<T, BM, BN, WM, WN, DEPTH, 1, true, 2>(a, st);
-        if (a.nrm_stats)
-            return a.plain ? launch_conv_p<T, BM, BN, WM, WN, DEPTH, 1, true, 1>(a, st) : launch_conv_p<T, BM, BN, WM, WN, DEPTH, 1, false, 1>(a, st);
+        if constexpr (SIBLINGS) {
+            if (mode == 2) return launch(bool_constant<true>{}, integral_constant<int, 2>{});
+        }
+        if (mode == 1) return plain ? launch(bool_constant<true>{}, integral_constant<int, 1>{}) : launch(bool_constant<false>{}, integral_constant<int, 1>{});
     }
-    return a.plain ? launch_conv_p<T, BM, BN, WM, WN, DEPTH, KS, true, 0>(a, st) : launch_conv_p<T, BM, BN, WM, WN, DEPTH, KS, false, 0>(a, st);
+    return plain ? launch(bool_constant<true>{}, integral_constant<int, 0>{}) : launch(bool_constant<false>{}, integral_constant<int, 0>{});
 }
 
 // Tile choice.  BN: smallest padded width, ties -> larger tile.  BM: the largest of {128, 64, 32} that still gives
@@ -1228,7 +1166,7 @@ static void choose_conv_tile_auto(int M, int NOUT, int& bm, int& bn) {
         const long w = (long)cdiv(NOUT, c) * c;
         if (w < best) { best = w; bn = c; }
     }
-    static const int minb = getenv("FN_CONV_MINBLOCKS") ? atoi(getenv("FN_CONV_MINBLOCKS")) : 384;   // tuning aid
+    static const int minb = env_int("FN_CONV_MINBLOCKS", 384);   // tuning aid
     bm = 32;
     for (int c : {128, 64}) {
         if ((long)cdiv(M, c) * cdiv(NOUT, bn) >= minb) { bm = c; break; }
@@ -1238,7 +1176,7 @@ static void choose_conv_tile_auto(int M, int NOUT, int& bm, int& bn) {
 }
 
 static void choose_conv_tile(int M, int NOUT, int forced, int& bm, int& bn) {
-    if (forced > 0) { bm = forced / 1000; bn = forced % 1000; return; }   // validated by check_tile
+    if (forced > 0) { bm = forced / 1000; bn = forced % 1000; return; }   // validated by valid_tile
     choose_conv_tile_auto(M, NOUT, bm, bn);
 }
 
@@ -1250,13 +1188,13 @@ static bool valid_tile(int t) {
 
 // In-launch split-K factor for the 32-row tiles: long k chains on few workgroups (see conv_igemm_body).
 static int choose_conv_ks(int M, int NOUT, int KTOT, int bm, int bn) {
-    static const int force = getenv("FN_CONV_KS") ? atoi(getenv("FN_CONV_KS")) : 0;   // tuning aid
+    static const int force = env_int("FN_CONV_KS", 0);   // tuning aid
     if (bm == 64) {   // 64-row tiles on grids of at most one workgroup per CU (block17 1x7 / 7x1, block35 3x3 at batch 90: 180 workgroups, 9-14 k
                       // tiles): a second wave per SIMD halves the k chain -- 13.6 -> 10.2 us per launch, step 7.06 -> 7.01 ms; larger grids
                       // (FN_CONV_KS64=400 / 640) and 128-wide tiles measured no gain
-        static const int ks64 = getenv("FN_CONV_KS64") ? atoi(getenv("FN_CONV_KS64")) : 256;   // largest grid that splits (0: never)
+        static const int ks64 = env_int("FN_CONV_KS64", 256);   // largest grid that splits (0: never)
         // four groups (1024 threads): k chains of >= 12 tiles on at most one workgroup per CU
-        static const int ks64_4 = getenv("FN_CONV_KS64_4") ? atoi(getenv("FN_CONV_KS64_4")) : 0;   // largest grid that splits four ways (0: never)
+        static const int ks64_4 = env_int("FN_CONV_KS64_4", 0);   // largest grid that splits four ways (0: never)
         const long grid = (long)cdiv(M, 64) * cdiv(NOUT, bn);
         if (force != 1 && force != 2 && bn <= 64 && cdiv(KTOT, 64) >= 12 && grid <= ks64_4) return 4;
         return (force != 1 && bn <= 64 && cdiv(KTOT, 64) >= 8 && grid <= ks64) ? 2 : 1;
@@ -1266,8 +1204,8 @@ static int choose_conv_ks(int M, int NOUT, int KTOT, int bm, int bn) {
     const int ntk = cdiv(KTOT, 64);
     // measured (tools/dev_ksweep.py): the chain costs ~0.16 us per k tile only while a CU holds one workgroup; with 3+
     // workgroups per CU the loop is issue-bound and splitting K just adds the reduction
-    static const int lim2 = getenv("FN_CONV_KS32_2") ? atoi(getenv("FN_CONV_KS32_2")) : 128;   // tuning aids: largest grids that split
-    static const int lim4 = getenv("FN_CONV_KS32_4") ? atoi(getenv("FN_CONV_KS32_4")) : 64;
+    static const int lim2 = env_int("FN_CONV_KS32_2", 128);   // tuning aids: largest grids that split
+    static const int lim4 = env_int("FN_CONV_KS32_4", 64);
     int ks = 1;
     if (ntk >= 8 && blocks <= lim2) ks = 2;
     if (ntk >= 16 && blocks <= lim4 && bn <= 64) ks = 4;
@@ -1286,52 +1224,76 @@ static int choose_conv_ks(int M, int NOUT, int KTOT, int bm, int bn) {
     X(32, 128, 1, 4, 4, 2) X(32, 64, 1, 4, 4, 2) X(32, 64, 1, 4, 4, 4) X(32, 32, 2, 2, 4, 2) X(32, 32, 2, 2, 4, 4)                       \
     X(64, 64, 2, 2, 2, 2) X(64, 32, 2, 2, 2, 2) X(64, 64, 2, 2, 2, 4) X(64, 32, 2, 2, 2, 4)
 
-// variant code: BM*1000 + BN (+ KS*1000000 when KS > 1)
-static int variant_code(int bm, int bn, int ks) { return bm * 1000 + bn + (ks > 1 ? ks * 1000000 : 0); }
+// Which kernel a validated ConvArgs runs on.  halo: conv_halo_kernel with column tile bn; otherwise conv_igemm_kernel<bm, bn, .., ks, plain,
+// mode> (mode 0: one plain source, 1: normalise on load, 2: sibling sources).
+struct ConvKernel {
+    bool halo;
+    int bm, bn, ks, plain, mode;
+};
 
-template <typename T> static int dispatch_conv(const ConvArgs& a, hipStream_t st) {
-    if (halo_eligible(a)) return launch_halo<T>(a, st);
+// The tile of an implicit-GEMM launch and the in-launch split-K factor that goes with it: the normalise-on-load and sibling-source
+// kernels exist with ks = 1 only.
+static void set_tile(ConvKernel& k, const ConvArgs& a, int bm, int bn) {
+    k.bm = bm;
+    k.bn = bn;
+    k.ks = k.mode != 0 ? 1 : choose_conv_ks(a.M, a.NOUT, a.KTOT, bm, bn);
+}
+
+// THE dispatch decision of forward / data-gradient launches: single launches (dispatch_conv), group members (fn_conv2d_group_build)
+// and fn_conv2d_variant all resolve through here, so what the variant names is what runs.
+static int resolve_conv(const ConvArgs& a, ConvKernel& k) {
+    k = ConvKernel{};
+    k.plain = a.plain;
+    k.mode = a.nt_total > 0 ? 2 : (a.nrm_stats ? 1 : 0);
+    if (halo_eligible(a)) {
+        k.halo = true;
+        k.bn = halo_bn(a);
+        return FN_OK;
+    }
     if (a.tile == TILE_HALO) {
         set_error("conv: the halo-tile kernel was requested (tile %d) for a layer it cannot run (needs 3x3, stride 1, channels %% 8 == 0)", a.tile);
         return FN_EUNSUPPORTED;
     }
     int bm, bn;
     choose_conv_tile(a.M, a.NOUT, a.tile, bm, bn);
-    if (const char* f = getenv("FN_CONV_TILE")) {   // tuning aid: "BMxBN"
+    set_tile(k, a, bm, bn);
+    return FN_OK;
+}
+
+template <typename T> static int dispatch_conv(const ConvArgs& a, hipStream_t st) {
+    ConvKernel k;
+    if (int rc = resolve_conv(a, k)) return rc;
+    if (k.halo) return launch_halo<T>(a, k.bn, st);
+    if (const char* f = getenv("FN_CONV_TILE")) {   // tuning aid "BMxBN": re-tiles single implicit-GEMM launches only (tools/dev_convbench.py)
         int fm = 0, fnn = 0;
-        if (sscanf(f, "%dx%d", &fm, &fnn) == 2) { bm = fm; bn = fnn; }
+        if (sscanf(f, "%dx%d", &fm, &fnn) == 2) set_tile(k, a, fm, fnn);
     }
-    const int ks = (a.nrm_stats || a.nt_total > 0) ? 1 : choose_conv_ks(a.M, a.NOUT, a.KTOT, bm, bn);
-#define FN_X(BM_, BN_, WM_, WN_, D_, KS_) \
-    if (bm == BM_ && bn == BN_ && ks == KS_) return launch_conv<T, BM_, BN_, WM_, WN_, D_, KS_>(a, st);
+#define FN_X(BM_, BN_, WM_, WN_, D_, KS_)                                                                                                  \
+    if (k.bm == BM_ && k.bn == BN_ && k.ks == KS_)                                                                                         \
+        return with_operand<KS_, true>(k.plain, k.mode, [&](auto plain, auto mode) {                                                       \
+            return launch_conv_p<T, BM_, BN_, WM_, WN_, D_, KS_, decltype(plain)::value, decltype(mode)::value>(a, st);                  \
+        });
     FN_CONV_VARIANTS(FN_X)
 #undef FN_X
-    set_error("conv: no tile variant %dx%d ks=%d", bm, bn, ks);
+    set_error("conv: no tile variant %dx%d ks=%d", k.bm, k.bn, k.ks);
     return FN_EUNSUPPORTED;
 }
 
 template <typename T>
-static int dispatch_conv_grouped(const ConvArgs* dev_args, const int32_t* dev_prefix, int n, int total, int bm, int bn, int ks, int plain,
-                                 size_t smem, hipStream_t st) {
-    const bool norm = (plain & 2) != 0;   // bit 1 of `plain`: every member normalises on load
-    plain &= 1;
-#define FN_X(BM_, BN_, WM_, WN_, D_, KS_)                                                                                                       \
-    if (bm == BM_ && bn == BN_ && ks == KS_) {                                                                                                  \
-        if constexpr (KS_ == 1) {                                                                                                               \
-            if (norm)                                                                                                                           \
-                return plain ? launch_conv_grouped_p<T, BM_, BN_, WM_, WN_, D_, 1, true, 1>(dev_args, dev_prefix, n, total, smem, st)         \
-                             : launch_conv_grouped_p<T, BM_, BN_, WM_, WN_, D_, 1, false, 1>(dev_args, dev_prefix, n, total, smem, st);       \
-        }                                                                                                                                       \
-        return plain ? launch_conv_grouped_p<T, BM_, BN_, WM_, WN_, D_, KS_, true, 0>(dev_args, dev_prefix, n, total, smem, st)              \
-                     : launch_conv_grouped_p<T, BM_, BN_, WM_, WN_, D_, KS_, false, 0>(dev_args, dev_prefix, n, total, smem, st);            \
-    }
+static int dispatch_conv_grouped(const ConvArgs* dev_args, const int32_t* dev_prefix, int n, int total, const ConvKernel& k, size_t smem, hipStream_t st) {
+#define FN_X(BM_, BN_, WM_, WN_, D_, KS_)                                                                                                  \
+    if (k.bm == BM_ && k.bn == BN_ && k.ks == KS_)                                                                                         \
+        return with_operand<KS_, false>(k.plain, k.mode, [&](auto plain, auto mode) {                                                      \
+            return launch_conv_grouped_p<T, BM_, BN_, WM_, WN_, D_, KS_, decltype(plain)::value, decltype(mode)::value>(dev_args, dev_prefix, n, \
+                                                                                                                          total, smem, st);  \
+        });
     FN_CONV_VARIANTS(FN_X)
 #undef FN_X
-    set_error("conv_grouped: no tile variant %dx%d ks=%d", bm, bn, ks);
+    set_error("conv_grouped: no tile variant %dx%d ks=%d", k.bm, k.bn, k.ks);
     return FN_EUNSUPPORTED;
 }
 
-static int check_desc(const fn_conv_desc* d) {
+int check_desc(const fn_conv_desc* d) {
     FN_REQUIRE(d != nullptr, "conv: null descriptor");
     FN_REQUIRE(d->dtype == FN_BF16 || d->dtype == FN_F16, "conv: dtype %d unsupported", d->dtype);
     FN_REQUIRE(d->Cin % 8 == 0, "conv: Cin=%d must be a multiple of 8 (pad the input channels)", d->Cin);
@@ -1345,363 +1307,6 @@ static int check_desc(const fn_conv_desc* d) {
     FN_REQUIRE((long)d->N * d->H * d->W < (1L << 31) / 8 && (long)d->N * d->OH * d->OW < (1L << 24) * 8L,
                "conv: tensor too large for 32-bit pixel indexing");
     return FN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// wgrad: dW[co][kcol] += sum_m dY[m][co] * X[m @ tap(kcol)][ci(kcol)]
-// ------------------------------------------------------------------------------------------------
-struct WgradArgs {
-    WgradOut out;   // first member: where the result goes (grouped launches; wgrad_reduce_kernel reads it through a byte stride)
-    const unsigned short* x;
-    const unsigned short* dy;
-    float* dw;
-    int M, OH, OW, H, W, Cin, Cout, KTOT, KW;
-    int stride, pad_h, pad_w;
-    int ld_x, ld_y;
-    int chunk;  // pixels per split (multiple of 64)
-    int gx, gy, splits;  // grid of this layer inside a grouped launch
-    int plain;  // 1x1 stride-1: source pixel == output pixel
-    float inv_ow, inv_ohw;
-    int x_bytes, dy_bytes;   // extents for the buffer resource descriptors (< 2^30)
-    // normalise-on-load of x (see fn_conv_desc.nrm_*)
-    const acc_t* nrm_stats;
-    const float* nrm_beta;
-    int nrm_sq_off, nrm_replicas, nrm_rep_stride, nrm_count;
-    float nrm_eps;
-    // Grouped launches are DETERMINISTIC and atomic-free (out.store = 1): a layer with one split stores its tiles straight into
-    // dw; a layer with several splits stores split z into slab z of out.ws and wgrad_reduce_kernel adds the slabs in order.
-    // (Global float atomics run at ~1.3 TB/s at the memory side, plain stores at ~6 TB/s, and the order of atomic adds -- hence
-    // the rounding of dW -- changed from run to run.)  out.store = 0: legacy single launch, atomic accumulation into dw.
-};
-
-// k-step pixel permutation shared by both operands: tile row of MFMA k index (g = lane>>4, h = half, q)
-//   rho = q + 4*(g&1) + 8*h + 16*(g>>1)   -> the 8 rows a 32-lane half reads per ds_read_b64_tr_b16
-//   are distinct mod 8, which with row strides of 160 B / 288 B makes the transposed reads conflict free.
-template <typename T, int BMW, int BNW, bool NORM>
-__device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bx, const int by, const int bz) {
-    constexpr int BK = 64;                   // pixels per stage
-    constexpr int DEPTH = (BMW * BNW <= 64 * 64) ? 3 : (BMW * BNW <= 64 * 128 ? 2 : 1);   // register stages in flight
-    constexpr int RSA = BMW * 2 + 32;        // LDS row strides in bytes (160 for 64, 288 for 128, 96 for 32)
-    constexpr int RSB = BNW * 2 + 32;
-    constexpr int A_BYTES = BK * RSA, B_BYTES = BK * RSB;
-    constexpr int CGA = BMW / 8, CGB = BNW / 8;  // 16-B chunks per row
-    constexpr int AP = BK * CGA / 256, BP = BK * CGB / 256;
-    constexpr int WMW = (BMW >= 64) ? 2 : 1, WNW = 4 / WMW;
-    constexpr int TM = BMW / WMW, TN = BNW / WNW;
-    constexpr int MREP = TM / 16, NREP = TN / 16;
-    static_assert(AP >= 1 && BP >= 1 && MREP >= 1 && NREP >= 1, "tile too small");
-    typedef typename LP<T>::vec8 vec8;
-
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sA = smem;                 // [2][BK][RSA]  dY tile  (rows = pixels, cols = co)
-    unsigned char* sB = smem + 2 * A_BYTES;   // [2][BK][RSB]  X  tile  (rows = pixels, cols = kcol)
-    float* sNs = reinterpret_cast<float*>(smem + 2 * (A_BYTES + B_BYTES));   // NORM: [BNW] scale, [BNW] shift of this tile's columns
-    float* sNh = sNs + BNW;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WNW, wn = wave % WNW;
-    const int n0 = bx * BNW;  // kcol tile
-    const int c0 = by * BMW;  // cout tile
-    const int mbeg = bz * a.chunk;
-    const int mend = min(a.M, mbeg + a.chunk);
-    const int nst = (mend - mbeg + BK - 1) / BK;
-    if (nst <= 0) return;
-    if constexpr (NORM) {
-        if (tid < BNW) {
-            const int e = ktab_entry((n0 >> 3) + (tid >> 3), a.KTOT, a.Cin, a.KW);
-            float sc = 0.f, sh = 0.f, mean, var;
-            if (e >= 0) {
-                const int c = (e & 0xffff) + (tid & 7);
-                bn_batch_affine(a.nrm_stats, c, a.nrm_sq_off, a.nrm_replicas, a.nrm_rep_stride, a.nrm_count, a.nrm_eps, a.nrm_beta[c], sc, sh,
-                                mean, var);
-            }
-            sNs[tid] = sc;
-            sNh[tid] = sh;
-        }
-        __syncthreads();
-    }
-
-    // B-operand columns handled by this thread (fixed for the whole kernel)
-    int bcol_c[BP], bcol_dy[BP], bcol_dx[BP], brow[BP];
-    bool bcol_ok[BP];
-#pragma unroll
-    for (int j = 0; j < BP; ++j) {
-        const int cidx = tid + 256 * j;
-        brow[j] = cidx / CGB;
-        const int e = ktab_entry((n0 >> 3) + (cidx % CGB), a.KTOT, a.Cin, a.KW);
-        bcol_ok[j] = e >= 0;
-        bcol_dy[j] = ((e >> 24) & 0xff) - a.pad_h;
-        bcol_dx[j] = ((e >> 16) & 0xff) - a.pad_w;
-        bcol_c[j] = e & 0xffff;
-    }
-    int arow[AP], acol[AP];
-#pragma unroll
-    for (int i = 0; i < AP; ++i) {
-        const int cidx = tid + 256 * i;
-        arow[i] = cidx / CGA;
-        acol[i] = c0 + (cidx % CGA) * 8;
-    }
-
-    u32x4 ra[DEPTH][AP], rb[DEPTH][BP];
-    unsigned bmask[DEPTH];   // NORM only: X chunks of a stage that hold real pixels (bits 8..)
-    // buffer loads with hardware zero fill (see conv_igemm_body): ragged rows / columns and padding need no select
-    constexpr unsigned OOB = 0x60000000u;
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.dy), 0, a.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, a.x_bytes, 0x00020000);
-    unsigned acolb[AP];
-#pragma unroll
-    for (int i = 0; i < AP; ++i) acolb[i] = acol[i] < a.Cout ? (unsigned)acol[i] * 2u : OOB;
-    auto load_tile = [&](int stg, u32x4 (&ra)[AP], u32x4 (&rb)[BP], unsigned& msk) {
-        unsigned mk = 0u;
-        const int mb = mbeg + stg * BK;
-#pragma unroll
-        for (int i = 0; i < AP; ++i) {
-            const int m = mb + arow[i];
-            const unsigned off = m < mend ? (unsigned)m * (unsigned)a.ld_y * 2u + acolb[i] : OOB;
-            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_dy, (int)off, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < BP; ++j) {
-            const int m = mb + brow[j];
-            bool ok = m < mend && bcol_ok[j];
-            int pix = m;
-            if (!a.plain) {
-                int n, rem, oy, ox;
-                fast_divmod(m, a.OH * a.OW, a.inv_ohw, n, rem);
-                fast_divmod(rem, a.OW, a.inv_ow, oy, ox);
-                const int iy = oy * a.stride + bcol_dy[j], ix = ox * a.stride + bcol_dx[j];
-                ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                pix = (n * a.H + iy) * a.W + ix;
-            }
-            const unsigned off = ok ? ((unsigned)pix * (unsigned)a.ld_x + (unsigned)bcol_c[j]) * 2u : OOB;
-            rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)off, 0, 0);
-            if constexpr (NORM) mk |= (ok ? 1u : 0u) << (8 + j);
-        }
-        msk = mk;
-    };
-    auto store_tile = [&](int buf, const u32x4 (&ra)[AP], const u32x4 (&rb)[BP], const unsigned msk) {
-#pragma unroll
-        for (int i = 0; i < AP; ++i) {
-            const int cidx = tid + 256 * i;
-            *reinterpret_cast<u32x4*>(sA + buf * A_BYTES + arow[i] * RSA + (cidx % CGA) * 16) = ra[i];
-        }
-#pragma unroll
-        for (int j = 0; j < BP; ++j) {
-            const int cidx = tid + 256 * j;
-            u32x4 v = rb[j];
-            if constexpr (NORM) {
-                if (msk & (1u << (8 + j))) {
-                    const int col = (cidx % CGB) * 8;
-                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(sNs + col), s1 = *reinterpret_cast<const f32x4*>(sNs + col + 4);
-                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(sNh + col), h1 = *reinterpret_cast<const f32x4*>(sNh + col + 4);
-                    float f[8];
-                    unpack8<T>(v, f);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        f[e] = fmaxf(fmaf(f[e], s0[e], h0[e]), 0.f);
-                        f[4 + e] = fmaxf(fmaf(f[4 + e], s1[e], h1[e]), 0.f);
-                    }
-                    v = pack8<T>(f);
-                }
-            }
-            *reinterpret_cast<u32x4*>(sB + buf * B_BYTES + brow[j] * RSB + (cidx % CGB) * 16) = v;
-        }
-    };
-
-    f32x4 acc[MREP][NREP];
-#pragma unroll
-    for (int i = 0; i < MREP; ++i)
-#pragma unroll
-        for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // transposed-read addressing: lane -> (g, q, p); supplies the address of row rho(g,h,q), columns 4p..4p+3
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-    const int rho0 = q + 4 * (g & 1) + 16 * (g >> 1);  // + 8*h + 32*ks
-    typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-    auto compute = [&](int buf) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            vec8 fa[MREP], fb[NREP];
-#pragma unroll
-            for (int i = 0; i < MREP; ++i) {
-                const unsigned char* base = sA + buf * A_BYTES + (wm * TM + i * 16 + 4 * p) * 2;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + (rho0 + 32 * ks) * RSA));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + (rho0 + 8 + 32 * ks) * RSA));
-                fa[i] = __builtin_bit_cast(vec8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
-#pragma unroll
-            for (int j = 0; j < NREP; ++j) {
-                const unsigned char* base = sB + buf * B_BYTES + (wn * TN + j * 16 + 4 * p) * 2;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + (rho0 + 32 * ks) * RSB));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + (rho0 + 8 + 32 * ks) * RSB));
-                fb[j] = __builtin_bit_cast(vec8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
-#pragma unroll
-            for (int i = 0; i < MREP; ++i)
-#pragma unroll
-                for (int j = 0; j < NREP; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);
-        }
-    };
-
-    const int last = nst - 1;   // branch-free steady state, clamped stage index (see conv_igemm_body)
-#pragma unroll
-    for (int d = 0; d < DEPTH; ++d) load_tile(min(d, last), ra[d], rb[d], bmask[d]);
-    store_tile(0, ra[0], rb[0], bmask[0]);
-    __syncthreads();
-    for (int s0 = 0; s0 < nst; s0 += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; ++d) {
-            const int stg = s0 + d;
-            load_tile(min(stg + DEPTH, last), ra[d], rb[d], bmask[d]);
-            if (stg < nst) compute(stg & 1);
-            store_tile((stg + 1) & 1, ra[(d + 1) % DEPTH], rb[(d + 1) % DEPTH], bmask[(d + 1) % DEPTH]);
-            __syncthreads();
-        }
-    }
-
-    // C layout: col = lane&15 (kcol), row = (lane>>4)*4 + r (cout)
-    float* const dst = a.out.ws ? a.out.ws + (long)bz * a.Cout * a.KTOT : a.dw;
-#pragma unroll
-    for (int i = 0; i < MREP; ++i)
-#pragma unroll
-        for (int j = 0; j < NREP; ++j) {
-            const int kc = n0 + wn * TN + j * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = c0 + wm * TM + i * 16 + g * 4 + r;
-                if (co < a.Cout && kc < a.KTOT) {
-                    if (a.out.store) dst[(long)co * a.KTOT + kc] = acc[i][j][r];
-                    else unsafeAtomicAdd(&a.dw[(long)co * a.KTOT + kc], acc[i][j][r]);
-                }
-            }
-        }
-}
-
-// Second stage of the grouped weight gradients: dw = slab 0 + slab 1 + ... in that order (blockIdx.y = layer; the per-layer
-// records of either weight-gradient kernel start with a WgradOut and are `stride` bytes apart).
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const unsigned char* __restrict__ args, int stride) {
-    const WgradOut a = *reinterpret_cast<const WgradOut*>(args + (long)blockIdx.y * stride);
-    if (a.ws == nullptr) return;
-    const long n4 = (long)a.Cout * a.KTOT / 4;          // layer sizes are multiples of 4
-    const f32x4* ws = reinterpret_cast<const f32x4*>(a.ws);
-    f32x4* dw = reinterpret_cast<f32x4*>(a.dw);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        f32x4 s = ws[i];
-        int z = 1;
-        for (; z + 8 <= a.splits; z += 8) {       // eight slab reads in flight, added in slab order
-            f32x4 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = ws[(long)(z + k) * n4 + i];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; z < a.splits; ++z) s += ws[(long)z * n4 + i];
-        dw[i] = s;
-    }
-}
-
-template <typename T, int BMW, int BNW, bool NORM>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
-    conv_wgrad_body<T, BMW, BNW, NORM>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// Grouped form: ONE launch computes the weight gradients of many layers.  Weight gradients have no consumer before the
-// optimiser, so the engine defers them to the end of backward and issues them per tile configuration: thousands of
-// workgroups per launch instead of 133 launches that each fill a fraction of the 256 CUs.
-// args[g] describes layer g; prefix[g] .. prefix[g+1] are its workgroups (gx * gy * splits).
-template <typename T, int BMW, int BNW, bool NORM>
-__global__ __launch_bounds__(256) void conv_wgrad_grouped_kernel(const unsigned char* __restrict__ args_raw, int stride, const int* __restrict__ prefix, int n) {
-    const int bid = blockIdx.x;
-    int lo = 0, hi = n;                    // largest g with prefix[g] <= bid
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= bid) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);           // wave-uniform: scalar loads of the record
-    const WgradArgs a = *reinterpret_cast<const WgradArgs*>(args_raw + (long)lo * stride);
-    // Workgroups that share a pixel chunk (same split, all gx*gy tiles) are consecutive in the layer's logical order: inside
-    // the layer give every XCD a contiguous run of it, so a chunk of X / dY is fetched into one L2 instead of all eight
-    // (per layer, not per launch: whole layers on one XCD would unbalance the chip).
-    const int gxy = a.gx * a.gy;
-    const int local = xcd_remap(bid - prefix[lo], gxy * a.splits);
-    const int bz = local / gxy, r = local - bz * gxy;
-    conv_wgrad_body<T, BMW, BNW, NORM>(a, r % a.gx, r / a.gx, bz);
-}
-
-template <typename T, int BMW, int BNW> static int launch_wgrad(const WgradArgs& a, int splits, hipStream_t st) {
-    constexpr int RSA = BMW * 2 + 32, RSB = BNW * 2 + 32;
-    // 64x64 stages are exactly 40 KiB: four workgroups per CU.  Only normalise-on-load launches pay for the affine table.
-    const size_t smem = 2 * 64 * (RSA + RSB) + (a.nrm_stats ? 2 * BNW * 4 : 0);
-    dim3 grid(cdiv(a.KTOT, BNW), cdiv(a.Cout, BMW), splits);
-    if (a.nrm_stats) hipLaunchKernelGGL((conv_wgrad_kernel<T, BMW, BNW, true>), grid, dim3(256), smem, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<T, BMW, BNW, false>), grid, dim3(256), smem, st, a);
-    return check_launch("conv_wgrad");
-}
-
-static void choose_wgrad_tile(int Cout, int KTOT, int& bmw, int& bnw) {
-    bmw = Cout <= 32 ? 32 : (Cout <= 64 || Cout % 128 != 0 ? 64 : 128);
-    bnw = (KTOT <= 64 || (cdiv(KTOT, 128) * 128 - KTOT) > 32) ? 64 : 128;
-}
-
-// Split-K factor over pixels.  Every split adds one fp32 copy of dW through global atomics (~1.3 TB/s chip-wide,
-// MI355X_MICROARCH.md) while fewer splits mean a longer serial stage chain per workgroup (~0.5 us per 64-pixel stage at
-// the occupancy these launches get).  Minimise  stages(s)*0.5us + s*bytes(dW)/1.3TB/s  subject to filling the chip.
-static int choose_wgrad_splits(int M, int Cout, int KTOT, int bmw, int bnw) {
-    const long tiles = (long)cdiv(KTOT, bnw) * cdiv(Cout, bmw);
-    const int stages = cdiv(M, 64);
-    static const int stem_wgs = getenv("FN_WG_STEMWGS") ? atoi(getenv("FN_WG_STEMWGS")) : 1024;   // tuning aid
-    if (stages >= 1024) {   // long chains (stem): ~1024 workgroups in total, at least 4 stages each
-        int s = (int)((stem_wgs + tiles - 1) / tiles);
-        if (s > stages / 4) s = stages / 4;
-        return s < 1 ? 1 : s;
-    }
-    const double atom_us = (double)Cout * KTOT * 4.0 / 1.3e6;   // one fp32 copy of dW
-    int best = 1;
-    double best_t = 1e30;
-    for (int s = 1; s <= stages && s <= 512; s = (s < 8 ? s + 1 : s + s / 4)) {
-        const double waves = (double)(tiles * s) / 512.0;        // ~2 workgroups per CU resident
-        const double t = cdiv(stages, s) * 0.5 * (waves > 1.0 ? waves : 1.0) + s * atom_us;
-        if (t < best_t) { best_t = t; best = s; }
-    }
-    return best;
-}
-
-static void final_wgrad_tile(int Cout, int KTOT, int& bmw, int& bnw) {
-    choose_wgrad_tile(Cout, KTOT, bmw, bnw);
-    static const int big = getenv("FN_WGRAD_BIG") ? atoi(getenv("FN_WGRAD_BIG")) : 0;   // tuning aid
-    if (big == 1) return;
-    // small problems: prefer 64-wide tiles so that enough workgroups exist without a deep split
-    if ((long)cdiv(KTOT, bnw) * cdiv(Cout, bmw) < (big == 2 ? 16 : 64)) {
-        if (bmw == 128) bmw = 64;
-        if (bnw == 128 && KTOT > 64) bnw = 64;
-    }
-}
-
-static int plan_wgrad(WgradArgs& a, int want_splits, int bmw, int bnw, bool grouped) {
-    int splits = want_splits > 0 ? want_splits : choose_wgrad_splits(a.M, a.Cout, a.KTOT, bmw, bnw);
-    if (grouped && want_splits <= 0) {
-        // inside a grouped launch the chip is full anyway: fewer, longer splits.  Every split adds one fp32 copy of dW through
-        // global atomics, and that traffic -- not the MFMA work -- is what the launch is made of once X / dY come from L2:
-        // measured 606 / 533 / 510 / 502 / 504 / 591 us for >= 8 / 16 / 32 / 48 / 64 / 96 stages per split
-        static const int min_stages = getenv("FN_WG_MINSTAGES") ? atoi(getenv("FN_WG_MINSTAGES")) : 48;   // tuning aid
-        const int cap = cdiv(cdiv(a.M, 64), min_stages);
-        if (splits > cap) splits = cap < 1 ? 1 : cap;
-    }
-    a.chunk = cdiv(cdiv(a.M, splits), 64) * 64;
-    splits = cdiv(a.M, a.chunk);
-    a.gx = cdiv(a.KTOT, bnw);
-    a.gy = cdiv(a.Cout, bmw);
-    a.splits = splits;
-    return splits;
-}
-
-template <typename T> static int dispatch_wgrad(WgradArgs& a, int want_splits, hipStream_t st) {
-    int bmw, bnw;
-    final_wgrad_tile(a.Cout, a.KTOT, bmw, bnw);
-    const int splits = plan_wgrad(a, want_splits, bmw, bnw, false);
-    if (bmw == 32) return bnw == 64 ? launch_wgrad<T, 32, 64>(a, splits, st) : launch_wgrad<T, 32, 128>(a, splits, st);
-    if (bmw == 64) return bnw == 64 ? launch_wgrad<T, 64, 64>(a, splits, st) : launch_wgrad<T, 64, 128>(a, splits, st);
-    return bnw == 64 ? launch_wgrad<T, 128, 64>(a, splits, st) : launch_wgrad<T, 128, 128>(a, splits, st);
 }
 
 }  // namespace fn
@@ -1724,7 +1329,7 @@ static int make_fwd_args(const fn_conv_desc* d, ConvArgs& a) {
     a.ld_src = d->ld_x; a.ld_out = d->ld_y; a.ld_res = d->ld_res;
     a.relu = d->relu; a.accumulate = d->accumulate; a.out_f32 = d->out_f32; a.scale = d->scale;
     a.stats_sq_off = d->stats_sq_off;
-    a.plain = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad_h == 0 && d->pad_w == 0) ? 1 : 0;
+    a.plain = is_plain(d);
     a.nocheck = (d->pad_h == 0 && d->pad_w == 0) ? 1 : 0;   // check_desc guarantees (OH-1)*stride + KH <= H
     a.stats_replicas = d->stats_replicas > 0 ? d->stats_replicas : 1;
     a.stats_rep_stride = d->stats_rep_stride;
@@ -1739,9 +1344,7 @@ static int make_fwd_args(const fn_conv_desc* d, ConvArgs& a) {
     a.tile = d->tile_fwd;
     if (d->nrm_stats) {
         FN_REQUIRE(d->nrm_beta && d->Cin <= 512 && d->nrm_count > 0 && d->nrm_eps > 0.f, "conv_fwd: normalise-on-load needs beta, Cin <= 512, count, eps");
-        a.nrm_stats = d->nrm_stats; a.nrm_beta = d->nrm_beta; a.nrm_sq_off = d->nrm_sq_off;
-        a.nrm_replicas = d->nrm_replicas > 0 ? d->nrm_replicas : 1; a.nrm_rep_stride = d->nrm_rep_stride;
-        a.nrm_count = d->nrm_count; a.nrm_eps = d->nrm_eps;
+        copy_norm_fields(d, a);
         if (d->nrm_z) {
             FN_REQUIRE(d->stride == 1 && d->OH == d->H && d->OW == d->W, "conv_fwd: nrm_z needs stride 1 and an output map of the input's size");
             a.nrm_z = (unsigned short*)d->nrm_z;
@@ -1766,7 +1369,7 @@ static int make_dgrad_args(const fn_conv_desc* d, ConvArgs& a) {
     a.s2 = d->stride == 2 ? 1 : 0;
     a.ld_src = d->ld_y; a.ld_out = d->ld_x; a.ld_res = 0;
     a.relu = 0; a.accumulate = d->accumulate; a.out_f32 = d->out_f32; a.scale = 1.f;
-    a.plain = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad_h == 0 && d->pad_w == 0) ? 1 : 0;
+    a.plain = is_plain(d);
     a.stats_replicas = 1;
     FN_REQUIRE((long)d->N * d->OH * d->OW * d->ld_y * 2 < (1L << 30) && (long)d->Cin * a.KTOT * 2 < (1L << 30),
                "conv_dgrad: dy or wt exceeds the 1 GiB range of 32-bit buffer offsets");
@@ -1831,32 +1434,34 @@ extern "C" int fn_conv2d_arg_bytes(void) { return (int)sizeof(ConvArgs); }
 
 // Host-side planning for n INDEPENDENT descriptors (op 0 = fwd, 1 = dgrad) that share tile `variant`
 // (= fn_conv2d_variant(desc, op)) and 1x1-ness: fills host_args / host_prefix, *smem_bytes; returns total workgroups.
+// A member is accepted iff it resolves to the group's kernel: the variant's tile and split, the first member's operand kind.
 extern "C" int fn_conv2d_group_build(const fn_conv_desc* descs, int n, int op, int variant, void* host_args, int32_t* host_prefix,
                                      int32_t* smem_bytes) {
     FN_REQUIRE(descs && host_args && host_prefix && smem_bytes && n > 0 && (op == 0 || op == 1), "conv_group_build: bad arguments");
-    const int ks = variant >= 1000000 ? variant / 1000000 : 1;
-    const int bm = variant % 1000000 / 1000, bn = variant % 1000;
+    ConvKernel group{};
+    variant_decode(variant, group.bm, group.bn, group.ks);
     ConvArgs* out = reinterpret_cast<ConvArgs*>(host_args);
     long total = 0;
     size_t smem = 0;
-    int plain0 = -1;
     for (int i = 0; i < n; ++i) {
         ConvArgs a;
         if (int rc = (op == 0 ? make_fwd_args(&descs[i], a) : make_dgrad_args(&descs[i], a))) return rc;
-        int m, k;
-        choose_conv_tile(a.M, a.NOUT, a.tile, m, k);
-        const int ksi = a.nrm_stats ? 1 : choose_conv_ks(a.M, a.NOUT, a.KTOT, m, k);
-        FN_REQUIRE(m == bm && k == bn && ksi == ks, "conv_group_build: descriptor %d dispatches to %dx%d ks=%d, group is %dx%d ks=%d", i, m, k,
-                   ksi, bm, bn, ks);
+        ConvKernel k;
+        if (int rc = resolve_conv(a, k)) return rc;
+        FN_REQUIRE(!k.halo, "conv_group_build: descriptor %d runs on the halo-tile kernel, a launch of its own", i);
+        FN_REQUIRE(k.bm == group.bm && k.bn == group.bn && k.ks == group.ks,
+                   "conv_group_build: descriptor %d dispatches to %dx%d ks=%d, group is %dx%d ks=%d", i, k.bm, k.bn, k.ks, group.bm, group.bn, group.ks);
         FN_REQUIRE(descs[i].dtype == descs[0].dtype, "conv_group_build: mixed dtypes");
-        FN_REQUIRE(a.nt_total == 0, "conv_group_build: a data gradient with sibling sources is a launch of its own");
-        const int pl = a.plain | (a.nrm_stats ? 2 : 0);
-        if (plain0 < 0) plain0 = pl;
-        FN_REQUIRE(pl == plain0, "conv_group_build: 1x1 / general / normalise-on-load convolutions cannot share a group");
-        plan_tiles(a, bm, bn);
+        FN_REQUIRE(k.mode != 2, "conv_group_build: a data gradient with sibling sources is a launch of its own");
+        if (i == 0) {
+            group.plain = k.plain;
+            group.mode = k.mode;
+        }
+        FN_REQUIRE(k.plain == group.plain && k.mode == group.mode, "conv_group_build: 1x1 / general / normalise-on-load convolutions cannot share a group");
+        plan_tiles(a, group.bm, group.bn);
         host_prefix[i] = (int32_t)total;
         total += (long)a.total_tiles;
-        const size_t sm = conv_smem_bytes(bm, bn, a.KTOT, a.plain, a.nrm_stats ? a.CS : 0, ks);
+        const size_t sm = conv_smem_bytes(group.bm, group.bn, a.KTOT, k.plain, k.mode == 1 ? a.CS : 0, group.ks);
         if (sm > smem) smem = sm;
         out[i] = a;
     }
@@ -1871,156 +1476,35 @@ extern "C" int fn_conv2d_grouped(const void* dev_args, const int32_t* dev_prefix
     FN_REQUIRE(dev_args && dev_prefix && n > 0 && n <= 64 && total_blocks > 0, "conv_grouped: bad arguments");
     FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
     const ConvArgs* a = reinterpret_cast<const ConvArgs*>(dev_args);
-    const int ks = variant >= 1000000 ? variant / 1000000 : 1, bm = variant % 1000000 / 1000, bn = variant % 1000;
-    return dtype == FN_BF16
-               ? dispatch_conv_grouped<__bf16>(a, dev_prefix, n, total_blocks, bm, bn, ks, plain, (size_t)smem_bytes, (hipStream_t)stream)
-               : dispatch_conv_grouped<_Float16>(a, dev_prefix, n, total_blocks, bm, bn, ks, plain, (size_t)smem_bytes, (hipStream_t)stream);
+    ConvKernel k{};
+    variant_decode(variant, k.bm, k.bn, k.ks);
+    k.plain = plain & 1;
+    k.mode = (plain & 2) ? 1 : 0;   // bit 1 of `plain`: every member normalises on load
+    return dtype == FN_BF16 ? dispatch_conv_grouped<__bf16>(a, dev_prefix, n, total_blocks, k, (size_t)smem_bytes, (hipStream_t)stream)
+                            : dispatch_conv_grouped<_Float16>(a, dev_prefix, n, total_blocks, k, (size_t)smem_bytes, (hipStream_t)stream);
 }
 
-static int make_wgrad_args(const fn_conv_desc* d, WgradArgs& a) {
-    if (int rc = check_desc(d)) return rc;
-    FN_REQUIRE(d->x && d->y && d->dw, "conv_wgrad: null x/dy/dw");
-    FN_REQUIRE(d->ld_y % 8 == 0 && d->ld_y >= d->Cout, "conv_wgrad: ld_y=%d invalid", d->ld_y);
-    FN_REQUIRE((long)d->N * d->OH * d->OW < (1L << 24), "conv_wgrad: N*OH*OW must be < 2^24");
-    a = WgradArgs{};
-    a.x = (const unsigned short*)d->x; a.dy = (const unsigned short*)d->y; a.dw = d->dw;
-    a.M = d->N * d->OH * d->OW; a.OH = d->OH; a.OW = d->OW; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.KTOT = d->KH * d->KW * d->Cin; a.KW = d->KW; a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w;
-    a.ld_x = d->ld_x; a.ld_y = d->ld_y;
-    a.plain = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad_h == 0 && d->pad_w == 0) ? 1 : 0;
-    a.inv_ow = 1.0f / (float)d->OW; a.inv_ohw = 1.0f / (float)(d->OH * d->OW);
-    FN_REQUIRE((long)d->N * d->H * d->W * d->ld_x * 2 < (1L << 30) && (long)a.M * d->ld_y * 2 < (1L << 30),
-               "conv_wgrad: x or dy exceeds the 1 GiB range of 32-bit buffer offsets");
-    a.x_bytes = d->N * d->H * d->W * d->ld_x * 2;
-    a.dy_bytes = a.M * d->ld_y * 2;
-    if (d->nrm_stats) {
-        FN_REQUIRE(d->nrm_beta && d->nrm_count > 0 && d->nrm_eps > 0.f, "conv_wgrad: normalise-on-load needs beta, count, eps");
-        a.nrm_stats = d->nrm_stats; a.nrm_beta = d->nrm_beta; a.nrm_sq_off = d->nrm_sq_off;
-        a.nrm_replicas = d->nrm_replicas > 0 ? d->nrm_replicas : 1; a.nrm_rep_stride = d->nrm_rep_stride;
-        a.nrm_count = d->nrm_count; a.nrm_eps = d->nrm_eps;
-    }
-    return FN_OK;
-}
-
-extern "C" int fn_conv2d_wgrad(const fn_conv_desc* d, void* stream) {
-    WgradArgs a;
-    if (int rc = make_wgrad_args(d, a)) return rc;
-    return d->dtype == FN_BF16 ? dispatch_wgrad<__bf16>(a, d->splits, (hipStream_t)stream)
-                               : dispatch_wgrad<_Float16>(a, d->splits, (hipStream_t)stream);
-}
-
-// ---- grouped weight gradients ------------------------------------------------------------------------------------
-// one record size for both weight-gradient kernels (groups of either kind use the same host / device buffers)
-extern "C" int fn_conv2d_wgrad_arg_bytes(void) {
-    const size_t a = sizeof(WgradArgs), b = wgrad_taps_arg_bytes();
-    return (int)(((a > b ? a : b) + 15) / 16 * 16);
-}
-
-// Host-side planning: fills host_args[n * fn_conv2d_wgrad_arg_bytes()] and host_prefix[n+1] for n descriptors that all
-// dispatch to `variant` (= fn_conv2d_variant(desc, 2)); returns the total number of workgroups (or a negative status).
-extern "C" int fn_conv2d_wgrad_group_build(const fn_conv_desc* descs, int n, int variant, void* host_args, int32_t* host_prefix, float* ws,
-                                           int64_t* ws_elems) {
-    FN_REQUIRE(descs && host_args && host_prefix && ws_elems && n > 0, "wgrad_group_build: bad arguments");
-    long ws_used = 0;
-    const size_t rec_bytes = (size_t)fn_conv2d_wgrad_arg_bytes();
-    if (variant >= WGRAD_TAPS_VARIANT) {      // tap-sharing kernel (conv_wgrad_taps.hip)
-        long total = 0;
-        for (int i = 0; i < n; ++i) {
-            if (int rc = check_desc(&descs[i])) return rc;
-            FN_REQUIRE(descs[i].dtype == descs[0].dtype, "wgrad_group_build: mixed dtypes");
-            host_prefix[i] = (int32_t)total;
-            const long wgs = wgrad_taps_plan(&descs[i], variant, reinterpret_cast<unsigned char*>(host_args) + i * rec_bytes, ws, &ws_used);
-            if (wgs < 0) return (int)wgs;
-            total += wgs;
-        }
-        FN_REQUIRE(total < (1L << 30), "wgrad_group_build: too many workgroups");
-        host_prefix[n] = (int32_t)total;
-        *ws_elems = ws_used;
-        return (int)total;
-    }
-    const bool norm = variant >= 1000000;
-    variant %= 1000000;
-    const int bmw = variant / 1000, bnw = variant % 1000;
-    long total = 0;
-    for (int i = 0; i < n; ++i) {
-        WgradArgs a;
-        if (int rc = make_wgrad_args(&descs[i], a)) return rc;
-        int m, k;
-        final_wgrad_tile(a.Cout, a.KTOT, m, k);
-        FN_REQUIRE(m == bmw && k == bnw, "wgrad_group_build: descriptor %d dispatches to %dx%d, group is %dx%d", i, m, k, bmw, bnw);
-        FN_REQUIRE(descs[i].dtype == descs[0].dtype, "wgrad_group_build: mixed dtypes");
-        FN_REQUIRE((a.nrm_stats != nullptr) == norm, "wgrad_group_build: descriptor %d: normalise-on-load members need a group of their own (variant + 1000000)", i);
-        const int splits = plan_wgrad(a, descs[i].splits, bmw, bnw, true);
-        FN_REQUIRE(((long)a.Cout * a.KTOT) % 4 == 0, "wgrad_group_build: descriptor %d: Cout*K must be a multiple of 4", i);
-        a.out = WgradOut{a.dw, nullptr, a.Cout, a.KTOT, splits, 1};
-        if (splits > 1) {            // slabs of this layer: [splits][Cout*KTOT]; ws == NULL on the sizing call
-            a.out.ws = ws ? ws + ws_used : reinterpret_cast<float*>(16);
-            ws_used += (long)splits * a.Cout * a.KTOT;
-        }
-        host_prefix[i] = (int32_t)total;
-        total += (long)a.gx * a.gy * splits;
-        *reinterpret_cast<WgradArgs*>(reinterpret_cast<unsigned char*>(host_args) + i * rec_bytes) = a;
-    }
-    FN_REQUIRE(total < (1L << 30), "wgrad_group_build: too many workgroups");
-    host_prefix[n] = (int32_t)total;
-    *ws_elems = ws_used;
-    return (int)total;
-}
-
-extern "C" int fn_conv2d_wgrad_reduce(const void* dev_args, int n, void* stream) {
-    FN_REQUIRE(dev_args && n > 0 && n < 65536, "wgrad_reduce: bad arguments");
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(64, n), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned char*>(dev_args),
-                       fn_conv2d_wgrad_arg_bytes());
-    return check_launch("wgrad_reduce");
-}
-
-template <typename T> static int launch_wgrad_grouped(const void* args, const int32_t* prefix, int n, int total, int variant, hipStream_t st) {
-    const bool norm = variant >= 1000000;     // +1000000: every member normalises x on load
-    variant %= 1000000;
-    const int bmw = variant / 1000, bnw = variant % 1000;
-    const unsigned char* a = reinterpret_cast<const unsigned char*>(args);
-    const int stride_ = fn_conv2d_wgrad_arg_bytes();
-#define FN_WG(BM_, BN_)                                                                                                     \
-    if (bmw == BM_ && bnw == BN_) {                                                                                         \
-        const size_t sm_ = 2 * 64 * ((BM_) * 2 + 32 + (BN_) * 2 + 32) + (norm ? 2 * (BN_) * 4 : 0);                            \
-        if (norm) hipLaunchKernelGGL((conv_wgrad_grouped_kernel<T, BM_, BN_, true>), dim3(total), dim3(256), sm_, st, a, stride_, prefix, n); \
-        else hipLaunchKernelGGL((conv_wgrad_grouped_kernel<T, BM_, BN_, false>), dim3(total), dim3(256), sm_, st, a, stride_, prefix, n);    \
-        return check_launch("conv_wgrad_grouped");                                                                          \
-    }
-    FN_WG(32, 64) FN_WG(32, 128) FN_WG(64, 64) FN_WG(64, 128) FN_WG(128, 64) FN_WG(128, 128)
-#undef FN_WG
-    set_error("wgrad_grouped: unknown variant %d", variant);
-    return FN_EINVAL;
-}
-
-extern "C" int fn_conv2d_wgrad_grouped(const void* dev_args, const int32_t* dev_prefix, int n, int total_blocks, int variant, int dtype,
-                                       void* stream) {
-    FN_REQUIRE(dev_args && dev_prefix && n > 0 && total_blocks > 0, "wgrad_grouped: bad arguments");
-    FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
-    if (variant >= WGRAD_TAPS_VARIANT) return wgrad_taps_launch(dev_args, dev_prefix, n, total_blocks, variant, dtype, (hipStream_t)stream);
-    return dtype == FN_BF16 ? launch_wgrad_grouped<__bf16>(dev_args, dev_prefix, n, total_blocks, variant, (hipStream_t)stream)
-                            : launch_wgrad_grouped<_Float16>(dev_args, dev_prefix, n, total_blocks, variant, (hipStream_t)stream);
-}
-
-// Which kernel instantiation a descriptor dispatches to: returns BM*1000 + BN (op 0 = fwd, 1 = dgrad) or
-// BMW*1000 + BNW (op 2 = wgrad).  Lets bench.py attribute HIP-event timings to the kernel names rocprofv3 reports.
+// Which kernel instantiation a descriptor dispatches to (codes: conv_args.h, include/facenet_hip.h): op 0 = fwd, 1 = dgrad:
+// BM*1000 + BN + KS*1000000 (KS > 1), or 9000000 + BN for the halo-tile kernel (never grouped, never re-tiled); op 2 = wgrad:
+// BMW*1000 + BNW, or a tap-sharing code (wgrad_taps.h).  train.py groups and tunes by it, bench.py attributes HIP-event timings
+// to the kernel names rocprofv3 reports.
 extern "C" int fn_conv2d_variant(const fn_conv_desc* d, int op) {
     if (!d || op < 0 || op > 2) return FN_EINVAL;
-    int a, b;
-    if (op < 2) {   // halo-tile kernel: 9000000 + BN (never grouped, never re-tiled)
-        ConvArgs ca;
-        if ((op == 0 ? make_fwd_args(d, ca) : make_dgrad_args(d, ca)) == FN_OK && halo_eligible(ca)) return 9000000 + halo_bn(ca);
-        if ((op == 0 ? d->tile_fwd : d->tile_dgrad) == TILE_HALO) return FN_EUNSUPPORTED;   // requested, but not a layer the kernel runs
+    if (op == 2) return wgrad_variant(d);
+    ConvArgs a;
+    if ((op == 0 ? make_fwd_args(d, a) : make_dgrad_args(d, a)) != FN_OK) {
+        // FALLBACK: callers probe variants with descriptors that are not launchable yet (no pointers, a leading dimension still
+        // missing).  Answer from the geometry alone: what the resolver reads of a ConvArgs, nothing the halo kernel would accept.
+        const int tile = op == 0 ? d->tile_fwd : d->tile_dgrad;
+        a = ConvArgs{};
+        a.M = op == 0 ? d->N * d->OH * d->OW : d->N * d->H * d->W;
+        a.NOUT = op == 0 ? d->Cout : d->Cin;
+        a.KTOT = d->KH * d->KW * (op == 0 ? d->Cin : d->Cout);
+        a.tile = valid_tile(tile) ? tile : 0;
+        if (op == 0) a.nrm_stats = d->nrm_stats;
+        else a.nt_total = d->dy2 ? 1 : 0;
     }
-    if (op == 0) {
-        choose_conv_tile(d->N * d->OH * d->OW, d->Cout, valid_tile(d->tile_fwd) ? d->tile_fwd : 0, a, b);
-        return variant_code(a, b, d->nrm_stats ? 1 : choose_conv_ks(d->N * d->OH * d->OW, d->Cout, d->KH * d->KW * d->Cin, a, b));
-    }
-    if (op == 1) {
-        choose_conv_tile(d->N * d->H * d->W, d->Cin, valid_tile(d->tile_dgrad) ? d->tile_dgrad : 0, a, b);
-        return variant_code(a, b, d->dy2 ? 1 : choose_conv_ks(d->N * d->H * d->W, d->Cin, d->KH * d->KW * d->Cout, a, b));
-    }
-    if (const int tv = wgrad_taps_variant(d)) return tv;     // k x k layers on maps of >= 32 pixels: the tap-sharing kernel
-    final_wgrad_tile(d->Cout, d->KH * d->KW * d->Cin, a, b);
-    return a * 1000 + b;
+    ConvKernel k;
+    if (int rc = resolve_conv(a, k)) return rc;
+    return k.halo ? VARIANT_HALO + k.bn : variant_encode(k.bm, k.bn, k.ks);
 }

@@ -277,8 +277,8 @@ static int taps_of(const fn_conv_desc* d) { return d->KH * d->KW; }
 // launches held 160-370 workgroups with 90-stage chains each and ran one after the other (measured: 363 us for the four).
 enum { TAPS_BMW = 64, TAPS_MAX = 9, TAPS_NPL = 3, TAPS_PATCH_BYTES = 15360 };   // patch buffer: 160 px x 96 B (stride 1) / 192 px x 80 B (stride 2)
 int wgrad_taps_variant(const fn_conv_desc* d) {
-    static const int enabled = getenv("FN_WGRAD_TAPS") ? atoi(getenv("FN_WGRAD_TAPS")) : 1;
-    static const int min_pix = getenv("FN_WGRAD_TAPS_MINPIX") ? atoi(getenv("FN_WGRAD_TAPS_MINPIX")) : 32;
+    static const int enabled = env_int("FN_WGRAD_TAPS", 1);
+    static const int min_pix = env_int("FN_WGRAD_TAPS_MINPIX", 32);
     if (!enabled || d->nrm_stats) return 0;
     const bool shape = (d->KH == 3 && d->KW == 3 && (d->stride == 1 || d->stride == 2)) ||
                        (d->stride == 1 && ((d->KH == 1 && d->KW == 7) || (d->KH == 7 && d->KW == 1)));
@@ -367,8 +367,8 @@ long wgrad_taps_plan(const fn_conv_desc* d, int variant, void* rec, float* ws, l
     // pixel splits.  The grouped launch holds the workgroups of every k x k layer, so a layer need not fill the chip alone; what a
     // split costs is one more fp32 copy of the layer's dW written and read again (slab), what it buys is a shorter serial chain
     // of stages (~0.5 us each): chains of about `chain` stages, slabs of at most `slab_mb` MB per layer.
-    static const int chain = getenv("FN_WGT_CHAIN") ? atoi(getenv("FN_WGT_CHAIN")) : 64;
-    static const int slab_mb = getenv("FN_WGT_SLAB_MB") ? atoi(getenv("FN_WGT_SLAB_MB")) : 16;
+    static const int chain = env_int("FN_WGT_CHAIN", 64);
+    static const int slab_mb = env_int("FN_WGT_SLAB_MB", 16);
     const long numel = (long)a.out.Cout * a.out.KTOT;
     int splits = d->splits > 0 ? d->splits : std::max(1, std::min(cdiv(ntiles, chain), (int)(((long)slab_mb << 20) / (numel * 4))));
     a.chunk = cdiv(ntiles, splits);
@@ -379,7 +379,7 @@ long wgrad_taps_plan(const fn_conv_desc* d, int variant, void* rec, float* ws, l
         a.out.ws = ws ? ws + *ws_used : reinterpret_cast<float*>(16);
         *ws_used += (long)splits * a.out.Cout * a.out.KTOT;
     }
-    static const int debug = getenv("FN_WGT_DEBUG") ? atoi(getenv("FN_WGT_DEBUG")) : 0;
+    static const int debug = env_int("FN_WGT_DEBUG", 0);
     if (debug && ws == nullptr)
         fprintf(stderr, "wgrad_taps: %dx%dx%d->%d k%dx%d s%d: tile %dx%d patch %d px, %d tiles, %d x %d x %d workgroups\n", d->H, d->W, d->Cin, d->Cout,
                 d->KH, d->KW, d->stride, a.TH, a.TW, a.npix, a.ntiles, a.gx, a.gy, splits);

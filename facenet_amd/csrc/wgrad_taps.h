@@ -1,4 +1,4 @@
-// Interface between the C ABI in conv_igemm.hip and the tap-sharing weight-gradient kernel in conv_wgrad_taps.hip.
+// Interface between the weight-gradient C ABI in conv_wgrad.hip and the tap-sharing weight-gradient kernel in conv_wgrad_taps.hip.
 #pragma once
 #include "common.h"
 #include "../../include/facenet_hip.h"
