@@ -4,7 +4,9 @@ MI355X: every image of every class directory -> detector -> (optionally only sin
 antialiased resize -> ``<outdir>/<class>/<stem>.png`` (further faces of one image: ``<stem>_<n>.png``).  The reference stores
 the box sizes in an h5 file (h5py is not installed here): they go to ``sizes.json`` next to the thumbnails instead.
 ``python -m facenet_amd.apps.extract_faces --config x.yaml`` (keys: dataset.path, outdir, image.size, image.margin,
-detect_multiple_faces, detector, mtcnn.weights_file)."""
+detect_multiple_faces, detector, mtcnn.weights_file, image.device_resize).  With ``image.device_resize`` the thumbnails are cropped
+and resized on the device (`image_processing_batch`): the same pixels, and the frame is uploaded once for
+the detector and the resize."""
 from __future__ import annotations
 
 import json
@@ -16,12 +18,13 @@ from PIL import Image
 
 from facenet_amd import config as config_mod
 from facenet_amd import dataset
-from facenet_amd.detectors.face_detector import FaceDetector, image_processing
+from facenet_amd.detectors.face_detector import FaceDetector, image_processing, image_processing_batch
 
 
-def extract_faces(classes, outdir, detector, image_options, detect_multiple_faces: bool = False, log=print):
-    """classes: iterable of objects with .name and .files.  Returns {'extracted': images that produced thumbnails,
-    'unread': files PIL could not open, 'sizes': {relative png path: [box height, box width]}}."""
+def extract_faces(classes, outdir, detector, image_options, detect_multiple_faces: bool = False, log=print, device_resize: bool = False):
+    """classes: iterable of objects with .name and .files.  device_resize: crop and resize on the device instead of in PIL (the
+    same pixels).  Returns {'extracted': images that produced thumbnails, 'unread': files PIL could not open,
+    'sizes': {relative png path: [box height, box width]}}."""
     outdir = Path(outdir)
     stats = {"extracted": 0, "unread": 0, "sizes": {}}
     for cls in classes:
@@ -35,13 +38,17 @@ def extract_faces(classes, outdir, detector, image_options, detect_multiple_face
             except Exception:
                 stats["unread"] += 1
                 continue
+            if device_resize:
+                import torch
+                pixels = torch.from_numpy(pixels if pixels.flags.writeable else pixels.copy()).to("cuda")
             boxes = detector.detect(pixels)
             if len(boxes) == 0 or (len(boxes) > 1 and not detect_multiple_faces):
                 continue
             stats["extracted"] += 1
+            thumbs = image_processing_batch(pixels, boxes, image_options).cpu().numpy() if device_resize else None
             for n, box in enumerate(boxes):
                 name = target if n == 0 else target.parent.joinpath('{}_{}{}'.format(target.stem, n, target.suffix))
-                image_processing(img, box, image_options).save(name)
+                (Image.fromarray(thumbs[n]) if device_resize else image_processing(img, box, image_options)).save(name)
                 stats["sizes"][str(name.relative_to(outdir))] = [int(box.height), int(box.width)]
     with outdir.joinpath("sizes.json").open("w") as fh:
         json.dump(stats["sizes"], fh, indent=1, sort_keys=True)
@@ -59,7 +66,8 @@ def main(**options):
     print('output directory', cfg.outdir)
     detector = FaceDetector(detector=cfg.detector if cfg.detector else 'pypimtcnn', weights_file=cfg.mtcnn.weights_file)
     print(detector)
-    extract_faces(dbase.classes, Path(cfg.outdir).expanduser(), detector, cfg.image, bool(cfg.detect_multiple_faces))
+    extract_faces(dbase.classes, Path(cfg.outdir).expanduser(), detector, cfg.image, bool(cfg.detect_multiple_faces),
+                  device_resize=bool(cfg.image.device_resize))
 
 
 if __name__ == '__main__':

@@ -205,6 +205,19 @@ typedef struct fn_augment_param {
  * one launch; S must be even.  Sizes are not checked against the src allocation: the caller owns the packing. */
 int fn_augment_u8(const uint8_t* src, const long long* offsets, const int32_t* hw, const fn_augment_param* params, uint8_t* dst, int N,
                   int S, void* stream);
+/* PIL's `frame.crop(window).resize((side, side), LANCZOS)` for 8-bit RGB, bit for bit, for F windows over
+ * one HWC u8 frame [H,W,3] in device memory.  `windows` is HOST memory, F x (left, top, right, bottom) with exclusive right /
+ * bottom; a window may reach outside the frame on any side (those pixels of the crop are 0).  dst u8 [F,S,S,3] holds rows / columns
+ * [oy, oy+S) x [ox, ox+S) of each side x side result: ox = oy = 0, S = side is the whole thumbnail, ox = oy = (side - size) / 2,
+ * S = size the centre cut that fn_crop_or_pad_u8 would take from it.  Limits: side <= FN_FACE_CROP_MAX_SIDE, every window
+ * 1 .. FN_FACE_CROP_MAX_EXTENT pixels per axis (the rows one output row needs must fit 64 KiB of LDS at any side), F <= 65535.
+ * `workspace` is device memory of at least the int32 words fn_face_crop_workspace reports for the same windows and side; the
+ * windows are copied into it on `stream`, then one table launch and one resampling launch follow. */
+#define FN_FACE_CROP_MAX_SIDE 256
+#define FN_FACE_CROP_MAX_EXTENT 3072
+int fn_face_crop_workspace(const int32_t* windows, int F, int side, long long* words);
+int fn_face_crop_resize_u8(const uint8_t* frame, int H, int W, const int32_t* windows, int F, int side, int ox, int oy, int S, uint8_t* dst,
+                           int32_t* workspace, long long workspace_words, void* stream);
 /* gather rows of a u8 image pool by index (triplet batch assembly): out[i] = pool[idx[i]].  bytes_per_image must be a multiple
  * of 16 (the images are copied as 16-byte vectors; fn_crop_or_pad_u8 / fn_augment_u8 refuse odd sizes likewise, so a 299 x 299 x 3
  * pool is not supported); anything else is rejected before the launch. */
