@@ -14,15 +14,58 @@
 //     (the halo kernel's layout: any run of 16 pixels is conflict free for ds_read_b128).  t1a is kept with a 3-pixel zero
 //     halo left and right, t1b with a 3-row halo above and below: the seven taps of the 1x7 / 7x1 layers are seven shifted
 //     views of the same LDS image, no gather, no bounds test;
-//   * only weights stream: per k step (32 input channels of one tap) a [columns][32] slab goes global -> registers -> LDS
-//     while the previous slab is multiplied (issue early / write late); the trunk tile of stage 1 streams the same way;
-//   * the epilogue of stages 1-3 adds the folded bias, applies ReLU and writes f16/bf16 straight into the next stage's LDS
-//     image; stage 4 goes through an fp32 C tile for 16-byte coalesced stores, adds the trunk (re-read from L2) and the bias
-//     in fp32 exactly like the un-fused epilogue (resid + scale * (acc + bias), one rounding).
-// Work per image: 88 MFLOP and 1.38 MB of weights; the weight stream (L2 -> CU, ~64 B/clk) and the MFMA time are about equal.
+//   * only weights stream: in stage 1 per k step (32 input channels) a [256 columns][32] slab and the trunk tile go global ->
+//     LDS while earlier slabs are multiplied: directly (LDS-DMA, three buffers, counted waits; stages 2-4 stream [128][64] slabs
+//     the same way), or through a ring of registers (issue early / write late) with FN_B17_DMA=0;
+//   * the MFMA is called as mfma(weights, pixels), so a lane holds four consecutive channels of one pixel: the epilogue of
+//     stages 1-3 adds the folded bias (requested BEFORE the k loop), applies ReLU and writes 8 bytes of f16/bf16 per fragment
+//     straight into the next stage's LDS image; stage 4 writes an fp32 C tile with 16-byte LDS stores, reads it back for 16-byte
+//     coalesced global stores, adds the trunk (requested from L2 at the pass's first k tile) and the bias in fp32 exactly like the
+//     un-fused epilogue (resid + scale * (acc + bias), one rounding).
+// Work per image: 88 MFLOP and 1.38 MB of weights.  A CU draws that stream from L2 at ~70 GB/s (~29 B/clk): 20 us per
+// image, against ~4 us of MFMA time -- one image per workgroup is bound by the weight stream's latency chain, not by the MFMA.
 #include "common.h"
 #include "../../include/facenet_hip.h"
 #include <cstdlib>
+
+#ifndef FN_FUSED_PHASES
+#define FN_FUSED_PHASES 0     // developer builds only (-DFN_FUSED_PHASES=1, tools/dev_fused_blocks.py): per-workgroup phase clocks, results unchanged
+#endif
+
+#if FN_FUSED_PHASES     // 100 MHz wall clock at the stage boundaries, summed per kernel (0 = Block17, 1 = Block35) into 256 replicas of 32 slots
+__device__ unsigned long long fn_fused_phase[256 * 2 * 32];
+extern "C" int fn_debug_fused_phases(unsigned long long* out, int reset) {
+    static unsigned long long host[256 * 2 * 32];
+    if (out) {
+        if (hipMemcpyFromSymbol(host, HIP_SYMBOL(fn_fused_phase), sizeof(host)) != hipSuccess) return -1;
+        for (int i = 0; i < 2 * 32; ++i) {
+            out[i] = 0;
+            for (int r = 0; r < 256; ++r) out[i] += host[r * 2 * 32 + i];
+        }
+    }
+    if (reset) {
+        for (auto& v : host) v = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(fn_fused_phase), host, sizeof(host)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+// slot 0 counts workgroups; FN_PH(slot) adds the time since the previous stamp to `slot` (thread 0, fire-and-forget atomic)
+#define FN_PH_INIT(kern)                                                                                  \
+    unsigned long long* const ph_p = fn_fused_phase + ((blockIdx.x & 255) * 2 + (kern)) * 32;            \
+    unsigned long long ph_last = wall_clock64();                                                          \
+    if (threadIdx.x == 0) atomicAdd(ph_p, 1ull);
+#define FN_PH(slot)                                                                                       \
+    {                                                                                                     \
+        const unsigned long long ph_t = wall_clock64();                                                   \
+        if (threadIdx.x == 0) atomicAdd(ph_p + (slot), ph_t - ph_last);                                   \
+        ph_last = ph_t;                                                                                   \
+    }
+#define FN_PH_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");     // splits "wait for what was requested" (all but the n youngest) from "use it"
+#else
+#define FN_PH_INIT(kern)
+#define FN_PH(slot)
+#define FN_PH_WAIT(n)
+#endif
 
 namespace fn {
 
@@ -72,6 +115,18 @@ __device__ __forceinline__ void warm_range(const unsigned char* p, long bytes, i
 
 __device__ __forceinline__ int swz64(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4); }
 
+// The MFMA is called as mfma(weights, pixels): a lane's four accumulator values are four CONSECUTIVE CHANNELS (4 fq + r of the
+// 16-column fragment) of ONE pixel (fr of the 16-row fragment).  A tower epilogue is then one 8-byte LDS store per fragment and a
+// stage-4 C-tile write one 16-byte store; the dot products are what mfma(pixels, weights) computes, k order included.
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+template <typename T> __device__ __forceinline__ u32x2 pack4_bias_relu(const f32x4& v, const f32x4& b) {
+    u32x2 o;
+    o[0] = (unsigned)LP<T>::from_f32(fmaxf(v[0] + b[0], 0.f)) | ((unsigned)LP<T>::from_f32(fmaxf(v[1] + b[1], 0.f)) << 16);
+    o[1] = (unsigned)LP<T>::from_f32(fmaxf(v[2] + b[2], 0.f)) | ((unsigned)LP<T>::from_f32(fmaxf(v[3] + b[3], 0.f)) << 16);
+    return o;
+}
+__device__ __forceinline__ f32x4 load_bias4(const float* b) { return f32x4{b[0], b[1], b[2], b[3]}; }      // 4-byte aligned is enough
+
 // Software pipeline shared by the four stages: k tiles kt+1 .. kt+D-1 are in flight in a ring of D register sets (a workgroup is
 // alone on its CU -- the LDS images take 130 KB -- so nothing but its own prefetch depth hides the L2 latency of the weight
 // stream), two LDS staging buffers, ONE barrier per k tile:
@@ -100,22 +155,31 @@ __device__ __forceinline__ int swz64(int row, int chunk) { return row * 64 + ((c
         }                                                                                   \
     }
 
-// LDS-DMA form of the weight stream of stages 2-4 (template DMA): the slabs go global -> LDS directly (buffer_load ... lds, 1 KiB per
+// LDS-DMA form of the weight stream (template DMA; stage 1 brings its trunk slices the same way): the slabs go global -> LDS directly (buffer_load ... lds, 1 KiB per
 // wave instruction, the chunk XOR of the LDS layout applied to the per-lane SOURCE address), three LDS buffers, a counted
 // s_waitcnt vmcnt(2) + a raw s_barrier per k tile -- no staging registers, no ds_write, the next two tiles stay in flight across
 // the barrier (cdna_hip_programming.md section 5, "Pipelining across barriers").  NB buffers: tile kt lives in buffer kt % 3.
-#define FN_DMA_PIPELINE(U_, NT_, ISSUE, COMPUTE)                                          \
+// WAIT(d) is the counted wait of the stage: vmcnt(2) where only the two youngest tiles (two instructions each) may be pending;
+// stage 4 lets its pass prefetch (issued after the tiles of d % 4 == 0) stay in flight as well.  Requests retire in order, and
+// every wait names only requests YOUNGER than the tile it needs, so an early store acknowledgement cannot satisfy it too soon.
+#define FN_DMA_WAIT2(d) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+// Tiles are guarded in groups of G_ (NT_ is a multiple of G_): the compiler then sees that a group runs whole, and what the
+// first tile of a group requests for the last one to use (stage 4) is not "possibly still pending" at the loop head.
+#define FN_DMA_PIPELINE(U_, G_, NT_, WAIT, ISSUE, COMPUTE)                                \
     {                                                                                       \
+        static_assert((U_) % (G_) == 0 && (NT_) % (G_) == 0 && (U_) % 3 == 0, "DMA pipeline shape"); \
         ISSUE(0, 0)                                                                         \
         ISSUE(min(1, (NT_) - 1), 1)                                                         \
         for (int kt0_ = 0; kt0_ < (NT_); kt0_ += (U_)) {                                    \
-            _Pragma("unroll") for (int d_ = 0; d_ < (U_); ++d_) {                           \
-                const int kt_ = kt0_ + d_;                                                  \
-                if (kt_ < (NT_)) {                                                          \
-                    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   /* this wave's share of tile kt has landed */ \
-                    __builtin_amdgcn_s_barrier();                      /* everybody's has; buffer (kt + 2) % 3 is free */ \
-                    ISSUE(min(kt_ + 2, (NT_) - 1), (d_ + 2) % 3)                            \
-                    COMPUTE(kt_, d_ % 3, d_)                                                \
+            _Pragma("unroll") for (int g_ = 0; g_ < (U_) / (G_); ++g_) {                    \
+                if (kt0_ + g_ * (G_) < (NT_)) {                                             \
+                    _Pragma("unroll") for (int e_ = 0; e_ < (G_); ++e_) {                   \
+                        const int d_ = g_ * (G_) + e_, kt_ = kt0_ + d_;                     \
+                        WAIT(d_)                                           /* this wave's share of tile kt has landed */ \
+                        __builtin_amdgcn_s_barrier();                      /* everybody's has; buffer (kt + 2) % 3 is free */ \
+                        ISSUE(min(kt_ + 2, (NT_) - 1), (d_ + 2) % 3)                        \
+                        COMPUTE(kt_, d_ % 3, d_)                                            \
+                    }                                                                       \
                 }                                                                           \
             }                                                                               \
         }                                                                                   \
@@ -138,7 +202,7 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
     unsigned char* sMixed = smem;
     unsigned char* sT1a = sMixed + MIXED_BYTES;           // [4 slices][8 x 14 pixels][64 B]
     unsigned char* sT1b = sT1a + PATCH_BYTES;             // [4 slices][14 x 8 pixels][64 B]
-    unsigned char* sStage = sT1b + PATCH_BYTES;           // [2][STAGE_BYTES]
+    unsigned char* sStage = sT1b + PATCH_BYTES;           // [3][STAGE_BYTES] (LDS-DMA) or [2][STAGE_BYTES] (register ring); stages 2-4 of the DMA form: [3][DMA_BUF]
     float* sC = reinterpret_cast<float*>(sT1a);           // stage 4: fp32 C tile [64][132] over the (dead) patches
 
     // 8 waves = 2 per SIMD (a wave alone on its SIMD cannot overlap its LDS / barrier waits with anything): wave = (row half wh,
@@ -150,6 +214,7 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
         warm_range(a.warm, a.warm_bytes, img - a.N, 512);
         return;
     }
+    FN_PH_INIT(0)
     const unsigned short* xin = a.x + (long)img * NPIX * C;
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(xin), 0, NPIX * C * 2, 0x00020000);
 
@@ -167,6 +232,11 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the folded biases of this lane's channels, requested before the k loop (they are cold: a full memory round trip)
+        f32x4 bias[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bias[j] = load_bias4((wq < 2 ? a.b_t0 : a.b_t1a) + (wq & 1) * 64 + j * 16 + fq * 4);
+        FN_PH(1)
         u32x4 ra[D], rb[D][2];
         const int voff = (lrow * C + lch * 8) * 2;                  // row lrow of either weight matrix
         const int voff_x = ((lrow & 63) * C + lch * 8) * 2;         // trunk pixel (both thread halves load it, the lower half stores it)
@@ -191,33 +261,49 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
             _Pragma("unroll") for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const vec8*>(sStage + (buf) * STAGE_BYTES + fa_off[i]); \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + (buf) * STAGE_BYTES + fb_off[j]); \
             _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                  \
-                _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);            \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa[i], acc[i][j]);            \
         }
-        FN_RING_PIPELINE(D, C / 32, S1_LOAD, S1_STORE, S1_COMPUTE)
+        if constexpr (DMA) {
+            // LDS-DMA form: three 20 KB buffers (tile kt in buffer kt % 3).  A 1 KiB wave instruction carries 16 rows of 64 bytes,
+            // the swz64 chunk XOR applied to the per-lane source address: wave w brings slab rows 32 w .. 32 w + 31 (two
+            // instructions: w_t0 for w < 4, w_t1a above) and, for w < 4, trunk pixels 16 w .. 16 w + 15 (a third), so the
+            // counted wait leaves three requests pending in waves 0-3 and two in waves 4-7.
+            const int wv = __builtin_amdgcn_readfirstlane(wave);          // the wave index in an SGPR: descriptor choice and wait count are scalar
+            const int drow = lane >> 2, dchunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);
+            const __amdgpu_buffer_rsrc_t rs_wd = wv < 4 ? rs_w0 : rs_w1;
+            const int dma_voff_w = (((wv & 3) * 32 + drow) * C + dchunk * 8) * 2, dma_voff_x = ((wv * 16 + drow) * C + dchunk * 8) * 2;
+#define S1_DMA_WAIT(d)                                                                                                    \
+            if (wv < 4) { asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); } else { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
+#define S1_DMA_ISSUE(kt, buf)                                                                                             \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                  \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_wd, (lds_ptr)(sStage + (buf) * STAGE_BYTES + 4096 + (wv * 2 + q) * 1024), 16, \
+                                                         dma_voff_w + q * 16 * C * 2, (kt) * 64, 0, 0);                    \
+            if (wv < 4)                                                                                                  \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_ptr)(sStage + (buf) * STAGE_BYTES + wv * 1024), 16, dma_voff_x, (kt) * 64, 0, 0);
+            FN_DMA_PIPELINE(12, 4, C / 32, S1_DMA_WAIT, S1_DMA_ISSUE, S1_COMPUTE)
+#undef S1_DMA_WAIT
+#undef S1_DMA_ISSUE
+        } else {
+            FN_RING_PIPELINE(D, C / 32, S1_LOAD, S1_STORE, S1_COMPUTE)
+        }
 #undef S1_LOAD
 #undef S1_STORE
 #undef S1_COMPUTE
+        FN_PH(2)
         // epilogue: column quarters 0,1 hold t0 (-> mixed slices 0..3), quarters 2,3 hold t1a (-> the 8 x 14 patch, interior columns 3..10)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int col = (wq & 1) * 64 + j * 16 + fr;            // channel within t0 / t1a
-            const float bias = wq < 2 ? a.b_t0[col] : a.b_t1a[col];
-            const int slice = col >> 5, cc = col & 31;
+            const int slice = (wq & 1) * 2 + (j >> 1), sub = ((j & 1) * 2 + (fq >> 1)), byte = (fq & 1) * 8;     // channels 16 j + 4 fq .. + 3 of t0 / t1a
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int p = wh * 32 + i * 16 + fq * 4 + r;   // pixel (y, x) = (p >> 3, p & 7)
-                    const unsigned short h = LP<T>::from_f32(fmaxf(acc[i][j][r] + bias, 0.f));
-                    if (wq < 2) {
-                        *reinterpret_cast<unsigned short*>(sMixed + slice * (NPIX * 64) + swz64(p, cc >> 3) + (cc & 7) * 2) = h;
-                    } else {
-                        const int pidx = (p >> 3) * 14 + (p & 7) + 3;
-                        *reinterpret_cast<unsigned short*>(sT1a + slice * (PATCH_PIX * 64) + swz64(pidx, cc >> 3) + (cc & 7) * 2) = h;
-                    }
-                }
+            for (int i = 0; i < 2; ++i) {
+                const int p = wh * 32 + i * 16 + fr;               // pixel (y, x) = (p >> 3, p & 7)
+                const u32x2 h = pack4_bias_relu<T>(acc[i][j], bias[j]);
+                if (wq < 2) *reinterpret_cast<u32x2*>(sMixed + slice * (NPIX * 64) + swz64(p, sub) + byte) = h;
+                else *reinterpret_cast<u32x2*>(sT1a + slice * (PATCH_PIX * 64) + swz64((p >> 3) * 14 + (p & 7) + 3, sub) + byte) = h;
+            }
         }
         __syncthreads();
+        FN_PH(3)
     }
 
     // Stages 2-4 stream slabs of [128 columns][64 input channels]: 128-byte rows, 16-byte chunk XOR (row & 7) (the implicit-GEMM
@@ -259,6 +345,9 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
                 const int base = stage == 2 ? (p >> 3) * 14 + (p & 7) : p;      // 7x1: pixel (y, x) at tap t is row y + t of the 14 x 8 patch
                 fa_off[t][i] = swz64(base + t * tstep, fq);
             }
+        f32x4 bias[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bias[j] = load_bias4(bias_p + wq * 32 + j * 16 + fq * 4);
         u32x4 rb[D][2];
         const int voff = (srow * (7 * CT) + sch * 8) * 2;
         // k tile kt = (tap, half): input channels 64 * half .. + 63 of tap kt >> 1.  The tile loop is unrolled by D = 4 from
@@ -274,7 +363,7 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
                 fa[i] = *reinterpret_cast<const vec8*>(src + ((half) * 2 + h) * (PATCH_PIX * 64) + fa_off[TAP][i]);              \
             _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + (buf) * STAGE_BYTES + fb_off[h][j]); \
             _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                        \
-                _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);                  \
+                _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa[i], acc[i][j]);                  \
         }
 #define S23_COMPUTE(kt, buf, d)                                                                                                  \
         {                                                                                                                        \
@@ -300,7 +389,7 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
                     fa[i] = *reinterpret_cast<const vec8*>(src + ((half) * 2 + h) * (PATCH_PIX * 64) + fa_off[TAP][i]);          \
                 _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = S23_DMA_FB(buf, h, j);                                     \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                    \
-                    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);              \
+                    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa[i], acc[i][j]);              \
             }
 #define S23_DMA_COMPUTE(kt, buf, d)                                                                                              \
             {                                                                                                                    \
@@ -315,7 +404,7 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
                 const int r = wave * 16 + 8 * q + (lane >> 3), cs = (lane & 7) ^ (r & 7);
                 dma_voff23[q] = (r * (7 * CT) + cs * 8) * 2;
             }
-            FN_DMA_PIPELINE(6, 14, S23_DMA_ISSUE, S23_DMA_COMPUTE)
+            FN_DMA_PIPELINE(6, 2, 14, FN_DMA_WAIT2, S23_DMA_ISSUE, S23_DMA_COMPUTE)
 #undef S23_DMA_ISSUE
 #undef S23_DMA_FB
 #undef S23_DMA_TAP
@@ -326,27 +415,27 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
 #undef S23_LOAD
 #undef S23_TAP
 #undef S23_COMPUTE
+        FN_PH(stage * 2)
         // 1x7 output -> 14 x 8 patch (rows 3..10); 7x1 output -> mixed slices 4..7
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int col = wq * 32 + j * 16 + fr;
-            const float bias = bias_p[col];
-            const int slice = col >> 5, cc = col & 31;
+            const int sub = j * 2 + (fq >> 1), byte = (fq & 1) * 8;      // channels 32 wq + 16 j + 4 fq .. + 3: slice wq
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int p = wh * 32 + i * 16 + fq * 4 + r;
-                    const unsigned short h = LP<T>::from_f32(fmaxf(acc[i][j][r] + bias, 0.f));
-                    if (stage == 2) *reinterpret_cast<unsigned short*>(sT1b + slice * (PATCH_PIX * 64) + swz64(p + 24, cc >> 3) + (cc & 7) * 2) = h;
-                    else *reinterpret_cast<unsigned short*>(sMixed + (4 + slice) * (NPIX * 64) + swz64(p, cc >> 3) + (cc & 7) * 2) = h;
-                }
+            for (int i = 0; i < 2; ++i) {
+                const int p = wh * 32 + i * 16 + fr;
+                const u32x2 h = pack4_bias_relu<T>(acc[i][j], bias[j]);
+                if (stage == 2) *reinterpret_cast<u32x2*>(sT1b + wq * (PATCH_PIX * 64) + swz64(p + 24, sub) + byte) = h;
+                else *reinterpret_cast<u32x2*>(sMixed + (4 + wq) * (NPIX * 64) + swz64(p, sub) + byte) = h;
+            }
         }
         __syncthreads();
+        FN_PH(stage * 2 + 1)
     }
 
     // ---------------- stage 4: out = act(x + scale * (mixed[64 x 256] * Wup[256 x 896] + bias)), 7 passes of 128 columns ----------------
-    // ONE pipeline over the 7 x 4 k tiles (the weight stream does not restart per pass); the pass epilogue runs inside the tile loop
+    // ONE pipeline over the 7 x 4 k tiles (the weight stream does not restart per pass); the pass epilogue runs inside the tile loop.
+    // What the epilogue of a pass reads from memory -- this thread's two residual chunks and its eight b_up values -- is requested
+    // at the pass's FIRST k tile, through the descriptor of image `img`, and has three k tiles to arrive.
     {
         constexpr int CLD = 132;
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w_up), 0, C * 256 * 2, 0x00020000);
@@ -356,50 +445,63 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
 #pragma unroll
         for (int i = 0; i < 2; ++i) fa_off[i] = swz64(wh * 32 + i * 16 + fr, fq);
         f32x4 acc[2][2];
-        // k tile kt = (pass, kk): columns 128 pass .. + 127, input channels 64 kk .. + 63 of mixed (slices 2 kk, 2 kk + 1); kk == d
-#define S4_LOAD(kt, d)                                                                                                           \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                            \
-            rb[d][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, voff + 64 * q * 256 * 2, ((((kt) >> 2) * 128) * 256 + ((kt) & 3) * 64) * 2, 0);
-#define S4_COMPUTE(kt, buf, d)                                                                                                   \
+        // epilogue role: pixel ep_p (+ 32 q), column group ep_cg of 8: 64 pixels x 16 groups = 1024 chunks, two per thread
+        const int ep_p = tid >> 4, ep_cg = tid & 15;
+        const int voff_res = (ep_p * C + ep_cg * 8) * 2;
+        u32x4 rres[2];
+        f32x4 bup[2];
+#define S4_PREFETCH(pass)                                                                                                        \
         {                                                                                                                        \
-            if ((d) == 0) {                                                                                                      \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                        \
+                rres[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, voff_res + q * 32 * C * 2, (pass) * 128 * 2, 0);           \
+            bup[0] = *reinterpret_cast<const f32x4*>(a.b_up + (pass) * 128 + ep_cg * 8);                                         \
+            bup[1] = *reinterpret_cast<const f32x4*>(a.b_up + (pass) * 128 + ep_cg * 8 + 4);                                     \
+        }
+#define S4_MULTIPLY(kk, SLAB)                                                                                                    \
+        {                                                                                                                        \
+            if ((kk) == 0) {                                                                                                     \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                    \
                     _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};                         \
             }                                                                                                                    \
             _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                                      \
                 vec8 fa[2], fb[2];                                                                                               \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                    \
-                    fa[i] = *reinterpret_cast<const vec8*>(sMixed + ((d) * 2 + h) * (NPIX * 64) + fa_off[i]);                    \
-                _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + (buf) * STAGE_BYTES + fb_off[h][j]); \
+                    fa[i] = *reinterpret_cast<const vec8*>(sMixed + ((kk) * 2 + h) * (NPIX * 64) + fa_off[i]);                   \
+                _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>((SLAB) + fb_off[h][j]);     \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                    \
-                    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);              \
-            }                                                                                                                    \
-            if ((d) == 3) {   /* pass complete: fp32 C tile (over the dead patches) -> coalesced residual epilogue */              \
-                const int pass = (kt) >> 2;                                                                                      \
-                _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                    \
-                    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                \
-                        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                            \
-                            sC[(wh * 32 + i * 16 + fq * 4 + r) * CLD + wq * 32 + j * 16 + fr] = acc[i][j][r];                            \
-                __syncthreads();                                                                                                 \
-                _Pragma("unroll") for (int q = 0; q < 2; ++q) {   /* 64 pixels x 16 column groups of 8 = 1024 chunks */           \
-                    const int idx = tid + 512 * q, p = idx >> 4, cg = idx & 15;                                                  \
-                    const int col = pass * 128 + cg * 8;                                                                         \
-                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8]);                                     \
-                    const f32x4 c1 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8 + 4]);                                 \
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.b_up + col), b1 = *reinterpret_cast<const f32x4*>(a.b_up + col + 4); \
-                    float rv[8], v[8];                                                                                           \
-                    unpack8<T>(load_global_b128(xin, (long)p * C + col), rv);                                                    \
-                    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                              \
-                        v[e] = rv[e] + a.scale * (c0[e] + b0[e]);                                                                \
-                        v[4 + e] = rv[4 + e] + a.scale * (c1[e] + b1[e]);                                                        \
-                    }                                                                                                            \
-                    if (a.relu) {                                                                                                \
-                        _Pragma("unroll") for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);                                   \
-                    }                                                                                                            \
-                    *reinterpret_cast<u32x4*>(a.y + ((long)img * NPIX + p) * C + col) = pack8<T>(v);                             \
-                }                                                                                                                \
+                    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa[i], acc[i][j]);              \
             }                                                                                                                    \
         }
+        /* pass complete: fp32 C tile (over the dead patches, one 16-byte store per fragment) -> coalesced residual epilogue */
+#define S4_PASS_EPILOGUE(pass, BARRIER)                                                                                          \
+        {                                                                                                                        \
+            FN_PH(8)                                                                                                             \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                        \
+                _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                    \
+                    *reinterpret_cast<f32x4*>(&sC[(wh * 32 + i * 16 + fr) * CLD + wq * 32 + j * 16 + fq * 4]) = acc[i][j];       \
+            BARRIER                                                                                                              \
+            FN_PH(9)                                                                                                             \
+            FN_PH_WAIT(8)         /* younger than the pass prefetch: six tile instructions and thread 0's two stamps */          \
+            FN_PH(10)                                                                                                            \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                                      \
+                const int pp = ep_p + 32 * q, col = (pass) * 128 + ep_cg * 8;                                                    \
+                const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sC[pp * CLD + ep_cg * 8]);                                     \
+                const f32x4 c1 = *reinterpret_cast<const f32x4*>(&sC[pp * CLD + ep_cg * 8 + 4]);                                 \
+                const f32x4 b0 = bup[0], b1 = bup[1];                                                                            \
+                float rv[8], v[8];                                                                                               \
+                unpack8<T>(rres[q], rv);                                                                                         \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                                  \
+                    v[e] = rv[e] + a.scale * (c0[e] + b0[e]);                                                                    \
+                    v[4 + e] = rv[4 + e] + a.scale * (c1[e] + b1[e]);                                                            \
+                }                                                                                                                \
+                if (a.relu) {                                                                                                    \
+                    _Pragma("unroll") for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);                                       \
+                }                                                                                                                \
+                *reinterpret_cast<u32x4*>(a.y + ((long)img * NPIX + pp) * C + col) = pack8<T>(v);                                \
+            }                                                                                                                    \
+            FN_PH(11)                                                                                                            \
+        }
+        // k tile kt = (pass, kk): columns 128 pass .. + 127, input channels 64 kk .. + 63 of mixed (slices 2 kk, 2 kk + 1)
         if constexpr (DMA) {
             // unrolled by 12 from multiples of 12: buffer = d % 3, kk = d & 3
             int dma_voff4[2];
@@ -408,59 +510,41 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
                 const int r = wave * 16 + 8 * q + (lane >> 3), cs = (lane & 7) ^ (r & 7);
                 dma_voff4[q] = (r * 256 + cs * 8) * 2;
             }
+            // the wait after a pass's first tile: its four prefetch requests are younger than both tiles in flight
+#define S4_DMA_WAIT(d)                                                                                                           \
+            if (((d) & 3) == 1) { asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); } else { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
 #define S4_DMA_ISSUE(kt, buf)                                                                                                    \
             _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                        \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr)(sStage + (buf) * DMA_BUF + (wave * 16 + 8 * q) * 128), 16,   \
                                                          dma_voff4[q], ((((kt) >> 2) * 128) * 256 + ((kt) & 3) * 64) * 2, 0, 0);
 #define S4_DMA_COMPUTE(kt, buf, d)                                                                                               \
             {                                                                                                                    \
-                if (((d) & 3) == 0) {                                                                                            \
-                    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                \
-                        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};                     \
-                }                                                                                                                \
-                _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                                  \
-                    vec8 fa[2], fb[2];                                                                                           \
-                    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                \
-                        fa[i] = *reinterpret_cast<const vec8*>(sMixed + (((d) & 3) * 2 + h) * (NPIX * 64) + fa_off[i]);          \
-                    _Pragma("unroll") for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + (buf) * DMA_BUF + fb_off[h][j]); \
-                    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                \
-                        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa[i], fb[j], acc[i][j]);          \
-                }                                                                                                                \
-                if (((d) & 3) == 3) {                                                                                            \
-                    const int pass = (kt) >> 2;                                                                                  \
-                    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                \
-                        _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                            \
-                            _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                        \
-                                sC[(wh * 32 + i * 16 + fq * 4 + r) * CLD + wq * 32 + j * 16 + fr] = acc[i][j][r];                \
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-                    __builtin_amdgcn_s_barrier();                                                                                \
-                    _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                              \
-                        const int idx = tid + 512 * q, p = idx >> 4, cg = idx & 15;                                              \
-                        const int col = pass * 128 + cg * 8;                                                                     \
-                        const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8]);                                 \
-                        const f32x4 c1 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8 + 4]);                             \
-                        const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.b_up + col), b1 = *reinterpret_cast<const f32x4*>(a.b_up + col + 4); \
-                        float rv[8], v[8];                                                                                       \
-                        unpack8<T>(load_global_b128(xin, (long)p * C + col), rv);                                                \
-                        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                          \
-                            v[e] = rv[e] + a.scale * (c0[e] + b0[e]);                                                            \
-                            v[4 + e] = rv[4 + e] + a.scale * (c1[e] + b1[e]);                                                    \
-                        }                                                                                                        \
-                        if (a.relu) {                                                                                            \
-                            _Pragma("unroll") for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);                               \
-                        }                                                                                                        \
-                        *reinterpret_cast<u32x4*>(a.y + ((long)img * NPIX + p) * C + col) = pack8<T>(v);                         \
-                    }                                                                                                            \
-                }                                                                                                                \
+                if (((d) & 3) == 0) S4_PREFETCH((kt) >> 2)                                                                       \
+                S4_MULTIPLY((d) & 3, sStage + (buf) * DMA_BUF)                                                                   \
+                if (((d) & 3) == 3)                                                                                              \
+                    S4_PASS_EPILOGUE((kt) >> 2, asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier();) \
             }
-            FN_DMA_PIPELINE(12, 28, S4_DMA_ISSUE, S4_DMA_COMPUTE)
+            FN_DMA_PIPELINE(12, 4, 28, S4_DMA_WAIT, S4_DMA_ISSUE, S4_DMA_COMPUTE)
+#undef S4_DMA_WAIT
 #undef S4_DMA_ISSUE
 #undef S4_DMA_COMPUTE
         } else {
+#define S4_LOAD(kt, d)                                                                                                           \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                        \
+                rb[d][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, voff + 64 * q * 256 * 2, ((((kt) >> 2) * 128) * 256 + ((kt) & 3) * 64) * 2, 0);
+#define S4_COMPUTE(kt, buf, d)                          /* D = 4: kk == d */                                                      \
+            {                                                                                                                    \
+                if ((d) == 0) S4_PREFETCH((kt) >> 2)                                                                             \
+                S4_MULTIPLY(d, sStage + (buf) * STAGE_BYTES)                                                                     \
+                if ((d) == 3) S4_PASS_EPILOGUE((kt) >> 2, __syncthreads();)                                                      \
+            }
             FN_RING_PIPELINE(D, 28, S4_LOAD, SLAB_STORE, S4_COMPUTE)
-        }
 #undef S4_LOAD
 #undef S4_COMPUTE
+        }
+#undef S4_PREFETCH
+#undef S4_MULTIPLY
+#undef S4_PASS_EPILOGUE
     }
 #undef SLAB_STORE
 }
@@ -474,7 +558,8 @@ __global__ __launch_bounds__(512) void block17_infer_kernel(const Block17Args a)
 // stays in LDS.  One workgroup (8 waves) per image: 289 pixels = 19 row fragments, wave w owns fragments w, w+8, w+16 and ALL
 // columns of a stage (the stages are only 32 .. 96 columns wide).  Activations: 64-byte pixel rows per 32-channel slice
 // (swz64); the 3x3 inputs are kept as 19 x 19 patches with a 1-pixel zero halo, so the nine taps are nine shifted views.
-// The weights of a stage (<= 48 KB) are staged in LDS in one piece; only the trunk of stage 1 streams (ring pipeline).
+// The weights of a stage (<= 48 KB) are staged in LDS in one piece, by LDS-DMA while the stage before multiplies; only the trunk
+// of stage 1 streams (ring pipeline).  mfma(weights, pixels) as in Block17: 8-byte tower stores, 16-byte C-tile stores.
 // ------------------------------------------------------------------------------------------------------------------------
 struct Block35Args {
     const unsigned short* x;       // [N, 17, 17, 256]
@@ -499,13 +584,15 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
     constexpr int PATCH_PIX = 19 * 19, PATCH_BYTES = (PATCH_PIX * 64 + 1023) / 1024 * 1024 + 1024;   // reads of padded rows stay inside
     constexpr int MIXED_BYTES = 3 * SLICE_BYTES;                     // t0 | t1 | t2
     constexpr int STAGE_BYTES = SLICE_BYTES + 96 * 64;               // stage 1: trunk slice + slab [96 columns][64 B]
+    static_assert(9 * 32 * 64 <= SLICE_BYTES && 3 * 256 * 64 <= 2 * STAGE_BYTES && MROWS * 36 * 4 <= 2 * PATCH_BYTES, "block35 LDS plan");
     typedef typename LP<T>::vec8 vec8;
+    typedef __attribute__((address_space(3))) void* lds_ptr;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sMixed = smem;
     unsigned char* sP1 = sMixed + MIXED_BYTES;
     unsigned char* sP2 = sP1 + PATCH_BYTES;
-    unsigned char* sStage = sP2 + PATCH_BYTES;            // [2][STAGE_BYTES]; later: the weights of a stage in one piece
+    unsigned char* sStage = sP2 + PATCH_BYTES;            // [2][STAGE_BYTES] in stage 1; later the 3x3 slab of stage 2b, then w_up in one piece
     float* sC = reinterpret_cast<float*>(sP1);            // stage 4: fp32 C tile [304][36] over the (dead) patches
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -518,34 +605,52 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
     const unsigned short* xin = a.x + (long)img * NPIX * C;
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(xin), 0, NPIX * C * 2, 0x00020000);
     constexpr unsigned OOB = 0x60000000u;
+    FN_PH_INIT(1)
+
+    // Weights of stages 2a .. 4 go global -> LDS by LDS-DMA (1 KiB per wave instruction: 16 slab rows of 64 bytes, the chunk XOR of
+    // swz64 applied to the per-lane SOURCE address), each stage's slab requested while the stage before it multiplies:
+    //   3x3 of 2a -> mixed slice 2 (dead until stage 3 writes it), at kernel entry;   3x3 of 2b -> sStage, during 2a;
+    //   3x3 of 3  -> mixed slice 2 again, during 2b;                                   w_up (48 KB) -> sStage, during 3.
+    // The wave that asked waits (vmcnt(0)) before the barrier that ends the stage before the slab's first use.
+    const int dma_row = lane >> 2, dma_chunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);      // row within the 16, source chunk of slot lane & 3
+    auto dma_w3x3 = [&](unsigned char* dst, const unsigned short* w) {                     // slab rows = tap * 32 + column, 18 instructions
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(w), 0, 32 * 288 * 2, 0x00020000);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int n = wave + 8 * k;
+            if (n < 18) {
+                const int r = n * 16 + dma_row;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(dst + n * 1024), 16, ((r & 31) * 288 + (r >> 5) * 32 + dma_chunk * 8) * 2, 0, 0, 0);
+            }
+        }
+    };
+    auto dma_wup = [&](unsigned char* dst) {                                               // slab rows = slice * 256 + column, 48 instructions
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w_up), 0, 256 * 96 * 2, 0x00020000);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const int n = wave + 8 * k, r = n * 16 + dma_row;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(dst + n * 1024), 16, ((r & 255) * 96 + (r >> 8) * 32 + dma_chunk * 8) * 2, 0, 0, 0);
+        }
+    };
+    unsigned char* const sW3 = sMixed + 2 * SLICE_BYTES;
+    dma_w3x3(sW3, a.w_3x3[0]);
 
     for (int i = tid; i < 2 * PATCH_BYTES / 16; i += 512) reinterpret_cast<u32x4*>(sP1)[i] = u32x4{0u, 0u, 0u, 0u};
 
-    // row fragments of this wave: f = wave + 8 i, i < 3, valid while f < 19 (wave-uniform)
+    // row fragments of this wave: f = wave + 8 i, i < 3, valid while f < 19 (wave-uniform).  With mfma(weights, pixels) lane (fr, fq)
+    // holds channels 4 fq .. + 3 of pixel prow[i] of every fragment: one pixel index per fragment, computed here once.
     const int nfr = wave < 3 ? 3 : 2;
-    int prow[3];          // first pixel of each fragment's lane (row = lane & 15)
+    int prow[3], ppatch[3];          // this lane's pixel of each fragment, and its index in a 19 x 19 patch
 #pragma unroll
-    for (int i = 0; i < 3; ++i) prow[i] = (wave + 8 * i) * 16 + fr;
-
-    // cooperative copy of a [rows][32 channels] weight block (64-byte rows in global, row stride `gstride` elements) into LDS
-    auto stage_weights = [&](unsigned char* dst, const unsigned short* w, int rows, int gstride, int goff) {
-        for (int i = tid; i < rows * 4; i += 512) {
-            const int r = i >> 2, ch = i & 3;
-            *reinterpret_cast<u32x4*>(dst + swz64(r, ch)) = load_global_b128(w, (long)r * gstride + goff + ch * 8);
-        }
-    };
-    // relu(acc + bias) -> LDS image: pixel p at index pidx(p) of `region` (slice base), channel c (0..31); C layout of the 16x16 MFMA
-    auto store_frag = [&](const f32x4& v, float bias, unsigned char* region, int frag, int col, bool patch) {
-        const int cc = col & 31;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int p = frag * 16 + fq * 4 + r;
-            if (p < NPIX) {
-                const int y = p / 17, x = p - y * 17;
-                const int pidx = patch ? (y + 1) * 19 + x + 1 : p;
-                *reinterpret_cast<unsigned short*>(region + swz64(pidx, cc >> 3) + (cc & 7) * 2) = LP<T>::from_f32(fmaxf(v[r] + bias, 0.f));
-            }
-        }
+    for (int i = 0; i < 3; ++i) {
+        prow[i] = (wave + 8 * i) * 16 + fr;
+        const int y = prow[i] / 17, x = prow[i] - y * 17;
+        ppatch[i] = (y + 1) * 19 + x + 1;
+    }
+    // relu(acc + bias) of fragment i, 16-column fragment j -> LDS image `region` (slice base): one 8-byte store
+    auto store_frag = [&](const f32x4& v, const f32x4& bias, unsigned char* region, int i, int j, bool patch) {
+        if (prow[i] < NPIX)
+            *reinterpret_cast<u32x2*>(region + swz64(patch ? ppatch[i] : prow[i], (j & 1) * 2 + (fq >> 1)) + (fq & 1) * 8) = pack4_bias_relu<T>(v, bias);
     };
 
     // ---------------- stage 1: [t0 | t1a | t2a] = relu(x[289 x 256] * W[256 x 96] + b): trunk slices stream, 8 k tiles of 32 channels ----------------
@@ -566,6 +671,10 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
         const int wr = tid >> 2, wch = tid & 3;                     // slab row (column of the stage) 0..95 for tid < 384
         const unsigned short* wrow = a.w_1x1[min(wr >> 5, 2)] + (long)(wr & 31) * C + wch * 8;
         const int st_b = wr < 96 ? SLICE_BYTES + swz64(wr, wch) : -1;
+        f32x4 bias[6];               // the folded biases of this lane's channels, requested before the k loop
+#pragma unroll
+        for (int j = 0; j < 6; ++j) bias[j] = load_bias4(a.b_1x1[j >> 1] + (j & 1) * 16 + fq * 4);
+        FN_PH(1)
 #define S1_LOAD(kt, d)                                                                                     \
         _Pragma("unroll") for (int q = 0; q < 3; ++q) ra[d][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, voff_a[q], (kt) * 64, 0); \
         rb[d] = load_global_b128(wrow, (kt) * 32);
@@ -581,26 +690,27 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
             _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                                  \
                 if (i < nfr) {                                                                                             \
                     const vec8 fa = *reinterpret_cast<const vec8*>(pa + swz64(prow[i], fq));                               \
-                    _Pragma("unroll") for (int j = 0; j < 6; ++j) acc[i][j] = LP<T>::mfma(fa, fb[j], acc[i][j]);           \
+                    _Pragma("unroll") for (int j = 0; j < 6; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa, acc[i][j]);           \
                 }                                                                                                          \
         }
         FN_RING_PIPELINE(D, C / 32, S1_LOAD, S1_STORE, S1_COMPUTE)
 #undef S1_LOAD
 #undef S1_STORE
 #undef S1_COMPUTE
+        FN_PH(2)
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            const int col = j * 16 + fr, t = col >> 5;               // tower 0 -> mixed slice 0, towers 1, 2 -> patches P1, P2
-            const float bias = a.b_1x1[t][col & 31];
+            const int t = j >> 1;                                    // tower 0 -> mixed slice 0, towers 1, 2 -> patches P1, P2
             unsigned char* region = t == 0 ? sMixed : (t == 1 ? sP1 : sP2);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-                if (i < nfr) store_frag(acc[i][j], bias, region, wave + 8 * i, col, t != 0);
+                if (i < nfr) store_frag(acc[i][j], bias[j], region, i, j, t != 0);
         }
         __syncthreads();
+        FN_PH(3)
     }
 
-    // ---------------- stages 2a, 2b, 3: 3x3 32 -> 32 from a 19 x 19 patch; weights [32][9][32] staged whole (18 KB) ----------------
+    // ---------------- stages 2a, 2b, 3: 3x3 32 -> 32 from a 19 x 19 patch; weights [32][9][32] (18 KB) already in LDS ----------------
     int fa_tap[9][3];          // LDS offset of this lane's A fragment i at tap t
 #pragma unroll
     for (int t = 0; t < 9; ++t)
@@ -614,11 +724,14 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
     for (int c3 = 0; c3 < 3; ++c3) {
         // c3 = 0: t1b = 3x3(P1) -> mixed slice 1; c3 = 1: t2b = 3x3(P2) -> P1 (its reader is done); c3 = 2: t2c = 3x3(P1) -> mixed slice 2
         const unsigned char* src = c3 == 1 ? sP2 : sP1;
-        for (int i = tid; i < 9 * 32 * 4; i += 512) {                // slab rows = tap * 32 + column
-            const int r = i >> 2, ch = i & 3, tap = r >> 5, co = r & 31;
-            *reinterpret_cast<u32x4*>(sStage + swz64(r, ch)) = load_global_b128(a.w_3x3[c3], (long)co * 288 + tap * 32 + ch * 8);
-        }
-        __syncthreads();
+        const unsigned char* wsl = c3 == 1 ? sStage : sW3;          // this stage's slab
+        f32x4 bias[2];               // requested first: requests retire in order, the epilogue must not wait for the slab behind them
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bias[j] = load_bias4(a.b_3x3[c3] + j * 16 + fq * 4);
+        if (c3 == 0) dma_w3x3(sStage, a.w_3x3[1]);                   // the next stage's slab, into what the stage before this one left dead
+        else if (c3 == 1) dma_w3x3(sW3, a.w_3x3[2]);
+        else dma_wup(sStage);
+        FN_PH(4 + 3 * c3)
         f32x4 acc[3][2];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -628,86 +741,99 @@ __global__ __launch_bounds__(512) void block35_infer_kernel(const Block35Args a)
         for (int t = 0; t < 9; ++t) {
             vec8 fb[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + swz64(t * 32 + j * 16 + fr, fq));
+            for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(wsl + swz64(t * 32 + j * 16 + fr, fq));
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 if (i < nfr) {
                     const vec8 fa = *reinterpret_cast<const vec8*>(src + fa_tap[t][i]);
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa, fb[j], acc[i][j]);
+                    for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa, acc[i][j]);
                 }
         }
-        __syncthreads();                                             // everybody is done reading src before P1 is overwritten (c3 = 1)
+        __syncthreads();                                             // everybody is done reading src and the slab before P1 / mixed slice 2 is overwritten
+        FN_PH(5 + 3 * c3)
+        unsigned char* region = c3 == 0 ? sMixed + SLICE_BYTES : (c3 == 1 ? sP1 : sMixed + 2 * SLICE_BYTES);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 16 + fr;
-            const float bias = a.b_3x3[c3][col];
-            unsigned char* region = c3 == 0 ? sMixed + SLICE_BYTES : (c3 == 1 ? sP1 : sMixed + 2 * SLICE_BYTES);
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-                if (i < nfr) store_frag(acc[i][j], bias, region, wave + 8 * i, col, c3 == 1);
-        }
+                if (i < nfr) store_frag(acc[i][j], bias[j], region, i, j, c3 == 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's share of the next slab has landed
         __syncthreads();
+        FN_PH(6 + 3 * c3)
     }
 
-    // ---------------- stage 4: out = act(x + scale * (mixed[289 x 96] * Wup[96 x 256] + bias)); weights staged whole (48 KB), 8 passes of 32 columns ----------------
+    // ---------------- stage 4: out = act(x + scale * (mixed[289 x 96] * Wup[96 x 256] + bias)); weights whole in sStage (48 KB), 8 passes of 32 columns ----------------
+    // The residual chunks and b_up values of pass p + 1 are requested before pass p multiplies (two register sets, the pass loop is
+    // unrolled by two); every address is formed through the descriptor of image `img` with a pass index clamped to 7.
     {
         constexpr int CLD = 36;
-        for (int i = tid; i < 3 * 256 * 4; i += 512) {               // slab rows = slice * 256 + column
-            const int r = i >> 2, ch = i & 3, sl = r >> 8, co = r & 255;
-            *reinterpret_cast<u32x4*>(sStage + swz64(r, ch)) = load_global_b128(a.w_up, (long)co * 96 + sl * 32 + ch * 8);
+        const int ep_cg = tid & 3;                                   // 289 pixels x 4 column groups of 8: chunks tid + 512 q
+        int voff_r[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) voff_r[q] = tid + 512 * q < NPIX * 4 ? (((tid + 512 * q) >> 2) * C + ep_cg * 8) * 2 : (int)OOB;
+        u32x4 r0[3], r1[3];
+        f32x4 b0[2], b1[2];
+#define S4_FETCH(pass, R, B)                                                                                              \
+        {                                                                                                                  \
+            _Pragma("unroll") for (int q = 0; q < 3; ++q) R[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, voff_r[q], (pass) * 64, 0); \
+            B[0] = *reinterpret_cast<const f32x4*>(a.b_up + (pass) * 32 + ep_cg * 8);                                      \
+            B[1] = *reinterpret_cast<const f32x4*>(a.b_up + (pass) * 32 + ep_cg * 8 + 4);                                  \
         }
-        __syncthreads();
+#define S4_PASS(pass, RC, BC, RN, BN, next)                                                                               \
+        {                                                                                                                  \
+            S4_FETCH(next, RN, BN)                                                                                         \
+            f32x4 acc[3][2];                                                                                               \
+            _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                                  \
+                _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};                       \
+            _Pragma("unroll") for (int sl = 0; sl < 3; ++sl) {                                                             \
+                vec8 fb[2];                                                                                                \
+                _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                              \
+                    fb[j] = *reinterpret_cast<const vec8*>(sStage + swz64(sl * 256 + (pass) * 32 + j * 16 + fr, fq));      \
+                _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                              \
+                    if (i < nfr) {                                                                                         \
+                        const vec8 fa = *reinterpret_cast<const vec8*>(sMixed + sl * SLICE_BYTES + swz64(prow[i], fq));    \
+                        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fb[j], fa, acc[i][j]);       \
+                    }                                                                                                      \
+            }                                                                                                              \
+            FN_PH(14)                                                                                                      \
+            _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                                  \
+                if (i < nfr) {                                                                                             \
+                    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                          \
+                        *reinterpret_cast<f32x4*>(&sC[prow[i] * CLD + j * 16 + fq * 4]) = acc[i][j];                       \
+                }                                                                                                          \
+            __syncthreads();                                                                                               \
+            FN_PH(15)                                                                                                      \
+            FN_PH_WAIT(7)         /* younger than this pass's chunks: the next pass's five requests and thread 0's two stamps */ \
+            FN_PH(16)                                                                                                      \
+            _Pragma("unroll") for (int q = 0; q < 3; ++q)                                                                  \
+                if (tid + 512 * q < NPIX * 4) {                                                                            \
+                    const int pp = (tid + 512 * q) >> 2, col = (pass) * 32 + ep_cg * 8;                                    \
+                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sC[pp * CLD + ep_cg * 8]);                           \
+                    const f32x4 c1 = *reinterpret_cast<const f32x4*>(&sC[pp * CLD + ep_cg * 8 + 4]);                       \
+                    float rv[8], v[8];                                                                                     \
+                    unpack8<T>(RC[q], rv);                                                                                 \
+                    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                        \
+                        v[e] = rv[e] + a.scale * (c0[e] + BC[0][e]);                                                       \
+                        v[4 + e] = rv[4 + e] + a.scale * (c1[e] + BC[1][e]);                                               \
+                    }                                                                                                      \
+                    if (a.relu) {                                                                                          \
+                        _Pragma("unroll") for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);                             \
+                    }                                                                                                      \
+                    *reinterpret_cast<u32x4*>(a.y + ((long)img * NPIX + pp) * C + col) = pack8<T>(v);                      \
+                }                                                                                                          \
+            __syncthreads();                                                                                               \
+            FN_PH(17)                                                                                                      \
+        }
+        S4_FETCH(0, r0, b0)
+        FN_PH(13)
 #pragma unroll 1
-        for (int pass = 0; pass < 8; ++pass) {
-            f32x4 acc[3][2];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int sl = 0; sl < 3; ++sl) {
-                vec8 fb[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const vec8*>(sStage + swz64(sl * 256 + pass * 32 + j * 16 + fr, fq));
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    if (i < nfr) {
-                        const vec8 fa = *reinterpret_cast<const vec8*>(sMixed + sl * SLICE_BYTES + swz64(prow[i], fq));
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) acc[i][j] = LP<T>::mfma(fa, fb[j], acc[i][j]);
-                    }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if (i < nfr) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sC[((wave + 8 * i) * 16 + fq * 4 + r) * CLD + j * 16 + fr] = acc[i][j][r];
-                }
-            __syncthreads();
-            for (int idx = tid; idx < NPIX * 4; idx += 512) {        // 289 pixels x 4 column groups of 8
-                const int p = idx >> 2, cg = idx & 3;
-                const int col = pass * 32 + cg * 8;
-                const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8]);
-                const f32x4 c1 = *reinterpret_cast<const f32x4*>(&sC[p * CLD + cg * 8 + 4]);
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.b_up + col), b1 = *reinterpret_cast<const f32x4*>(a.b_up + col + 4);
-                float rv[8], v[8];
-                unpack8<T>(load_global_b128(xin, (long)p * C + col), rv);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = rv[e] + a.scale * (c0[e] + b0[e]);
-                    v[4 + e] = rv[4 + e] + a.scale * (c1[e] + b1[e]);
-                }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                *reinterpret_cast<u32x4*>(a.y + ((long)img * NPIX + p) * C + col) = pack8<T>(v);
-            }
-            __syncthreads();
+        for (int pass = 0; pass < 8; pass += 2) {
+            S4_PASS(pass, r0, b0, r1, b1, pass + 1)
+            S4_PASS(pass + 1, r1, b1, r0, b0, min(pass + 2, 7))
         }
+#undef S4_FETCH
+#undef S4_PASS
     }
 }
 
@@ -737,8 +863,9 @@ extern "C" int fn_block17_infer_warm(const void* x, void* y, int N, const void* 
                   (const unsigned short*)w_t1b, (const unsigned short*)w_t1c, (const unsigned short*)w_up, b_t0, b_t1a, b_t1b, b_t1c, b_up,
                   scale, relu, N, (const unsigned char*)warm, (long)warm_bytes};
     const int grid = N + (warm ? WARM_WGS : 0);
-    constexpr size_t smem = 8 * 64 * 64 + 2 * 4 * 112 * 64 + 3 * 16 * 1024;      // staging: 2 x 20 KB (register ring) or 3 x 16 KB (LDS-DMA)
-    static const int use_dma = env_int("FN_B17_DMA", 1);   // measured: stages 2+3 12.4 -> 9.6 us per block (tools/dev_block17.py)
+    constexpr size_t smem = 8 * 64 * 64 + 2 * 4 * 112 * 64 + 3 * 20 * 1024;      // staging: 3 x 20 KB (LDS-DMA, stage 1), 3 x 16 KB (LDS-DMA, stages 2-4), 2 x 20 KB (register ring)
+    static_assert(smem <= 160 * 1024 && 64 * 132 * 4 <= 2 * 4 * 112 * 64, "block17 LDS plan: mixed 32 KB | two patches 56 KB (fp32 C tile over them) | staging 60 KB");
+    static const int use_dma = env_int("FN_B17_DMA", 1);   // measured: stages 2+3 12.4 -> 9.6 us per block (per-stage times: tools/dev_fused_blocks.py)
     static LdsOptIn ok[4];
     const void* kerns[4] = {reinterpret_cast<const void*>(block17_infer_kernel<__bf16, false>), reinterpret_cast<const void*>(block17_infer_kernel<_Float16, false>),
                             reinterpret_cast<const void*>(block17_infer_kernel<__bf16, true>), reinterpret_cast<const void*>(block17_infer_kernel<_Float16, true>)};
