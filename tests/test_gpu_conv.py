@@ -588,6 +588,19 @@ def _tiles(M):
     return (M + 31) // 32 + 4          # workgroups that can add into one column of a fixed-point sum (any tile, parity classes)
 
 
+_MEMO = {}
+
+
+def _memo(key, make):
+    """fp64 references of operands that are a function of `key` alone, shared between the tests that follow each other (the
+    tiles of one layer); a handful are kept."""
+    if key not in _MEMO:
+        while len(_MEMO) >= 8:
+            _MEMO.pop(next(iter(_MEMO)))
+        _MEMO[key] = make()
+    return _MEMO[key]
+
+
 class _Layer:
     """One convolution launch (forward op 0 / data gradient op 1) with its fp64 reference and its checks."""
 
@@ -605,13 +618,15 @@ class _Layer:
 def _fwd_layer(lib, dt, geo, seed, out, c0=0, x=None, x_c0=0, stats=None, bias=False, resid=False, scale=1.0, relu=0, tile=0):
     """out: _Buf receiving channels [c0, c0 + Cout); x: shared input buffer (channels [x_c0, x_c0 + Cin)); stats: (_Acc, offset, replicas)."""
     N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(geo)
-    if x is None:
+    fresh = x is None
+    if fresh:
         x = _mk((N, H, W, Cin), dt, seed=seed)
     w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=seed + 1)
     d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=x.shape[-1], ld_y=out.t.shape[-1])
     d.x, d.w, d.y, d.relu, d.tile_fwd = ptr(x, x_c0), ptr(w), ptr(out.t, c0), relu, tile
     out.claim(c0, Cout)
-    conv, aconv = conv_fp64(x[..., x_c0:x_c0 + Cin], w, s, ph, pw)
+    # operands made here are a function of (geo, dt, seed): their reference is computed once and shared (never modified)
+    conv, aconv = _memo(("fwd", geo, dt, seed), lambda: conv_fp64(x, w, s, ph, pw)) if fresh else conv_fp64(x[..., x_c0:x_c0 + Cin], w, s, ph, pw)
     ref, aref, keep = conv, aconv, [x, w]
     if bias:
         b = (torch.randn(Cout, generator=torch.Generator().manual_seed(seed + 2)) * 0.5).cuda()
@@ -645,27 +660,31 @@ def _fwd_layer(lib, dt, geo, seed, out, c0=0, x=None, x_c0=0, stats=None, bias=F
     return _Layer(0, d, keep, checks, bufs)
 
 
-def _dgrad_layer(lib, dt, geo, seed, out, c0=0, accumulate=0, bn=None, tile=0, siblings=(), rb=None):
+def _dgrad_layer(lib, dt, geo, seed, out, c0=0, accumulate=0, bn=None, tile=0, siblings=(), rb=None, lds=None):
     """out: _Buf receiving dX channels [c0, c0 + Cin); accumulate: dX adds to a random base; bn: (_Acc, offset, replicas, relu)
     for the fused BatchNorm-backward reduction of the layer that produced x; siblings: Cout of the 1x1 sources dy2 / dy3;
-    rb: the fused residual backward (see _fuse_rb)."""
+    rb: the fused residual backward (see _fuse_rb); lds: row strides of dy, dy2, dy3 (each source the first channels of a wider
+    buffer, like the slices of `mixed`; default: contiguous)."""
     N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(geo)
-    dy = _mk((N, OH, OW, Cout), dt, seed=seed)
+    lds = list(lds) if lds else [Cout] + list(siblings)
+    dyb = _mk((N, OH, OW, lds[0]), dt, seed=seed)
+    dy = dyb[..., :Cout]
     w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=seed + 1)
     wt = _pack_t(lib, w, dt)
-    d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=out.t.shape[-1])
-    d.y, d.w, d.dx, d.accumulate, d.tile_dgrad = ptr(dy), ptr(wt), ptr(out.t, c0), accumulate, tile
-    g, ag = dgrad_fp64(dy, w, H, W, s, ph, pw)
-    ref, aref, keep = g, ag, [dy, w, wt]
+    d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=out.t.shape[-1], ld_y=lds[0])
+    d.y, d.w, d.dx, d.accumulate, d.tile_dgrad = ptr(dyb), ptr(wt), ptr(out.t, c0), accumulate, tile
+    g, ag = _memo(("dgrad", geo, dt, seed, lds[0]), lambda: dgrad_fp64(dy, w, H, W, s, ph, pw))
+    ref, aref, keep = g, ag, [dyb, w, wt]
     K = kh * kw * Cout
     for i, c2 in enumerate(siblings):          # sibling 1x1 layers reading the same x: their products join the same GEMM
-        dyi, wi = _mk((N, OH, OW, c2), dt, seed=seed + 10 + i), _mk((c2, 1, 1, Cin), dt, 0.1, seed=seed + 20 + i)
+        dyib, wi = _mk((N, OH, OW, lds[1 + i]), dt, seed=seed + 10 + i), _mk((c2, 1, 1, Cin), dt, 0.1, seed=seed + 20 + i)
+        dyi = dyib[..., :c2]
         wti = _pack_t(lib, wi, dt)
-        setattr(d, ("dy2", "dy3")[i], ptr(dyi)); setattr(d, ("w2", "w3")[i], ptr(wti))
-        setattr(d, ("Cout2", "Cout3")[i], c2); setattr(d, ("ld_y2", "ld_y3")[i], c2)
-        gi, agi = dgrad_fp64(dyi, wi, H, W, 1, 0, 0)
+        setattr(d, ("dy2", "dy3")[i], ptr(dyib)); setattr(d, ("w2", "w3")[i], ptr(wti))
+        setattr(d, ("Cout2", "Cout3")[i], c2); setattr(d, ("ld_y2", "ld_y3")[i], lds[1 + i])
+        gi, agi = _memo(("sibling", geo[:4], c2, dt, seed, i, lds[1 + i]), lambda: dgrad_fp64(dyi, wi, H, W, 1, 0, 0))
         ref, aref, K = ref + gi, aref + agi, K + c2
-        keep += [dyi, wi, wti]
+        keep += [dyib, wi, wti]
     if rb is not None:
         return _fuse_rb(lib, dt, d, out, c0, ref, aref, K, seed, keep, **rb)
     if accumulate:
@@ -1031,3 +1050,147 @@ def test_conv_split_k_variants(lib, bm, bn, ks, c, dt):
         L.check(f"{bm}x{bn} ks {ks} op {L.op}")
         for b in L.bufs:
             b.check_untouched(f"{bm}x{bn} ks {ks} op {L.op}")
+
+
+# ---- element-wise bounds: single launches, the halo-tile kernel, every pinnable tile, sibling sources, normalise-on-load, nrm_z ----
+# The launches the rel_err tests above run, held element by element: outputs start as NaN inside wider bit-patterned buffers
+# (channels [8, 8 + C)), BatchNorm statistics go to 4 replicas at a non-zero column offset, and every test asserts the variant
+# fn_conv2d_variant names for its launch.  (Weight gradients: tests/test_gpu_conv_wgrad.py.)
+
+# fn_conv2d_variant(d, 0) / (d, 1) of CASES under the library heuristic (HALO_CASES: with the halo-tile kernel requested)
+CASE_VARIANTS = [(32032, 32032), (32032, 2032032), (32032, 32032), (2032032, 4032032), (32032, 32032), (32032, 32032), (4032032, 2032032),
+                 (2032032, 2032032), (2032032, 2032032), (2032032, 2032032), (2032032, 2032032), (32032, 4032032), (4032032, 32032),
+                 (9000064, 9000032), (9000064, 9000032), (9000032, 9000032), (9000032, 9000064)]
+NINE_TILES = [128128, 128064, 128032, 64128, 64064, 64032, 32128, 32064, 32032]
+
+
+def _launch_checked(lib, L, what):
+    for b in L.bufs:
+        b.reset()
+    L.launch(lib)
+    torch.cuda.synchronize()
+    L.check(what)
+    for b in L.bufs:
+        b.check_untouched(what)
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("case", CASES)
+def test_conv_single_launches_elementwise(lib, case, dt):
+    """Every layer of CASES as a single launch against fp64, element by element: forward with BatchNorm statistics over four
+    replicas, the data gradient plain and accumulated onto a base; the four HALO_CASES on conv_halo_kernel (tile 9000000), where
+    one wrong border pixel of one tile fails."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(case)
+    tile = HALO if case in HALO_CASES else 0
+    want = CASE_VARIANTS[CASES.index(case)]
+    f = _fwd_layer(lib, dt, case, 800, _Buf((N, OH, OW, Cout + 16), dt), c0=8, stats=(_Acc(4, Cout + 8), 8, 4), tile=tile)
+    g0 = _dgrad_layer(lib, dt, case, 810, _Buf((N, H, W, Cin + 16), dt), c0=8, tile=tile)
+    g1 = _dgrad_layer(lib, dt, case, 810, _Buf((N, H, W, Cin + 16), dt), c0=8, accumulate=1, tile=tile)
+    for L, what in ((f, "forward"), (g0, "dgrad"), (g1, "dgrad, accumulate")):
+        assert lib.fn_conv2d_variant(C.byref(L.d), L.op) == want[L.op]
+        _launch_checked(lib, L, f"{case} {what}")
+
+
+@pytest.mark.parametrize("tile", NINE_TILES)
+@pytest.mark.parametrize("case", TILE_CASES)
+def test_conv_explicit_tiles_elementwise(lib, case, tile):
+    """test_conv_explicit_tiles element by element: every tile a caller may pin, forward with BatchNorm statistics and data
+    gradient, against one fp64 reference per layer."""
+    dt = _lib.FN_BF16
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(case)
+    f = _fwd_layer(lib, dt, case, 820, _Buf((N, OH, OW, Cout + 16), dt), c0=8, stats=(_Acc(4, Cout + 8), 8, 4), tile=tile)
+    g = _dgrad_layer(lib, dt, case, 830, _Buf((N, H, W, Cin + 16), dt), c0=8, tile=tile)
+    for L in (f, g):
+        assert _lib.variant_tile(lib.fn_conv2d_variant(C.byref(L.d), L.op)) == tile          # (+ KS * 1000000: in-launch split-K)
+        _launch_checked(lib, L, f"{case} tile {tile} op {L.op}")
+
+
+@pytest.mark.parametrize("tile", [0, 128064, 64064, 32032, 32128])
+@pytest.mark.parametrize("nsrc", [2, 3])
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+def test_dgrad_sibling_sources_elementwise(lib, dt, nsrc, tile):
+    """The multi-source data gradient of test_dgrad_sibling_sources_equal_the_sum_of_single_dgrads (dY slices of wider buffers,
+    ld_y2 / ld_y3 > Cout, K tails that are no multiples of the 64-wide k tile) element by element against the fp64 sum of the
+    per-layer gradients, plain and accumulated."""
+    N, H, W, Cin = 3, 9, 9, 256
+    couts, lds = [32, 40, 96][:nsrc], [96, 40, 160][:nsrc]
+    for acc in (0, 1):
+        L = _dgrad_layer(lib, dt, (N, H, W, Cin, couts[0], 1, 1, 1, 0, 0), 840, _Buf((N, H, W, Cin + 16), dt), c0=8, accumulate=acc, tile=tile,
+                         siblings=couts[1:], lds=lds)
+        assert lib.fn_conv2d_variant(C.byref(L.d), 1) == (tile or 32032)                      # sibling launches never split K
+        _launch_checked(lib, L, f"{nsrc} sources, tile {tile}, accumulate {acc}")
+
+
+def _norm_fwd(lib, dt, case, seed, tile=0, z_out=None):
+    """A normalise-on-load forward launch (x: the raw slice of tests.test_gpu_conv_wgrad._bn_operand) into a NaN-prefilled slice
+    of a wider buffer; the reference is conv_fp64 of the tensor fn_bn_relu_train_fwd writes from the same statistics."""
+    from tests.test_gpu_conv_wgrad import _bn_operand
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(case)
+    raw, z, set_norm, keep = _bn_operand(lib, case, dt, seed)
+    w = _mk((Cout, kh, kw, Cin), dt, 0.1, seed=seed + 1)
+    out = _Buf((N, OH, OW, Cout + 16), dt)
+    out.claim(8, Cout)
+    d = conv_desc(N, H, W, Cin, Cout, kh, kw, s, ph, pw, dt, ld_x=Cin + 16, ld_y=Cout + 16)
+    d.w, d.y, d.tile_fwd = ptr(w), ptr(out.t, 8), tile
+    set_norm(d)
+    if z_out is not None:
+        d.nrm_z = ptr(z_out.t, 8)
+    zs = z[..., 8:8 + Cin]
+    ref, aref = _memo(("norm fwd", case, dt, seed), lambda: conv_fp64(zs, w, s, ph, pw))
+    check = lambda what: assert_elementwise(out.t[..., 8:8 + Cout], ref, aref, kh * kw * Cin + 3, dt, what + ": y")
+    return _Layer(0, d, [raw, z, w, keep], [check], [out] + ([z_out] if z_out is not None else [])), zs
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("case", NORM_CASES)
+def test_conv_normalise_on_load_forward_elementwise(lib, case, dt):
+    """The forward half of test_conv_normalise_on_load_equals_materialised_bn against fp64: y from the RAW tensor and its
+    statistics == the convolution of the materialised activation, element by element, zero padding included."""
+    L, zs = _norm_fwd(lib, dt, case, 850)
+    assert lib.fn_conv2d_variant(C.byref(L.d), 0) == 32032                                    # normalise-on-load never splits K
+    _launch_checked(lib, L, f"{case} normalise-on-load")
+
+
+NRMZ_LAYERS = [(3, 9, 9, 64, 160, 1, 1, 1, 0, 0), (2, 9, 9, 64, 160, 3, 3, 1, 1, 1)]      # M = 243 / 162: ragged in every row tile
+
+
+@pytest.mark.parametrize("dt", [_lib.FN_BF16, _lib.FN_F16])
+@pytest.mark.parametrize("tile", [32032, 128064])
+@pytest.mark.parametrize("case", NRMZ_LAYERS)
+def test_conv_nrm_z_side_write(lib, case, tile, dt):
+    """fn_conv_desc.nrm_z: the activated tensor the lazy BatchNorm plan lets its single reader write.  Cout = 160 spans five /
+    three column tiles (only the first tile's workgroups write), x and nrm_z are slices of wider buffers.  The contract is
+    bit-equality: nrm_z, NaN-prefilled, afterwards holds exactly what fn_bn_relu_train_fwd writes from the same statistics (the
+    same fma, ReLU and rounding), its neighbour bytes untouched; y is within the fp64 bound and bit-identical to the launch
+    without nrm_z."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(case)
+    zb = _Buf((N, H, W, Cin + 16), dt)
+    zb.claim(8, Cin)
+    plain, zs = _norm_fwd(lib, dt, case, 860, tile=tile)
+    side, _ = _norm_fwd(lib, dt, case, 860, tile=tile, z_out=zb)
+    for L in (plain, side):
+        assert lib.fn_conv2d_variant(C.byref(L.d), 0) == tile
+        _launch_checked(lib, L, f"{case} tile {tile} nrm_z {L is side}")
+    assert same_bits(side.bufs[0].t, plain.bufs[0].t), "y differs with nrm_z"
+    assert same_bits(zb.t[..., 8:8 + Cin], zs), "nrm_z differs from fn_bn_relu_train_fwd's output"
+    first = zb.t.clone()
+    side.launch(lib)                                        # again onto the written tensor: the same bits
+    torch.cuda.synchronize()
+    assert same_bits(zb.t, first)
+
+
+def test_conv_nrm_z_rejections(lib):
+    """nrm_z needs stride 1 and an output map of the input's size, and it needs nrm_stats: refused before any launch."""
+    dt = _lib.FN_BF16
+    t = torch.zeros(2 * 9 * 9 * 160, dtype=lp_dtype(dt), device="cuda")
+    st = torch.zeros(256, dtype=torch.int64, device="cuda")
+    for geo, norm in (((2, 9, 9, 64, 160, 3, 3, 2, 1, 1), True), ((2, 9, 9, 64, 160, 3, 3, 1, 0, 0), True), ((2, 9, 9, 64, 160, 3, 3, 1, 1, 1), False)):
+        d = conv_desc(*geo, dt)
+        d.x = d.w = d.y = d.nrm_z = ptr(t)
+        if norm:
+            d.nrm_stats, d.nrm_beta, d.nrm_count, d.nrm_eps, d.nrm_sq_off = ptr(st), ptr(st), 162, 1e-3, 64
+        with pytest.raises(ValueError):
+            _lib.check(lib.fn_conv2d_fwd(C.byref(d), stream()))
+        d.nrm_z = None
+        if norm:                                            # the same descriptor without nrm_z is a valid launch
+            assert lib.fn_conv2d_variant(C.byref(d), 0) > 0

@@ -147,3 +147,58 @@ def dgrad_fp64(dy_nhwc, w_ohwi, H, W, stride, ph, pw):
         y.backward(dy.double().cpu().permute(0, 3, 1, 2))
         return x.grad.permute(0, 2, 3, 1).contiguous()
     return f(dy_nhwc, w), f(dy_nhwc.abs(), w.abs())
+
+
+# ---- weight gradients -------------------------------------------------------------------------------------------------------
+# dW[co][ky][kx][ci] = sum over the M = N*OH*OW output pixels of dY[n,oy,ox,co] * X[n, oy*s - ph + ky, ox*s - pw + kx, ci]: an fp32
+# sum of M exact products, stored in fp32 (assert_elementwise(..., out_f32=True)).  A launch split over pixels adds `splits`
+# partial sums (global atomics into dW, or slabs added by the ordered reduce), in any order: k = M + splits + 2.
+# The bound is about M 2^-24 absref, one missing pixel term about absref / M: the check sees a single dropped term only while
+# M^2 << 2^24, so every weight-gradient case keeps M <= 2048 (M^2 2^-24 <= 1/4).
+WGRAD_MAX_M = 2048
+
+
+def lp_randn(shape, dt, scale=1.0, seed=0):
+    """Seeded normal values rounded to the storage type, on the CPU."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(lp_dtype(dt))
+
+
+def wgrad_pixels(case):
+    """M = N*OH*OW of a (N, H, W, Cin, Cout, kh, kw, stride, ph, pw) case: the number of terms of one dW element."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw = case[:10]
+    return N * ((H + 2 * ph - kh) // s + 1) * ((W + 2 * pw - kw) // s + 1)
+
+
+def wgrad_k(M, splits):
+    """Length of the longest fp32 chain behind one dW element: M products, `splits` partial sums, the store."""
+    return M + max(int(splits), 1) + 2
+
+
+def wgrad_operands(case, dt, seed):
+    """(x [N,H,W,Cin], dy [N,OH,OW,Cout]) of a weight-gradient case: rounded operands on the CPU, shared by the GPU tests and
+    the host test of their bound."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw = case[:10]
+    OH, OW = (H + 2 * ph - kh) // s + 1, (W + 2 * pw - kw) // s + 1
+    return lp_randn((N, H, W, Cin), dt, seed=seed), lp_randn((N, OH, OW, Cout), dt, seed=seed + 1)
+
+
+def wgrad_fp64(x_nhwc, dy_nhwc, kh, kw, stride, ph, pw):
+    """(fp64 weight gradient [Cout, kh, kw, Cin] of the convolution, the same sum over |x| |dy|) on the CPU from the rounded
+    operands: tap (ky, kx) is the product of dY [M, Cout]^T with the strided window of the zero-padded x that tap reads."""
+    x, dy = x_nhwc.double().cpu(), dy_nhwc.double().cpu()
+    N, H, W, Cin = x.shape
+    _, OH, OW, Cout = dy.shape
+    assert OH == (H + 2 * ph - kh) // stride + 1 and OW == (W + 2 * pw - kw) // stride + 1, (x.shape, dy.shape)
+    xp = torch.zeros(N, H + 2 * ph, W + 2 * pw, Cin, dtype=torch.float64)
+    xp[:, ph:ph + H, pw:pw + W] = x
+    g = dy.reshape(-1, Cout)
+
+    def f(a, b):
+        out = torch.empty(Cout, kh, kw, Cin, dtype=torch.float64)
+        for ky in range(kh):
+            for kx in range(kw):
+                win = a[:, ky:ky + (OH - 1) * stride + 1:stride, kx:kx + (OW - 1) * stride + 1:stride]
+                out[:, ky, kx] = b.t() @ win.reshape(-1, Cin)
+        return out
+    return f(xp, g), f(xp.abs(), g.abs())
