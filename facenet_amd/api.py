@@ -66,13 +66,18 @@ class FaceNet:
     def embedding_size(self):
         return self._model.embedding_size
 
-    def evaluate(self, images):
+    def evaluate_device(self, images):
+        """``evaluate`` without the copy to the host: the device tensor [N, E].  It may alias the plan's output buffer, which
+        the next call at the same batch size overwrites."""
         emb = self._model(images, training=False)
         if not self._normalized:   # un-normalised bottleneck (BN output in inference mode)
             n = emb.shape[0]
             plan = self._model._plan(n, False)
             emb = plan.embedding.buf.act.view(n, -1)
-        return emb.detach().cpu().numpy()
+        return emb.detach()
+
+    def evaluate(self, images):
+        return self.evaluate_device(images).cpu().numpy()
 
     def image_to_embedding(self, image_arrays: Iterable[np.ndarray]) -> np.ndarray:
         image_arrays = np.asarray(image_arrays)

@@ -1,0 +1,125 @@
+# coding:utf-8
+"""Who is in every photograph of a data set: detector -> crop -> network -> gallery search on the device (FacePipeline.identify,
+DESIGN.md section 19): ``python -m facenet_amd.apps.identify --config x.yaml``.
+
+Keys: those of apps/photo_embeddings.py (dataset.path, model.*, image.size, image.margin, detector, mtcnn.weights_file, file)
+and gallery.path (required: the .npz of apps/embeddings.py with the known faces), gallery.metric (0 or 1), identify.k (neighbours
+kept per face, 1..64) and at most one of identify.threshold (a number) and identify.classifier (an .npz written by a
+FaceToFaceNormalizedEmbeddingsClassifier's ``save``); with neither every face gets its nearest gallery row's label.  Every image
+of the data set is read and its faces go to ``file``, one .npz with a row per face: ``files``, ``face``, ``boxes`` int64 [N, 4],
+``confidence`` float64 [N] as photo_embeddings writes them, ``labels`` int64 [N] (-1: nobody nearer than the threshold),
+``names`` [N] ('' for -1 or a gallery without names), ``distances`` float32 [N, k] and ``rows`` int32 [N, k] (gallery rows by
+ascending distance; -1 / inf where the gallery has fewer than k rows).  One line is logged per face."""
+from __future__ import annotations
+
+from pathlib import Path
+
+import click
+import numpy as np
+from PIL import Image
+
+from facenet_amd.apps import photo_embeddings
+from facenet_amd.config import Config, _merge
+
+DEFAULTS = dict(photo_embeddings.DEFAULTS, gallery={"path": None, "metric": 0},
+                identify={"threshold": None, "classifier": None, "k": 1})
+
+
+def load_options(path=None, overrides: dict = None) -> Config:
+    """DEFAULTS <- yaml <- overrides.  ``file`` defaults to <dataset.path>_<model stem>/identified.npz."""
+    cfg = dict(DEFAULTS)
+    if path is not None:
+        import yaml
+        with open(Path(path).expanduser()) as f:
+            cfg = _merge(cfg, yaml.safe_load(f) or {})
+    if overrides:
+        cfg = _merge(cfg, overrides)
+    c = Config(cfg)
+    if not c.dataset.path:
+        raise ValueError("identify: dataset.path is not specified")
+    if not c.gallery.path:
+        raise ValueError("identify: gallery.path is not specified")
+    c.gallery.path = Path(c.gallery.path).expanduser()
+    if c.gallery.metric not in (0, 1):
+        raise ValueError("Undefined similarity metric {}".format(c.gallery.metric))
+    if c.identify.threshold is not None and c.identify.classifier is not None:
+        raise ValueError("identify: give identify.threshold or identify.classifier, not both")
+    if c.identify.classifier is not None:
+        c.identify.classifier = Path(c.identify.classifier).expanduser()
+    if not isinstance(c.identify.k, int) or not 1 <= c.identify.k <= 64:
+        raise ValueError(f"identify.k must be an integer in [1, 64], got {c.identify.k!r}")
+    if c.file:
+        c.file = Path(c.file).expanduser()
+    else:
+        stem = Path(c.model.path).stem if c.model.path else "model"
+        c.file = Path(str(Path(c.dataset.path).expanduser()) + "_" + stem) / "identified.npz"
+    if c.file.suffix != ".npz":
+        raise ValueError(f"{c.file}: the output file must be an .npz")
+    return c
+
+
+def load_gallery(options):
+    """(Gallery, fp32 threshold or None) of the options."""
+    from facenet_amd.faceclass import FaceToFaceNormalizedEmbeddingsClassifier
+    from facenet_amd.recognize import Gallery
+    gallery = Gallery.from_file(options.gallery.path, metric=options.gallery.metric)
+    classifier = None
+    if options.identify.classifier is not None:
+        classifier = FaceToFaceNormalizedEmbeddingsClassifier().load(options.identify.classifier)
+    return gallery, gallery.threshold_of(options.identify.threshold, classifier)
+
+
+def write_identified(options, pipeline=None, gallery=None, threshold=None, log=print):
+    """pipeline: a FacePipeline (built from the options when None); gallery / threshold: as `load_gallery` returns them."""
+    from facenet_amd import dataset
+
+    dbase = dataset.Database(options.dataset)
+    log(dbase)
+    pipeline = photo_embeddings.build_pipeline(options) if pipeline is None else pipeline
+    if gallery is None:
+        gallery, threshold = load_gallery(options)
+    log(gallery)
+    k = options.identify.k
+    files, face, boxes, confidence, labels, names, distances, rows, unread = [], [], [], [], [], [], [], [], 0
+    for path in dbase.files:
+        try:
+            pixels = np.asarray(Image.open(path).convert(pipeline.detector.mode), dtype=np.uint8)
+        except Exception:
+            unread += 1
+            continue
+        found, crops = pipeline.crops(pixels)
+        if len(found) == 0:
+            continue
+        emb = pipeline.embed_device(crops)
+        dist, near = (t.cpu().numpy() for t in gallery.search(emb, k=k))
+        for n, box in enumerate(found):
+            label, name, _, _ = gallery.who(dist[n, 0], near[n, 0], threshold)
+            name = "" if name is None else str(name)
+            files.append(str(path))
+            face.append(n)
+            boxes.append([box.left, box.top, box.width, box.height])
+            confidence.append(np.nan if box.confidence is None else float(box.confidence))
+            labels.append(label)
+            names.append(name)
+            distances.append(dist[n])
+            rows.append(near[n])
+            log(f"{path} face {n}: {name or label} distance {dist[n, 0]:.6f} gallery row {near[n, 0]}")
+    options.file.parent.mkdir(parents=True, exist_ok=True)
+    np.savez(options.file, files=np.asarray(files, dtype=str), face=np.asarray(face, dtype=np.int64),
+             boxes=np.asarray(boxes, dtype=np.int64).reshape(-1, 4), confidence=np.asarray(confidence, dtype=np.float64),
+             labels=np.asarray(labels, dtype=np.int64), names=np.asarray(names, dtype=str),
+             distances=np.asarray(distances, dtype=np.float32).reshape(-1, k), rows=np.asarray(rows, dtype=np.int32).reshape(-1, k))
+    log('Number of files that cannot be read', unread)
+    log(f"output file: {options.file}")
+    log(f"number of faces: {len(files)} in {dbase.nrof_images} images")
+    return options.file
+
+
+@click.command()
+@click.option("--config", default=None, type=Path, help="Path to yaml config file with used options for the application.")
+def main(**options):
+    write_identified(load_options(options["config"]))
+
+
+if __name__ == "__main__":
+    main()

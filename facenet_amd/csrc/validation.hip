@@ -116,16 +116,14 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
 // with a stride (diagonal pairs and off-diagonal pairs in separate workgroups), covers each pair with 64x64 super-tiles
 // (wave w: rows 16w..16w+15 against four 16x16 column tiles, empty tiles skipped) and keeps the weighted fp64 tables in
 // LDS until it has seen all its pairs: the global fp64 atomics happen once per workgroup, not once per class pair.
-constexpr int OT = 64;          // rows / columns of a super-tile
-constexpr int OE = 32;          // embedding chunk
-constexpr int OLD = OE + 4;     // LDS row stride in floats: 16-byte aligned rows, conflict-free ds_read_b128 per 16 lanes
+constexpr int OT = F32_TILE;    // rows / columns of a super-tile
+constexpr int OE = F32_CHUNK;   // embedding chunk
+constexpr int OLD = F32_LD;     // LDS row stride in floats
 constexpr int OMAXF = 16;       // folds
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Column c of a chunk goes to LDS position opos(c): inside each block of 16 the 4x4 (step, lane group) index is
-// transposed, so that the float4 a lane of group g reads holds k = 4s + g for the four MFMA steps s = 0..3 in order.
-__device__ __forceinline__ int opos(int c) { return (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3); }
+__device__ __forceinline__ int opos(int c) { return f32_chunk_pos(c); }     // common.h: shared with identify.hip
 
 __device__ __forceinline__ void stage_rows(float (*dst)[OLD], const float* __restrict__ src, int rows, int E, int e0, bool vec, int tid) {
     if (vec) {                                            // E % 4 == 0: rows are 16-byte aligned

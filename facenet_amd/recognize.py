@@ -4,13 +4,24 @@
 (`FaceDetector.detect` -> MTCNN) and to the crop kernel (`image_processing_batch`, the pixels of `image_processing` followed by the
 centre cut of `image.size`), whose uint8 output goes straight to `FaceNet.evaluate`.  The network plans one launch list (and
 captures one graph) per batch size, so the face batch is zero-padded up to one of `BATCH_SIZES`: photos with 1, 2 or 3 faces
-share a plan.  Inference has no coupling between the images of a batch, so the padding rows change nothing."""
+share a plan.  Inference has no coupling between the images of a batch, so the padding rows change nothing.
+
+``Gallery(embeddings, labels, names, files, metric)`` answers "who is this?" (DESIGN.md section 19): it keeps the known faces'
+embeddings on the device and ``search`` returns each query's k nearest rows from one fn_gallery_search call, whose distances
+are those of the validation kernels bit for bit; ``identify`` turns the nearest row into (label, name, distance, row), open-set
+with a threshold (a number, or a trained FaceToFaceNormalizedEmbeddingsClassifier's) and closed-set without.
+``FacePipeline.identify`` hands the network's device output straight to the search."""
 from __future__ import annotations
+
+from pathlib import Path
 
 import numpy as np
 import torch
 
+from . import _lib
 from .detectors.face_detector import image_processing_batch
+from .faceclass import _as_table, _ptr, _stream
+from .statistics import _decode_ord
 
 BATCH_SIZES = (1, 4, 16, 64, 256)
 
@@ -54,3 +65,183 @@ class FacePipeline:
         if len(boxes) == 0:
             return []
         return list(zip(boxes, self.embed(crops)))
+
+    def embed_device(self, crops):
+        """`embed` without the copy to the host: device float32 [F, E] (a copy: the plan's output buffer is reused)."""
+        n = crops.shape[0]
+        batch = crops.new_zeros((padded_batch(n),) + tuple(crops.shape[1:]))
+        batch[:n] = crops
+        return self.facenet.evaluate_device(batch)[:n].to(dtype=torch.float32, copy=True)
+
+    def identify(self, image, gallery, **kw):
+        """-> list of (BoundingBox, (label, name, distance, row)) through `gallery.identify(embeddings, **kw)`; [] without a
+        network or search launch when nothing was detected.  The embeddings never visit the host."""
+        boxes, crops = self.crops(image)
+        if len(boxes) == 0:
+            return []
+        return list(zip(boxes, gallery.identify(self.embed_device(crops), **kw)))
+
+
+MAX_K = 64                # fn_gallery_search: 1 <= k <= 64
+MAX_LENGTH = 512          # ... and embedding length a multiple of 4 up to 512
+
+
+def _class_names(labels, files):
+    """label -> the name of the directory that holds one of its files (the class directories of dataset.Database)."""
+    names = {}
+    for label, f in zip(np.asarray(labels).tolist(), np.asarray(files).tolist()):
+        names.setdefault(int(label), Path(str(f)).parent.name)
+    return names
+
+
+class Gallery:
+    """The known faces: fp32 unit-norm embeddings [G, E] resident on the device, optionally an integer label per row (default:
+    every row is its own class), a name per label (a dict, or a sequence indexed by label) and the file of every row.  ``metric``
+    0 reports 2 (1 - x.y), 1 arccos(x.y) (statistics.py:45-53); both rank by the former.  Labels stay on the host as int64 and
+    are looked up there from the rows a search returns (fn_gallery_search's own int32 ``labels`` table is not used), so any
+    non-negative integer is a valid label."""
+
+    def __init__(self, embeddings, labels=None, names=None, files=None, metric=0, device="cuda"):
+        if metric not in (0, 1):
+            raise ValueError("Undefined similarity metric {}".format(metric))            # statistics.py:55
+        shape = tuple(embeddings.shape) if hasattr(embeddings, "shape") else np.shape(embeddings)
+        if len(shape) != 2 or shape[0] < 1:
+            raise ValueError(f"gallery embeddings must be a non-empty 2-D [G, E] array, got shape {shape}")
+        if shape[1] % 4 or not 4 <= shape[1] <= MAX_LENGTH:
+            raise ValueError(f"embedding length {shape[1]} must be a multiple of 4 in [4, {MAX_LENGTH}]")
+        if labels is None:
+            host_labels = np.arange(shape[0], dtype=np.int64)
+        else:
+            host_labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+            if host_labels.shape != (shape[0],) or host_labels.dtype.kind not in "iu":
+                raise ValueError(f"labels must be {shape[0]} integers, got shape {host_labels.shape} of {host_labels.dtype}")
+            if host_labels.min() < 0:
+                raise ValueError("labels must not be negative: -1 is what an unidentified face gets")
+        if files is not None and len(files) != shape[0]:
+            raise ValueError(f"files must name {shape[0]} rows, got {len(files)}")
+        if names is not None and not isinstance(names, dict):
+            names = {i: n for i, n in enumerate(names)}
+        if names is not None and not set(np.unique(host_labels).tolist()) <= set(names):
+            raise ValueError("names must cover every label")
+        self.metric, self.device = metric, torch.device(device)
+        self.labels = host_labels.astype(np.int64)
+        self.names = names
+        self.files = None if files is None else np.asarray(files, dtype=str)
+        self.embeddings = _as_table(embeddings, self.device)
+
+    @classmethod
+    def from_file(cls, path, metric=0, device="cuda"):
+        """The .npz of apps/embeddings.py (``embeddings`` / ``labels`` / ``files``); names are the class directories of ``files``."""
+        path = Path(path).expanduser()
+        if path.suffix == ".h5":
+            raise ValueError(f"{path}: .h5 embeddings files need h5py, which this project does not use; "
+                             "write an .npz with 'embeddings' and 'labels' (facenet_amd.apps.embeddings)")
+        with np.load(path) as f:
+            embeddings = np.asarray(f["embeddings"], dtype=np.float32)
+            labels = np.asarray(f["labels"]) if "labels" in f else None
+            files = np.asarray(f["files"]) if "files" in f else None
+        names = _class_names(labels, files) if labels is not None and files is not None else None
+        return cls(embeddings, labels=labels, names=names, files=files, metric=metric, device=device)
+
+    @property
+    def nrof_images(self):
+        return self.embeddings.shape[0]
+
+    @property
+    def nrof_classes(self):
+        return len(np.unique(self.labels))
+
+    @property
+    def length(self):
+        return self.embeddings.shape[1]
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}\n" + f"Number of classes {self.nrof_classes} \n" + f"Number of images {self.nrof_images}\n" +
+                f"Embedding length {self.length}\n" + f"metric: {self.metric}\n")
+
+    def _search(self, queries, k, skip, slab_rows, atol):
+        """-> device (dist [Q, k], rows [Q, k]) after every check of `search`."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        shape = tuple(queries.shape) if hasattr(queries, "shape") else np.shape(queries)
+        if len(shape) != 2:
+            raise ValueError(f"queries must be a 2-D [Q, E] array, got shape {shape}")
+        if shape[1] != self.length:
+            raise ValueError(f"embedding lengths differ: queries {shape[1]}, gallery {self.length}")
+        Q, G = shape[0], self.nrof_images
+        if skip is not None:
+            skip = np.asarray(skip.cpu() if torch.is_tensor(skip) else skip)
+            if skip.shape != (Q,) or skip.dtype.kind not in "iu":
+                raise ValueError(f"skip must be {Q} integers (a gallery row, or -1), got shape {skip.shape} of {skip.dtype}")
+        dev = self.device
+        dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
+        rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+        if Q == 0:
+            return dist, rows
+        if dev.type != "cuda":
+            raise _lib.FacenetHipError("Gallery.search runs fn_gallery_search on the GPU; facenet_amd has no CPU fallback")
+        lib = _lib.load()
+        q = _as_table(queries, dev)
+        skip_dev = None if skip is None else torch.from_numpy(skip.astype(np.int32)).to(dev)
+        import ctypes
+        nbytes = ctypes.c_longlong(0)
+        _lib.check(lib.fn_gallery_search_workspace(Q, G, k, int(slab_rows), ctypes.byref(nbytes)), "gallery_search_workspace")
+        ws = torch.empty(max(1, (nbytes.value + 7) // 8), dtype=torch.int64, device=dev)
+        rng = None if atol is None else torch.zeros(2, dtype=torch.int32, device=dev)
+        _lib.check(lib.fn_gallery_search(_ptr(q), Q, _ptr(self.embeddings), G, self.length, k, self.metric, _ptr(skip_dev), None, int(slab_rows),
+                                         _ptr(ws), _ptr(dist), _ptr(rows), None, _ptr(rng), _stream(dev)),
+                   "gallery_search")
+        if rng is None:
+            return dist, rows
+        lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())       # waits for the search
+        lim = 1 + atol
+        if lo < -lim or hi > lim:       # statistics.py:40-42
+            raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+        return dist, rows
+
+    def search(self, queries, k=1, skip=None, slab_rows=0, atol=1.e-5):
+        """The k nearest gallery rows of every query row -> (dist float32 [Q, k], rows int32 [Q, k]), ascending by (distance,
+        row); NumPy in gives NumPy out, a device tensor in gives device tensors out.  ``skip`` [Q]: the gallery row query q must
+        not return (-1: none).  A query with fewer than k admissible rows gets row -1 at distance +inf in the tail.  Raises the
+        reference's ValueError when some dot product leaves +-(1 + atol); that check reads two words back and so waits for the
+        search on the host, also when tensors go in and come out.  ``atol=None`` leaves the check out: the call then only
+        enqueues work on the current stream.  ``slab_rows`` is fn_gallery_search's (0: chosen by the library; the result does not
+        depend on it)."""
+        dist, rows = self._search(queries, k, skip, slab_rows, atol)
+        if torch.is_tensor(queries):
+            return dist, rows
+        return dist.cpu().numpy(), rows.cpu().numpy()
+
+    def leave_one_out(self, k=1):
+        """Every gallery row's k nearest OTHER rows, device tensors: ``search(gallery, k, skip=arange(G))``."""
+        return self.search(self.embeddings, k, skip=np.arange(self.nrof_images, dtype=np.int32))
+
+    def threshold_of(self, threshold=None, classifier=None):
+        """The fp32 threshold of `identify`: the number given, a classifier's trained one, or None (closed set)."""
+        if threshold is not None and classifier is not None:
+            raise ValueError("identify takes a threshold or a classifier, not both")
+        if classifier is not None:
+            from .faceclass import FaceToFaceNormalizedEmbeddingsClassifier
+            if not isinstance(classifier, FaceToFaceNormalizedEmbeddingsClassifier):
+                raise ValueError("identify needs a FaceToFaceNormalizedEmbeddingsClassifier: its distance is the gallery's metric 0")
+            if self.metric != 0:
+                raise ValueError("a classifier's threshold applies to metric 0, this gallery reports metric {}".format(self.metric))
+            return classifier.variable("threshold", mode="numpy")
+        return None if threshold is None else np.float32(threshold)
+
+    def identify(self, queries, threshold=None, classifier=None, k=1):
+        """-> for every query row (label, name, distance, row) of its nearest gallery row.  ``k`` is the width of the search that
+        is run; only its best column is used, so any k gives the same answer and k = 1 is the cheapest.  Open set:
+        label -1 and name None unless ``distance < threshold`` (the strict < of the classifiers' predict, in fp32); the
+        threshold is the number given or ``classifier.variable("threshold")``.  Neither: closed set, always the nearest."""
+        thr = self.threshold_of(threshold, classifier)
+        dist, rows = self._search(queries, k, None, 0, 1.e-5)
+        return [self.who(d, r, thr) for d, r in zip(dist[:, 0].cpu().numpy(), rows[:, 0].cpu().numpy())]
+
+    def who(self, distance, row, threshold=None):
+        """(label, name, distance, row) of one search result: label -1, name None when there is no row or, with an fp32
+        ``threshold`` (`threshold_of`), ``distance < threshold`` is false."""
+        known = row >= 0 and (threshold is None or distance < threshold)
+        label = int(self.labels[row]) if known else -1
+        return label, (self.names[label] if known and self.names is not None else None), float(distance), int(row)

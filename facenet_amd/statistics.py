@@ -44,6 +44,24 @@ def pairwise_similarities(xa, xb=None, metric: int = 0, atol: float = 1.e-5, dev
     return sims.cpu().numpy()
 
 
+def cmc(labels, rows):
+    """Closed-set cumulative match curve of a leave-one-out search (host NumPy).  labels [n]: the class of every gallery row;
+    rows int [n, k]: row i's neighbours in ascending distance, itself excluded, -1 where there is none (Gallery.leave_one_out).
+    -> (curve float64 [k], left_out): curve[r] is the share of rows whose first r + 1 neighbours contain their own label.  A
+    row whose class has no other image cannot be matched: such rows are left out of the share and counted in left_out."""
+    labels, rows = np.asarray(labels), np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[0] != labels.shape[0]:
+        raise ValueError("cmc: rows must be [len(labels), k], got {} for {} labels".format(rows.shape, labels.shape[0]))
+    _, inverse, counts = np.unique(labels, return_inverse=True, return_counts=True)
+    scored = counts[inverse] > 1
+    left_out = int(np.count_nonzero(~scored))
+    if not scored.any():
+        return np.zeros(rows.shape[1], dtype=np.float64), left_out
+    hit = (labels[np.maximum(rows, 0)] == labels[:, None]) & (rows >= 0)
+    found = np.logical_or.accumulate(hit[scored], axis=1)
+    return found.mean(axis=0, dtype=np.float64), left_out
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Face-to-face validation (facenet/statistics.py:82-331) on the GPU.  Same class names, properties and report text as
 # the reference; the O(classes^2 x thresholds) NumPy loops run as ONE launch of fn_confidence_counts per matrix.

@@ -353,6 +353,22 @@ int fn_confidence_counts_folds(const float* emb, const int32_t* cls_start, const
                                const int32_t* train_classes, int C, int E, int F, const float* thresholds, int T, int metric,
                                double* out, int32_t* range, void* stream);
 
+/* ---- 1:N identification: for each of Q query rows the k nearest of G gallery rows; the [Q, G] distance
+ * matrix never reaches memory.  s(q, g) is the same fp32 fmaf chain as fn_confidence_counts (exact fp32 MFMA), sc = s clipped to
+ * [-1, 1]; rows are ranked by ascending (2 (1 - sc), gallery row) for both metrics, equal distances going to the lower row; dist
+ * is 2 (1 - sc) (metric 0) or acosf(sc) (metric 1).  queries fp32 [Q, E], gallery fp32 [G, E], unit-norm rows, both and the
+ * workspace 16-byte aligned; 1 <= k <= 64; E a multiple of 4 in [4, 512].  skip int32 [Q] or NULL: the gallery row query q must
+ * not return (-1: none).  labels int32 [G] or NULL.  slab_rows: gallery rows per workgroup, rounded up to a multiple of 64 (0:
+ * chosen by the library); the result does not depend on it.  workspace: at least the bytes fn_gallery_search_workspace reports
+ * for the same Q, G, k and slab_rows.  dist fp32 [Q, k], rows int32 [Q, k], row_labels int32 [Q, k] or NULL (needs labels):
+ * ascending; a query with fewer than k admissible rows gets row -1, dist +inf, label -1 in the tail.  range (2 words or NULL):
+ * ordered-int min/max of s over all Q x G pairs, as in fn_pairwise_sqdist.  The caller owns every buffer; the call allocates
+ * nothing and does not synchronise. */
+int fn_gallery_search_workspace(int Q, int G, int k, int slab_rows, long long* bytes);
+int fn_gallery_search(const float* queries, int Q, const float* gallery, int G, int E, int k, int metric, const int32_t* skip,
+                      const int32_t* labels, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* row_labels,
+                      float* range, void* stream);
+
 /* ---- softmax classifier loss: apps/train_softmax.py:91 (SparseCategoricalCrossentropy(from_logits)); loss: fp32[4] as above;
  * dbias (optional): fixed point, FN_ACC_GRAD_BITS, += column sums of dlogits */
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
