@@ -138,6 +138,12 @@ _SIGNATURES = {
     "fn_confidence_counts_folds": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_gallery_search_workspace": [_i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_gallery_search": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    "fn_radius_workspace": [_i, _i, _i, C.POINTER(C.c_longlong)],
+    "fn_radius_count": [_p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _p, _p, _p],
+    "fn_radius_fill": [_p, _i, _p, _i, _i, _i, _f, _p, _i, _p, _p, _p, C.c_longlong, _p],
+    "fn_dbscan_init": [_i, _p, _i, _p, _p, _p, _p],
+    "fn_dbscan_rounds": [_i, _p, _p, _p, _p, _p, _i, _p],
+    "fn_dbscan_finish": [_i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p],
     "fn_softmax_xent_fwd_bwd": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _f, _i, _p],
     "fn_center_loss_fwd_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p],
     "fn_center_update": [_p, _i, _i, _i, _p, _i, C.c_double, _p],

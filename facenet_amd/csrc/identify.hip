@@ -15,24 +15,16 @@
 // candidates) and appends the survivors to the row's list; a list that cannot take another column tile is cut to its k
 // smallest by the wave that owns the row.  Rows belong to one wave: selection needs no workgroup barrier.
 // gallery_merge_kernel: one wave per query cuts the slabs' k-lists to the final k and writes distances, rows and labels.
-#include "common.h"
+#include "identify_stage.h"      // IT, IE, ILD, IdChunk, id_load, id_store, id_ord, id_slabs: shared with cluster.hip
 #include "../../include/facenet_hip.h"
 
 namespace fn {
 
-constexpr int IT = F32_TILE;         // query rows per workgroup, gallery rows per super-tile
-constexpr int IE = F32_CHUNK;        // embedding chunk
-constexpr int ILD = F32_LD;          // LDS row stride in floats (common.h: the staging validation.hip uses)
 constexpr int IMAXK = 64;
 constexpr int IMERGE_CAP = 128;      // merge list: up to 64 kept + 64 new keys
 constexpr unsigned long long INONE = ~0ull;
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ int id_ord(float f) {
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
 
 // list capacity of a row for a given k: the k kept keys and one column tile (16) of survivors, in steps of 16
 __host__ __device__ __forceinline__ int id_cap(int k) { return ((k + 15) / 16) * 16 + 16; }
@@ -60,29 +52,6 @@ __device__ __forceinline__ int id_prune(u64* __restrict__ list, int n, int k, u6
     }
     __builtin_amdgcn_wave_barrier();
     return n < k ? n : k;
-}
-
-struct IdChunk {      // one thread's share of a staged chunk: 2 float4 of the query tile, 2 of the gallery tile
-    float4 a[2], b[2];
-};
-
-__device__ __forceinline__ void id_load(IdChunk& c, const float* __restrict__ qrows, int nq, const float* __restrict__ grows, int ng, int E,
-                                        int e0, int tid) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int t = tid + i * 256, r = t >> 3, col = e0 + (t & 7) * 4;
-        c.a[i] = (r < nq && col < E) ? *reinterpret_cast<const float4*>(qrows + (long)r * E + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        c.b[i] = (r < ng && col < E) ? *reinterpret_cast<const float4*>(grows + (long)r * E + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
-__device__ __forceinline__ void id_store(const IdChunk& c, float (*sA)[ILD], float (*sB)[ILD], int tid) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int t = tid + i * 256, r = t >> 3, p = f32_chunk_pos((t & 7) * 4);
-        sA[r][p] = c.a[i].x; sA[r][p + 4] = c.a[i].y; sA[r][p + 8] = c.a[i].z; sA[r][p + 12] = c.a[i].w;
-        sB[r][p] = c.b[i].x; sB[r][p + 4] = c.b[i].y; sB[r][p + 8] = c.b[i].z; sB[r][p + 12] = c.b[i].w;
-    }
 }
 
 __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __restrict__ queries, int Q, const float* __restrict__ gallery, int G,
@@ -258,23 +227,6 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(const u64* __restrict
     dist[o] = d;
     rows[o] = row;
     if (row_labels) row_labels[o] = labels[row];
-}
-
-// Slab height (a multiple of 64) and count.  Chosen by the library: about 8192 workgroups in all (32 per CU: the tail of the
-// last round stays small), but never slabs of fewer than 512 rows, whose first super-tiles (thresholds still open, every
-// value a survivor) would weigh too much; with many query tiles this is one slab.
-static int id_slabs(int Q, int G, int slab_rows, int* rows_out) {
-    const long qtiles = cdiv(Q, IT);
-    long rows = slab_rows;
-    if (rows <= 0) {
-        const long want = cdiv(8192, qtiles);
-        rows = cdiv(G, want);
-        if (rows < 512) rows = 512;
-    }
-    rows = (rows + IT - 1) / IT * IT;
-    if (rows > (1L << 30)) rows = 1L << 30;
-    *rows_out = (int)rows;
-    return cdiv(G, rows);
 }
 
 // partial lists per (slab, query): four when the waves split the column tiles (Q <= 16), else one

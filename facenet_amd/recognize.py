@@ -10,7 +10,12 @@ share a plan.  Inference has no coupling between the images of a batch, so the p
 embeddings on the device and ``search`` returns each query's k nearest rows from one fn_gallery_search call, whose distances
 are those of the validation kernels bit for bit; ``identify`` turns the nearest row into (label, name, distance, row), open-set
 with a threshold (a number, or a trained FaceToFaceNormalizedEmbeddingsClassifier's) and closed-set without.
-``FacePipeline.identify`` hands the network's device output straight to the search."""
+``FacePipeline.identify`` hands the network's device output straight to the search.
+
+``Gallery.within`` is the range query: every gallery row nearer than eps as a CSR, from fn_radius_count /
+fn_radius_fill, with the same distances and the same strict fp32 < as validation and identification.  ``Gallery.cluster`` runs
+DBSCAN on the self-join (fn_dbscan_*) and returns a `Clustering`; ``FacePipeline.cluster`` does so for the faces of a list of
+photographs without their embeddings leaving the device."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -81,9 +86,64 @@ class FacePipeline:
             return []
         return list(zip(boxes, gallery.identify(self.embed_device(crops), **kw)))
 
+    def cluster(self, images, metric=0, **kw):
+        """Detect, crop and embed the faces of a list of photographs, then `Gallery.cluster(**kw)` them; the embeddings never
+        visit the host.  -> (Clustering, faces): faces[row] = (image index, face index within the image, BoundingBox).  Without a
+        single face: (None, [])."""
+        faces, embeddings = [], []
+        for index, image in enumerate(images):
+            boxes, crops = self.crops(image)
+            if len(boxes) == 0:
+                continue
+            embeddings.append(self.embed_device(crops))
+            faces.extend((index, n, box) for n, box in enumerate(boxes))
+        if not faces:
+            return None, []
+        return Gallery(torch.cat(embeddings), metric=metric, device=self.device).cluster(**kw), faces
+
 
 MAX_K = 64                # fn_gallery_search: 1 <= k <= 64
 MAX_LENGTH = 512          # ... and embedding length a multiple of 4 up to 512
+
+
+MAX_EDGES = 2 ** 31      # cols are int32 positions of a CSR that one allocation holds
+DBSCAN_ROUNDS = 8         # rounds enqueued between two looks at the converged flag
+
+
+def check_edges(nnz, max_edges=None):
+    """The size rule of `Gallery.within`, applied before anything of that size is allocated."""
+    if nnz >= MAX_EDGES:
+        raise ValueError(f"the radius search found nnz = {nnz} neighbour pairs, 2^31 or more: choose a smaller eps")
+    if max_edges is not None and nnz > max_edges:
+        raise ValueError(f"the radius search found nnz = {nnz} neighbour pairs, more than max_edges = {max_edges}: choose a smaller eps")
+
+
+class Clustering:
+    """The result of `Gallery.cluster`: ``labels`` int64 [G] (cluster ids 0 .. nrof_clusters - 1 in ascending order of each
+    cluster's smallest core row, -1 for noise), ``core`` bool [G], ``nrof_clusters``, ``nrof_noise``, ``rounds`` (hook-and-jump
+    rounds run), ``eps`` / ``min_samples`` and the CSR it was built from: ``offsets`` int64 [G + 1], ``rows`` int32 [nnz],
+    ``dist`` float32 [nnz] (device tensors)."""
+
+    def __init__(self, labels, core, nrof_clusters, nrof_noise, rounds, eps, min_samples, offsets, rows, dist):
+        self.labels, self.core = labels, core
+        self.nrof_clusters, self.nrof_noise, self.rounds = nrof_clusters, nrof_noise, rounds
+        self.eps, self.min_samples = eps, min_samples
+        self.offsets, self.rows, self.dist = offsets, rows, dist
+
+    @property
+    def sizes(self):
+        """int64 [nrof_clusters]: rows per cluster (noise rows are in none)."""
+        return np.bincount(self.labels[self.labels >= 0], minlength=self.nrof_clusters).astype(np.int64)
+
+    def members(self, c):
+        """The rows of cluster c, ascending (c = -1: the noise rows)."""
+        if not -1 <= c < self.nrof_clusters:
+            raise ValueError(f"cluster {c} is not in [-1, {self.nrof_clusters})")
+        return np.nonzero(self.labels == c)[0]
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}\n" + f"Number of images {len(self.labels)}\n" + f"Number of clusters {self.nrof_clusters}\n" +
+                f"Number of noise images {self.nrof_noise}\n" + f"eps: {self.eps} min_samples: {self.min_samples}\n")
 
 
 def _class_names(labels, files):
@@ -245,3 +305,97 @@ class Gallery:
         known = row >= 0 and (threshold is None or distance < threshold)
         label = int(self.labels[row]) if known else -1
         return label, (self.names[label] if known and self.names is not None else None), float(distance), int(row)
+
+    def _within(self, queries, eps, skip, slab_rows, atol, max_edges):
+        """-> device (offsets int64 [Q + 1], rows int32 [nnz], dist float32 [nnz]) after every check of `within`."""
+        eps = np.float32(eps)
+        if np.isnan(eps):
+            raise ValueError("eps must be a number, got NaN")
+        shape = tuple(queries.shape) if hasattr(queries, "shape") else np.shape(queries)
+        if len(shape) != 2:
+            raise ValueError(f"queries must be a 2-D [Q, E] array, got shape {shape}")
+        if shape[1] != self.length:
+            raise ValueError(f"embedding lengths differ: queries {shape[1]}, gallery {self.length}")
+        if max_edges is not None and max_edges < 0:
+            raise ValueError(f"max_edges must not be negative, got {max_edges}")
+        Q, G = shape[0], self.nrof_images
+        if skip is not None:
+            skip = np.asarray(skip.cpu() if torch.is_tensor(skip) else skip)
+            if skip.shape != (Q,) or skip.dtype.kind not in "iu":
+                raise ValueError(f"skip must be {Q} integers (a gallery row, or -1), got shape {skip.shape} of {skip.dtype}")
+        dev = self.device
+        offsets = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        if Q == 0:
+            return offsets, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        if dev.type != "cuda":
+            raise _lib.FacenetHipError("Gallery.within runs fn_radius_count on the GPU; facenet_amd has no CPU fallback")
+        lib = _lib.load()
+        q = _as_table(queries, dev)
+        skip_dev = None if skip is None else torch.from_numpy(skip.astype(np.int32)).to(dev)
+        import ctypes
+        nbytes = ctypes.c_longlong(0)
+        _lib.check(lib.fn_radius_workspace(Q, G, int(slab_rows), ctypes.byref(nbytes)), "radius_workspace")
+        ws = torch.empty(max(2, (nbytes.value + 7) // 8), dtype=torch.int64, device=dev)
+        rng = torch.zeros(2, dtype=torch.int32, device=dev)
+        common = (_ptr(q), Q, _ptr(self.embeddings), G, self.length, self.metric, float(eps), _ptr(skip_dev), int(slab_rows), _ptr(ws))
+        _lib.check(lib.fn_radius_count(*common, _ptr(offsets), _ptr(rng), _stream(dev)), "radius_count")
+        nnz = int(offsets[Q].item())                                # waits for the count
+        if atol is not None:
+            lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
+            lim = 1 + atol
+            if lo < -lim or hi > lim:       # statistics.py:40-42
+                raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+        check_edges(nnz, max_edges)
+        rows = torch.empty(nnz, dtype=torch.int32, device=dev)
+        dist = torch.empty(nnz, dtype=torch.float32, device=dev)
+        if nnz:
+            _lib.check(lib.fn_radius_fill(*common, _ptr(rows), _ptr(dist), nnz, _stream(dev)), "radius_fill")
+        return offsets, rows, dist
+
+    def within(self, queries, eps, skip=None, slab_rows=0, atol=1.e-5, max_edges=None):
+        """Every gallery row at ``distance < eps`` (the gallery's metric, strict fp32 <) of every query row, as a CSR ->
+        (offsets int64 [Q + 1], rows int32 [nnz], dist float32 [nnz]): query q's neighbours are rows[offsets[q]:offsets[q + 1]],
+        ascending by gallery row.  NumPy in gives NumPy out, a device tensor in gives device tensors out.  ``skip`` [Q]: the
+        gallery row query q must not return (-1: none).  The call reads nnz back between its two passes, so it waits for the
+        device.  Raises the reference's ValueError when some dot product leaves +-(1 + atol) (``atol=None``: no such check), and a
+        ValueError naming nnz when it exceeds ``max_edges`` or reaches 2^31, before the rows are allocated.  ``slab_rows`` is
+        fn_radius_count's (0: chosen by the library; the result does not depend on it)."""
+        out = self._within(queries, eps, skip, slab_rows, atol, max_edges)
+        if torch.is_tensor(queries):
+            return out
+        return tuple(t.cpu().numpy() for t in out)
+
+    def neighbours(self, eps, max_edges=None):
+        """The self-join, device tensors: every gallery row's OTHER rows within eps, ``within(gallery, eps, skip=arange(G))``.
+        The distances are symmetric bit for bit, so row j is in i's list exactly when i is in j's."""
+        return self.within(self.embeddings, eps, skip=np.arange(self.nrof_images, dtype=np.int32), max_edges=max_edges)
+
+    def cluster(self, threshold=None, classifier=None, min_samples=1, max_edges=None):
+        """DBSCAN over the gallery's rows at eps = the threshold (a number, or a trained classifier's: `threshold_of`) -> a
+        `Clustering`.  A row is a core row when it has at least ``min_samples`` rows within eps, itself included; clusters are
+        the connected components of the core rows; a non-core row with a core neighbour joins its nearest core neighbour's
+        cluster (equal distances: the lower row); every other row is noise, label -1.  ``min_samples=1`` is single linkage at
+        the threshold."""
+        if threshold is None and classifier is None:
+            raise ValueError("cluster needs a threshold or a classifier: clustering has no closed set")
+        if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or min_samples < 1:
+            raise ValueError(f"min_samples must be an integer of at least 1, got {min_samples!r}")
+        eps = self.threshold_of(threshold, classifier)
+        offsets, rows, dist = self.neighbours(eps, max_edges=max_edges)
+        dev, N = self.device, self.nrof_images
+        lib = _lib.load()
+        labels = torch.empty(N, dtype=torch.int32, device=dev)
+        core = torch.empty(N, dtype=torch.int32, device=dev)
+        ids = torch.empty(N, dtype=torch.int32, device=dev)
+        info = torch.zeros(8, dtype=torch.int32, device=dev)
+        st = _stream(dev)
+        _lib.check(lib.fn_dbscan_init(N, _ptr(offsets), int(min_samples), _ptr(labels), _ptr(core), _ptr(info), st), "dbscan_init")
+        while True:
+            _lib.check(lib.fn_dbscan_rounds(N, _ptr(offsets), _ptr(rows), _ptr(core), _ptr(labels), _ptr(info), DBSCAN_ROUNDS, st), "dbscan_rounds")
+            if int(info[0].item()):
+                break
+        _lib.check(lib.fn_dbscan_finish(N, _ptr(offsets), _ptr(rows), _ptr(dist), self.metric, _ptr(self.embeddings), self.length, _ptr(core),
+                                        _ptr(labels), _ptr(ids), _ptr(info), st), "dbscan_finish")
+        _, rounds, clusters, noise = info.cpu().tolist()[:4]
+        return Clustering(labels.cpu().numpy().astype(np.int64), core.cpu().numpy().astype(bool), clusters, noise, rounds, float(eps),
+                          int(min_samples), offsets, rows, dist)

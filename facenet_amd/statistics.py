@@ -62,6 +62,33 @@ def cmc(labels, rows):
     return found.mean(axis=0, dtype=np.float64), left_out
 
 
+def pairwise_clustering_scores(truth, labels):
+    """Pairwise (precision, recall, F) of a clustering against the true classes, the usual face-clustering measure: of all
+    pairs of rows that share a cluster the share that share a class, of all pairs that share a class the share that share a
+    cluster, and their harmonic mean.  ``labels`` < 0 are noise rows: each is a cluster of its own.  Computed from the
+    contingency table in exact (Python) integers; a ratio with an empty denominator is 1, as in ConfidenceMatrix."""
+    truth, labels = np.asarray(truth), np.asarray(labels)
+    if truth.ndim != 1 or truth.shape != labels.shape:
+        raise ValueError("pairwise_clustering_scores: truth and labels must be 1-D and of equal length, got {} and {}".format(
+            truth.shape, labels.shape))
+    if labels.dtype.kind not in "iu":
+        raise ValueError("pairwise_clustering_scores: labels must be integers, got {}".format(labels.dtype))
+    n = len(labels)
+    _, t = np.unique(truth, return_inverse=True)
+    labels = labels.astype(np.int64)
+    noise = labels < 0
+    c = np.where(noise, (labels.max() + 1 if n else 0) + np.arange(n), labels)        # every noise row a singleton
+    _, c = np.unique(c, return_inverse=True)
+    pairs = lambda counts: sum(int(k) * (int(k) - 1) // 2 for k in counts)
+    nt = int(t.max()) + 1 if n else 1
+    _, cell = np.unique(c.astype(np.int64) * nt + t, return_counts=True)                # the non-empty cells of the table
+    both, same_cluster, same_class = pairs(cell), pairs(np.bincount(c)), pairs(np.bincount(t))
+    precision = both / same_cluster if same_cluster else 1.0
+    recall = both / same_class if same_class else 1.0
+    f = 2 * precision * recall / (precision + recall) if precision + recall else 0.0
+    return precision, recall, f
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Face-to-face validation (facenet/statistics.py:82-331) on the GPU.  Same class names, properties and report text as
 # the reference; the O(classes^2 x thresholds) NumPy loops run as ONE launch of fn_confidence_counts per matrix.

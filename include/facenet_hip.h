@@ -369,6 +369,40 @@ int fn_gallery_search(const float* queries, int Q, const float* gallery, int G, 
                       const int32_t* labels, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* row_labels,
                       float* range, void* stream);
 
+/* ---- face clustering ------------------------------------------------------------------------------------
+ * Radius search: every (query, gallery row) pair with d < eps as a CSR; the [Q, G] matrix never reaches memory.  s, sc and d
+ * (2 (1 - sc) for metric 0, acosf(sc) for metric 1) are those of fn_gallery_search and fn_confidence_counts bit for bit, and the
+ * comparison is the strict fp32 <.  queries, gallery, E, skip, slab_rows and the alignment rule: as fn_gallery_search.
+ * fn_radius_count: offsets int64 [Q + 1] receives the exclusive scan of the rows' neighbour counts (offsets[Q] = nnz); range
+ *   (2 words or NULL): ordered-int min/max of s over all Q x G pairs.  The workspace (fn_radius_workspace bytes for the same Q, G,
+ *   slab_rows) keeps where every (slab, query) writes and goes unchanged to
+ * fn_radius_fill with the same queries, gallery, metric, eps, skip and slab_rows: cols int32 / dist fp32 [capacity] receive each
+ *   row's neighbours in ascending column order (the CSR does not depend on slab_rows).  Nothing is written at or beyond
+ *   `capacity`; it should be offsets[Q], which the caller reads between the two calls.
+ * Neither call allocates or synchronises.
+ *
+ * DBSCAN on the self-join CSR (Q = G = N, skip[i] = i): a row is a core row when degree + 1 >= min_samples; clusters are the
+ * connected components of the core rows; a non-core row with a core neighbour joins the cluster of the core neighbour with the
+ * smallest (bits(d0) << 32 | col) key, d0 the metric-0 distance; every other row is noise, label -1; ids 0 .. C - 1 ascend with
+ * each cluster's smallest core row.
+ * fn_dbscan_init: core int32 [N], labels int32 [N] (the working forest until fn_dbscan_finish), info int32 [8] = {converged,
+ *   rounds run, clusters, noise rows, 4 words of the library's}.
+ * fn_dbscan_rounds: enqueues `rounds` (1 .. 1024) rounds of hooking to the minimum label + pointer jumping; a round does
+ *   nothing once info[0] is set.  The caller reads info[0] and repeats while it is 0.
+ * fn_dbscan_finish, once, after convergence: border rows, consecutive ids, info[2], info[3].  ids: int32 [N] scratch.  metric 0:
+ *   dist IS d0 and emb may be NULL; metric 1: d0 is recomputed from emb fp32 [N, E] (the same fmaf chain).
+ * None of the three allocates or synchronises. */
+int fn_radius_workspace(int Q, int G, int slab_rows, long long* bytes);
+int fn_radius_count(const float* queries, int Q, const float* gallery, int G, int E, int metric, float eps, const int32_t* skip,
+                    int slab_rows, void* workspace, int64_t* offsets, int32_t* range, void* stream);
+int fn_radius_fill(const float* queries, int Q, const float* gallery, int G, int E, int metric, float eps, const int32_t* skip,
+                   int slab_rows, const void* workspace, int32_t* cols, float* dist, long long capacity, void* stream);
+int fn_dbscan_init(int N, const int64_t* offsets, int min_samples, int32_t* labels, int32_t* core, int32_t* info, void* stream);
+int fn_dbscan_rounds(int N, const int64_t* offsets, const int32_t* cols, const int32_t* core, int32_t* labels, int32_t* info,
+                     int rounds, void* stream);
+int fn_dbscan_finish(int N, const int64_t* offsets, const int32_t* cols, const float* dist, int metric, const float* emb, int E,
+                     const int32_t* core, int32_t* labels, int32_t* ids, int32_t* info, void* stream);
+
 /* ---- softmax classifier loss: apps/train_softmax.py:91 (SparseCategoricalCrossentropy(from_logits)); loss: fp32[4] as above;
  * dbias (optional): fixed point, FN_ACC_GRAD_BITS, += column sums of dlogits */
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
