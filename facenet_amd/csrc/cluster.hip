@@ -1,13 +1,11 @@
 // Face clustering: a radius search, "every gallery row nearer than eps" as a CSR, and DBSCAN on that CSR.
 // The [Q, G] distance matrix never reaches memory.
 //
-// Arithmetic (exact): s(q, g) = the ascending-e fmaf chain of identify.hip / validation.hip on v_mfma_f32_16x16x4_f32 (the same
-// staging, identify_stage.h), sc = min(max(s, -1), 1), d = 2 (1 - sc) (metric 0) or acosf(sc) (metric 1): the expressions of
-// confidence_kernel.  (q, g) are neighbours when d < eps, the strict fp32 comparison of ConfidenceMatrix, the classifiers'
-// predict and Gallery.who.  rd_neighbour is that predicate, used by both passes and by nothing else.
+// Arithmetic (exact): pair_tiles.h's, the dot products and distances of identify.hip / validation.hip.  (q, g) are neighbours
+// when pair_distance(s, metric) < eps, the strict fp32 comparison of ConfidenceMatrix, the classifiers' predict and Gallery.who.
 //
-// radius_kernel<FILL>: one workgroup of 4 waves per (64 query rows, slab of gallery rows), wave w = query rows 16w..16w+15, the
-// loop of gallery_search_kernel without its selection.  After a super-tile, for each column tile and accumulator register the
+// radius_kernel<FILL>: one workgroup of 4 waves per (64 query rows, slab of gallery rows), wave w = query rows 16w..16w+15, on
+// pair_tiles.h's walk_gallery.  After a super-tile, for each column tile and accumulator register the
 // 16 lanes of a lane group hold 16 consecutive columns of ONE query row: a ballot gives the group's hits, a hit's position is the
 // row's cursor plus the popcount of the lower hit bits, and the cursor advances by the group's popcount.  Rows belong to one wave
 // and column tiles are met in ascending order: no atomics, no workgroup barrier, columns ascending.  The count pass
@@ -20,28 +18,21 @@
 // are stars again).  A round whose hook met no such edge found the fixed point, each core row labelled by the smallest row of its
 // component, which is unique: scheduling cannot change the result.  Then border rows take the label of the core neighbour with
 // the smallest (bits(d0) << 32 | col) key, and a scan over the roots gives consecutive ids in ascending order of the roots.
-#include "identify_stage.h"
+#include "pair_tiles.h"
 #include "../../include/facenet_hip.h"
 
 namespace fn {
 
 typedef unsigned long long u64;
 
-// THE neighbour predicate; d is what the CSR reports
-__device__ __forceinline__ bool rd_neighbour(float s, int metric, float eps, float& d) {
-    const float sc = fminf(fmaxf(s, -1.f), 1.f);
-    d = (metric == 0) ? 2.f * (1.f - sc) : acosf(sc);
-    return d < eps;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(256, 4) void radius_kernel(const float* __restrict__ queries, int Q, const float* __restrict__ gallery, int G, int E,
                                                      int metric, float eps, const int* __restrict__ skip, int slab_rows, int* __restrict__ counts,
                                                      const long long* __restrict__ base, int* __restrict__ cols, float* __restrict__ dist,
                                                      long long capacity, int* __restrict__ range) {
-    __shared__ __align__(16) float sA[IT][ILD], sB[IT][ILD];
+    __shared__ __align__(16) float sA[F32_TILE][F32_LD], sB[F32_TILE][F32_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lg = lane >> 4;
-    const int q0 = blockIdx.x * IT, slab = blockIdx.y;
+    const int q0 = blockIdx.x * F32_TILE, slab = blockIdx.y;
     const int g0 = slab * slab_rows, g1 = (int)min((long)G, (long)g0 + slab_rows);     // g0 < G < 2^31; the sum may pass it
     const int nq = Q - q0;                                     // >= 1
     const bool wave_live = wave * 16 < nq;
@@ -53,40 +44,10 @@ __global__ __launch_bounds__(256, 4) void radius_kernel(const float* __restrict_
         skip_row[r] = (skip && q < Q) ? skip[q] : -1;
         cursor[r] = (FILL && q < Q) ? base[(long)slab * Q + q] : 0;
     }
-    const int nchunk = (E + IE - 1) / IE, ntile = (g1 - g0 + IT - 1) / IT;
-    const float* qrows = queries + (long)q0 * E;
-    f32x4 acc[4];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float lo = 3e38f, hi = -3e38f;
-    IdChunk next;
-    id_load(next, qrows, nq, gallery + (long)g0 * E, g1 - g0, E, 0, tid);
-    for (int tile = 0; tile < ntile; ++tile) {
-        const int c0 = g0 + tile * IT;                         // first gallery row of the super-tile
-        for (int ch = 0; ch < nchunk; ++ch) {
-            __syncthreads();                                   // the previous chunk has been read
-            id_store(next, sA, sB, tid);
-            __syncthreads();
-            if (ch + 1 < nchunk)
-                id_load(next, qrows, nq, gallery + (long)c0 * E, g1 - c0, E, (ch + 1) * IE, tid);
-            else if (tile + 1 < ntile)
-                id_load(next, qrows, nq, gallery + (long)(c0 + IT) * E, g1 - c0 - IT, E, 0, tid);
-            if (!wave_live) continue;                          // wave-uniform: no query row in this wave's 16
-#pragma unroll
-            for (int blk = 0; blk < IE / 16; ++blk) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(&sA[wave * 16 + lr][blk * 16 + lg * 4]);
-                f32x4 bv[4];
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(&sB[ct * 16 + lr][blk * 16 + lg * 4]);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)       // k ascending per accumulator; the four accumulators are independent
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[ct][s], acc[ct], 0, 0, 0);
-            }
-        }
-        if (!wave_live) continue;
-        // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register.  Column tiles ascending, so each row's hits come out
-        // in ascending column order.
+    DotRange seen;
+    // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register.  Column tiles ascending, so each row's hits come out in
+    // ascending column order.
+    walk_gallery(sA, sB, queries + (long)q0 * E, nq, gallery, g0, g1, E, wave_live, wave * 16, -1, [&](int c0, f32x4 (&acc)[4]) {
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
             const int col = c0 + ct * 16 + lr;
@@ -94,12 +55,9 @@ __global__ __launch_bounds__(256, 4) void radius_kernel(const float* __restrict_
             for (int r = 0; r < 4; ++r) {
                 const float s = acc[ct][r];
                 const bool real = wave * 16 + lg * 4 + r < nq && col < g1;     // padding rows and zero-padded columns: never neighbours
-                if (!FILL && real) {
-                    lo = fminf(lo, s);
-                    hi = fmaxf(hi, s);
-                }
-                float d;
-                const bool hit = rd_neighbour(s, metric, eps, d) && real && col != skip_row[r];
+                if (!FILL && real) seen.add(s);
+                const float d = pair_distance(s, metric);                      // what the CSR reports
+                const bool hit = d < eps && real && col != skip_row[r];
                 const unsigned group = (unsigned)(__ballot(hit) >> (lg * 16)) & 0xffffu;        // the 16 columns of this row
                 if (FILL && hit) {
                     const long long pos = cursor[r] + __popc(group & ((1u << lr) - 1u));
@@ -110,16 +68,10 @@ __global__ __launch_bounds__(256, 4) void radius_kernel(const float* __restrict_
                 }
                 cursor[r] += __popc(group);
             }
-            acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-    }
+    });
     if (FILL) return;
-    lo = -wave_max(-lo);
-    hi = wave_max(hi);
-    if (lane == 0 && range && hi >= lo) {
-        atomicMin(&range[0], id_ord(lo));
-        atomicMax(&range[1], id_ord(hi));
-    }
+    seen.publish(range, lane);
     if (lr == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -229,7 +181,7 @@ __global__ void dbscan_jump_kernel(const int* __restrict__ core, int N, int* __r
 
 // A non-core row with a core neighbour joins the cluster of the core neighbour with the smallest (bits(d0) << 32 | col) key.
 // d0 is the metric-0 distance: the CSR's own for metric 0; for metric 1 it is recomputed from the fmaf chain, which is the MFMA's
-// bit for bit (acosf(sc) does not give sc back).  Also flags the roots for the scan.
+// bit for bit (the arccos does not give sc back).  Also flags the roots for the scan.
 __global__ void dbscan_border_kernel(const long long* __restrict__ offsets, const int* __restrict__ cols, const float* __restrict__ dist, int metric,
                                      const float* __restrict__ emb, int E, const int* __restrict__ core, int N, int* __restrict__ labels,
                                      int* __restrict__ ids, const int* __restrict__ info) {
@@ -244,13 +196,7 @@ __global__ void dbscan_border_kernel(const long long* __restrict__ offsets, cons
     for (long long e = offsets[i]; e < offsets[i + 1]; ++e) {
         const int j = cols[e];
         if (j < 0 || j >= N || !core[j]) continue;
-        float d0 = dist[e];
-        if (metric == 1) {
-            const float *x = emb + (long)i * E, *y = emb + (long)j * E;
-            float s = 0.f;
-            for (int k = 0; k < E; ++k) s = fmaf(x[k], y[k], s);
-            d0 = 2.f * (1.f - fminf(fmaxf(s, -1.f), 1.f));
-        }
+        const float d0 = metric == 1 ? pair_distance(dot_chain(emb + (long)i * E, emb + (long)j * E, E), 0) : dist[e];
         const u64 key = ((u64)__float_as_uint(d0) << 32) | (unsigned)j;
         best = key < best ? key : best;
     }
@@ -280,33 +226,15 @@ __global__ void dbscan_relabel_kernel(const int* __restrict__ ids, int N, int* _
     if ((threadIdx.x & 63) == 0 && noise) atomicAdd(&info[DB_NOISE], __popcll(noise));
 }
 
-static int rd_check(const char* what, int Q, int G, int slab_rows, int* srows, int* slabs) {
-    FN_REQUIRE(Q >= 1 && G >= 1, "%s: Q and G must be at least 1 (Q %d, G %d)", what, Q, G);
-    FN_REQUIRE(slab_rows >= 0, "%s: bad arguments", what);
-    *slabs = id_slabs(Q, G, slab_rows, srows);
-    FN_REQUIRE(*slabs <= 65535, "%s: %d slabs of %d rows (at most 65535)", what, *slabs, *srows);
-    return FN_OK;
-}
-
 // workspace: base int64 [slabs][Q], then counts int32 [slabs][Q]
 static long long rd_base_bytes(int slabs, int Q) { return (long long)slabs * Q * (long long)sizeof(long long); }
-
-static int rd_check_call(const char* what, const void* queries, const void* gallery, const void* workspace, int E, int metric, float eps) {
-    FN_REQUIRE(E >= 4 && E % 4 == 0 && E <= 512, "%s: the embedding length must be a multiple of 4 in [4, 512] (E %d)", what, E);
-    FN_REQUIRE(metric == 0 || metric == 1, "Undefined similarity metric %d", metric);   // statistics.py:55
-    FN_REQUIRE(eps == eps, "%s: eps is NaN", what);
-    FN_REQUIRE(queries && gallery && workspace, "%s: bad arguments", what);
-    FN_REQUIRE(((uintptr_t)queries | (uintptr_t)gallery | (uintptr_t)workspace) % 16 == 0,
-               "%s: queries, gallery and workspace must be 16-byte aligned", what);
-    return FN_OK;
-}
 
 }  // namespace fn
 using namespace fn;
 
 extern "C" int fn_radius_workspace(int Q, int G, int slab_rows, long long* bytes) {
     int srows, slabs;
-    if (int rc = rd_check("radius_workspace", Q, G, slab_rows, &srows, &slabs)) return rc;
+    if (int rc = check_walk_shape("radius_workspace", Q, G, slab_rows, &srows, &slabs)) return rc;
     FN_REQUIRE(bytes, "radius_workspace: bad arguments");
     *bytes = rd_base_bytes(slabs, Q) + (long long)slabs * Q * (long long)sizeof(int);
     return FN_OK;
@@ -315,14 +243,15 @@ extern "C" int fn_radius_workspace(int Q, int G, int slab_rows, long long* bytes
 extern "C" int fn_radius_count(const float* queries, int Q, const float* gallery, int G, int E, int metric, float eps, const int32_t* skip,
                                int slab_rows, void* workspace, int64_t* offsets, int32_t* range, void* stream) {
     int srows, slabs;
-    if (int rc = rd_check("radius_count", Q, G, slab_rows, &srows, &slabs)) return rc;
-    if (int rc = rd_check_call("radius_count", queries, gallery, workspace, E, metric, eps)) return rc;
+    if (int rc = check_walk_shape("radius_count", Q, G, slab_rows, &srows, &slabs)) return rc;
+    if (int rc = check_walk_args("radius_count", queries, gallery, workspace, E, metric)) return rc;
+    FN_REQUIRE(eps == eps, "radius_count: eps is NaN");
     FN_REQUIRE(offsets && (uintptr_t)offsets % 8 == 0, "radius_count: offsets must be an 8-byte aligned int64 [Q + 1]");
     hipStream_t st = (hipStream_t)stream;
     long long* base = (long long*)workspace;
     int* counts = (int*)((char*)workspace + rd_base_bytes(slabs, Q));
     if (range) fill_words(range, 0x7f7fffffu, 0x80800000u, 2, st);
-    hipLaunchKernelGGL(radius_kernel<false>, dim3((unsigned)cdiv(Q, IT), (unsigned)slabs), dim3(256), 0, st, queries, Q, gallery, G, E, metric, eps,
+    hipLaunchKernelGGL(radius_kernel<false>, dim3((unsigned)cdiv(Q, F32_TILE), (unsigned)slabs), dim3(256), 0, st, queries, Q, gallery, G, E, metric, eps,
                        (const int*)skip, srows, counts, (const long long*)nullptr, (int*)nullptr, (float*)nullptr, 0LL, (int*)range);
     hipLaunchKernelGGL(radius_scan_kernel, dim3(1), dim3(SCAN_T), 0, st, (const int*)counts, slabs, Q, base, (long long*)offsets);
     return check_launch("radius_count");
@@ -331,11 +260,12 @@ extern "C" int fn_radius_count(const float* queries, int Q, const float* gallery
 extern "C" int fn_radius_fill(const float* queries, int Q, const float* gallery, int G, int E, int metric, float eps, const int32_t* skip,
                               int slab_rows, const void* workspace, int32_t* cols, float* dist, long long capacity, void* stream) {
     int srows, slabs;
-    if (int rc = rd_check("radius_fill", Q, G, slab_rows, &srows, &slabs)) return rc;
-    if (int rc = rd_check_call("radius_fill", queries, gallery, workspace, E, metric, eps)) return rc;
+    if (int rc = check_walk_shape("radius_fill", Q, G, slab_rows, &srows, &slabs)) return rc;
+    if (int rc = check_walk_args("radius_fill", queries, gallery, workspace, E, metric)) return rc;
+    FN_REQUIRE(eps == eps, "radius_fill: eps is NaN");
     FN_REQUIRE(capacity >= 0 && (capacity == 0 || (cols && dist)), "radius_fill: cols and dist must hold `capacity` >= 0 elements");
     if (capacity == 0) return FN_OK;
-    hipLaunchKernelGGL(radius_kernel<true>, dim3((unsigned)cdiv(Q, IT), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, queries, Q, gallery, G,
+    hipLaunchKernelGGL(radius_kernel<true>, dim3((unsigned)cdiv(Q, F32_TILE), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, queries, Q, gallery, G,
                        E, metric, eps, (const int*)skip, srows, (int*)nullptr, (const long long*)workspace, (int*)cols, dist, capacity,
                        (int*)nullptr);
     return check_launch("radius_fill");

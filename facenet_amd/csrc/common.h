@@ -175,14 +175,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + (bid >> 3);
 }
 
-// ---- staging of exact-fp32 MFMA operand tiles (v_mfma_f32_16x16x4_f32), ONE definition for validation.hip and identify.hip:
-// both must multiply in the same k order for their distances to agree bit for bit.  64 x 64 super-tiles, 32-wide embedding
-// chunks, LDS rows of 36 floats (16-byte aligned, conflict-free ds_read_b128 per 16 lanes).  Column c of a chunk goes to LDS
-// position f32_chunk_pos(c): inside each block of 16 the 4x4 (step, lane group) index is transposed, so that the float4 a lane
-// of group g reads holds k = 4s + g for the four MFMA steps s = 0..3 in order.
-constexpr int F32_TILE = 64, F32_CHUNK = 32, F32_LD = F32_CHUNK + 4;
-__device__ __forceinline__ int f32_chunk_pos(int c) { return (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3); }
-
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // integer tuning aid / switch from the environment; callers keep it in a function-local `static const int`: read once per process

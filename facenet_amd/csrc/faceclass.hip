@@ -7,7 +7,7 @@
 // therefore has the same bits in fn_f2f_distance, fn_f2f_pair_counts and the training loss, and the counts equal
 // (fn_f2f_distance < threshold).sum() exactly.  fp32 throughout: the decision d < threshold is taken on fp32 values.
 // DESIGN.md section 12.
-#include "common.h"
+#include "pair_tiles.h"      // tri_decode
 #include "../../include/facenet_hip.h"
 
 namespace fn {
@@ -83,14 +83,6 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// (i, k), k <= i, from the linear index b = i (i + 1) / 2 + k
-__device__ __forceinline__ void tri_decode(long b, int& i, int& k) {
-    i = (int)((sqrtf(8.f * (float)b + 1.f) - 1.f) * 0.5f);
-    while ((long)i * (i + 1) / 2 > b) --i;
-    while ((long)(i + 1) * (i + 2) / 2 <= b) ++i;
-    k = (int)(b - (long)i * (i + 1) / 2);
 }
 
 // ---- norms -----------------------------------------------------------------------------------------------------------------

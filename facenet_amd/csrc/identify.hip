@@ -9,13 +9,12 @@
 // lanes meet the candidates in.  All ones is "no candidate".
 //
 // gallery_search_kernel: one workgroup per (64 query rows, slab of gallery rows).  The slab is walked in 64-column
-// super-tiles staged as in confidence_folds_kernel (32-wide chunks, opos transposition, wave w = query rows 16w..16w+15
-// against four 16x16 column tiles); the next chunk's global loads are in flight while the current one is multiplied.  After
+// super-tiles by pair_tiles.h's walk_gallery (wave w = query rows 16w..16w+15 against four 16x16 column tiles).  After
 // a super-tile each lane compares its 16 values with its rows' current k-th best key (LDS, all ones until a row has k
 // candidates) and appends the survivors to the row's list; a list that cannot take another column tile is cut to its k
 // smallest by the wave that owns the row.  Rows belong to one wave: selection needs no workgroup barrier.
 // gallery_merge_kernel: one wave per query cuts the slabs' k-lists to the final k and writes distances, rows and labels.
-#include "identify_stage.h"      // IT, IE, ILD, IdChunk, id_load, id_store, id_ord, id_slabs: shared with cluster.hip
+#include "pair_tiles.h"
 #include "../../include/facenet_hip.h"
 
 namespace fn {
@@ -58,16 +57,16 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
                                                              int E, int k, const int* __restrict__ skip, int slab_rows, int split, u64* __restrict__ partial,
                                                              int* __restrict__ range) {
     extern __shared__ __align__(16) unsigned char dyn[];
-    __shared__ __align__(16) float sA[IT][ILD], sB[IT][ILD];
-    __shared__ u64 sThr[IT];
-    __shared__ int sCnt[IT];
+    __shared__ __align__(16) float sA[F32_TILE][F32_LD], sB[F32_TILE][F32_LD];
+    __shared__ u64 sThr[F32_TILE];
+    __shared__ int sCnt[F32_TILE];
     const int cap = id_cap(k);
-    u64* sList = reinterpret_cast<u64*>(dyn);                  // [IT][cap]
+    u64* sList = reinterpret_cast<u64*>(dyn);                  // [F32_TILE][cap]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lg = lane >> 4;
-    const int q0 = blockIdx.x * IT, slab = blockIdx.y;
+    const int q0 = blockIdx.x * F32_TILE, slab = blockIdx.y;
     const int g0 = slab * slab_rows, g1 = (int)min((long)G, (long)g0 + slab_rows);     // g0 < G < 2^31; the sum may pass it
     const int nq = Q - q0;                                     // >= 1
-    if (tid < IT) {
+    if (tid < F32_TILE) {
         sThr[tid] = INONE;
         sCnt[tid] = 0;
     }
@@ -81,53 +80,14 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
         const int q = q0 + qwave * 16 + lg * 4 + r;
         skip_row[r] = (skip && q < Q) ? skip[q] : -1;
     }
-    const int nchunk = (E + IE - 1) / IE, ntile = (g1 - g0 + IT - 1) / IT;
-    const float* qrows = queries + (long)q0 * E;
-    f32x4 acc[4];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float lo = 3e38f, hi = -3e38f;
-    IdChunk next;
-    id_load(next, qrows, nq, gallery + (long)g0 * E, g1 - g0, E, 0, tid);
-    for (int tile = 0; tile < ntile; ++tile) {
-        const int c0 = g0 + tile * IT;                         // first gallery row of the super-tile
-        for (int ch = 0; ch < nchunk; ++ch) {
-            __syncthreads();                                   // the previous chunk has been read (and the lists initialised)
-            id_store(next, sA, sB, tid);
-            __syncthreads();
-            if (ch + 1 < nchunk)
-                id_load(next, qrows, nq, gallery + (long)c0 * E, g1 - c0, E, (ch + 1) * IE, tid);
-            else if (tile + 1 < ntile)
-                id_load(next, qrows, nq, gallery + (long)(c0 + IT) * E, g1 - c0 - IT, E, 0, tid);
-            if (!wave_live) continue;                          // wave-uniform: no query row in this wave's 16
-#pragma unroll
-            for (int blk = 0; blk < IE / 16; ++blk) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(&sA[qwave * 16 + lr][blk * 16 + lg * 4]);
-                if (split) {                      // wave-uniform
-                    const f32x4 bv = *reinterpret_cast<const f32x4*>(&sB[wave * 16 + lr][blk * 16 + lg * 4]);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc[0], 0, 0, 0);
-                    continue;
-                }
-                f32x4 bv[4];
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(&sB[ct * 16 + lr][blk * 16 + lg * 4]);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)       // k ascending per accumulator; the four accumulators are independent
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[ct][s], acc[ct], 0, 0, 0);
-            }
-        }
-        if (!wave_live) continue;
-        // selection: C/D layout column = lane & 15, row = 4 (lane >> 4) + register
+    DotRange seen;
+    // selection after each super-tile: C/D layout column = lane & 15, row = 4 (lane >> 4) + register
+    walk_gallery(sA, sB, queries + (long)q0 * E, nq, gallery, g0, g1, E, wave_live, qwave * 16, split ? wave * 16 : -1, [&](int c0, f32x4 (&acc)[4]) {
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
             if (split && ct > 0) break;                        // split: accumulator 0 holds column tile `wave`
             const int tcol = c0 + (split ? wave : ct) * 16;
-            if (tcol >= g1) {                                  // beyond the slab: zero-padded columns, never candidates
-                acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                continue;
-            }
+            if (tcol >= g1) continue;                          // beyond the slab: zero-padded columns, never candidates
             const int col = tcol + lr;
             bool appended = false;
 #pragma unroll
@@ -135,19 +95,15 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
                 const int row = wave * 16 + lg * 4 + r;         // the list; the query row is qwave * 16 + lg * 4 + r
                 const float s = acc[ct][r];
                 if (qwave * 16 + lg * 4 + r >= nq || col >= g1) continue;          // padding rows and zero-padded columns are never candidates
-                lo = fminf(lo, s);
-                hi = fmaxf(hi, s);
+                seen.add(s);
                 if (col == skip_row[r]) continue;
-                const float sc = fminf(fmaxf(s, -1.f), 1.f);
-                const float d0 = 2.f * (1.f - sc);
-                const u64 key = ((u64)__float_as_uint(d0) << 32) | (unsigned)col;
+                const u64 key = ((u64)__float_as_uint(pair_distance(s, 0)) << 32) | (unsigned)col;
                 if (key < sThr[row]) {
                     const int slot = atomicAdd(&sCnt[row], 1);  // < cap: a row holds <= cap - 16 before a column tile adds <= 16
                     sList[row * cap + slot] = key;
                     appended = true;
                 }
             }
-            acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (__ballot(appended) == 0ull) continue;          // the common case once the thresholds are tight
             __builtin_amdgcn_wave_barrier();
             const int cnt = lane < 16 ? sCnt[wave * 16 + lane] : 0;
@@ -160,13 +116,8 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
             }
             __builtin_amdgcn_wave_barrier();
         }
-    }
-    lo = -wave_max(-lo);
-    hi = wave_max(hi);
-    if (lane == 0 && range && hi >= lo) {
-        atomicMin(&range[0], id_ord(lo));
-        atomicMax(&range[1], id_ord(hi));
-    }
+    });
+    seen.publish(range, lane);
     __syncthreads();                                           // also orders the list initialisation for an empty slab walk
     const long pslab = split ? (long)slab * 4 + wave : slab;
     for (int r = 0; r < 16; ++r) {                             // ascending k-list of every list of this wave -> partial[pslab][q][k]
@@ -217,13 +168,7 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(const u64* __restrict
     const u64 key = sList[lane];
     const int row = (int)(unsigned)(key & 0xffffffffull);
     float d = __uint_as_float((unsigned)(key >> 32));
-    if (metric == 1) {
-        const float* x = queries + (long)q * E;
-        const float* y = gallery + (long)row * E;
-        float s = 0.f;
-        for (int e = 0; e < E; ++e) s = fmaf(x[e], y[e], s);
-        d = acosf(fminf(fmaxf(s, -1.f), 1.f));
-    }
+    if (metric == 1) d = pair_distance(dot_chain(queries + (long)q * E, gallery + (long)row * E, E), 1);
     dist[o] = d;
     rows[o] = row;
     if (row_labels) row_labels[o] = labels[row];
@@ -232,21 +177,14 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(const u64* __restrict
 // partial lists per (slab, query): four when the waves split the column tiles (Q <= 16), else one
 static int id_lists(int Q) { return Q <= 16 ? 4 : 1; }
 
-static int id_check_shape(int Q, int G, int k) {
-    FN_REQUIRE(Q >= 1 && G >= 1, "gallery_search: Q and G must be at least 1 (Q %d, G %d)", Q, G);
-    FN_REQUIRE(k >= 1 && k <= IMAXK, "gallery_search: k must be in [1, 64] (k %d)", k);
-    return FN_OK;
-}
-
 }  // namespace fn
 using namespace fn;
 
 extern "C" int fn_gallery_search_workspace(int Q, int G, int k, int slab_rows, long long* bytes) {
-    if (int rc = id_check_shape(Q, G, k)) return rc;
     FN_REQUIRE(bytes && slab_rows >= 0, "gallery_search_workspace: bad arguments");
-    int rows;
-    const int slabs = id_slabs(Q, G, slab_rows, &rows);
-    FN_REQUIRE(slabs <= 65535, "gallery_search: %d slabs of %d rows (at most 65535)", slabs, rows);
+    int srows, slabs;
+    if (int rc = check_walk_shape("gallery_search", Q, G, slab_rows, &srows, &slabs)) return rc;
+    FN_REQUIRE(k >= 1 && k <= IMAXK, "gallery_search: k must be in [1, 64] (k %d)", k);
     *bytes = (long long)slabs * id_lists(Q) * Q * k * (long long)sizeof(u64);
     return FN_OK;
 }
@@ -254,20 +192,16 @@ extern "C" int fn_gallery_search_workspace(int Q, int G, int k, int slab_rows, l
 extern "C" int fn_gallery_search(const float* queries, int Q, const float* gallery, int G, int E, int k, int metric, const int32_t* skip,
                                  const int32_t* labels, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* row_labels,
                                  float* range, void* stream) {
-    if (int rc = id_check_shape(Q, G, k)) return rc;
-    FN_REQUIRE(E >= 4 && E % 4 == 0 && E <= 512, "gallery_search: the embedding length must be a multiple of 4 in [4, 512] (E %d)", E);
-    FN_REQUIRE(metric == 0 || metric == 1, "Undefined similarity metric %d", metric);   // statistics.py:55
-    FN_REQUIRE(queries && gallery && workspace && dist && rows && slab_rows >= 0, "gallery_search: bad arguments");
-    FN_REQUIRE(((uintptr_t)queries | (uintptr_t)gallery | (uintptr_t)workspace) % 16 == 0,
-               "gallery_search: queries, gallery and workspace must be 16-byte aligned");
+    int srows, slabs;
+    if (int rc = check_walk_shape("gallery_search", Q, G, slab_rows, &srows, &slabs)) return rc;
+    FN_REQUIRE(k >= 1 && k <= IMAXK, "gallery_search: k must be in [1, 64] (k %d)", k);
+    if (int rc = check_walk_args("gallery_search", queries, gallery, workspace, E, metric)) return rc;
+    FN_REQUIRE(dist && rows, "gallery_search: bad arguments");
     FN_REQUIRE(!row_labels || labels, "gallery_search: row_labels needs labels");
-    int srows;
-    const int slabs = id_slabs(Q, G, slab_rows, &srows);
-    FN_REQUIRE(slabs <= 65535, "gallery_search: %d slabs of %d rows (at most 65535)", slabs, srows);
     hipStream_t st = (hipStream_t)stream;
     if (range) fill_words(range, 0x7f7fffffu, 0x80800000u, 2, st);
-    const size_t dyn = (size_t)IT * id_cap(k) * sizeof(u64);   // <= 40 KiB; with the static tiles below the 64 KiB default
-    hipLaunchKernelGGL(gallery_search_kernel, dim3((unsigned)cdiv(Q, IT), (unsigned)slabs), dim3(256), dyn, st, queries, Q, gallery, G, E, k,
+    const size_t dyn = (size_t)F32_TILE * id_cap(k) * sizeof(u64);   // <= 40 KiB; with the static tiles below the 64 KiB default
+    hipLaunchKernelGGL(gallery_search_kernel, dim3((unsigned)cdiv(Q, F32_TILE), (unsigned)slabs), dim3(256), dyn, st, queries, Q, gallery, G, E, k,
                        (const int*)skip, srows, (int)(id_lists(Q) == 4), (u64*)workspace, (int*)range);
     hipLaunchKernelGGL(gallery_merge_kernel, dim3((unsigned)Q), dim3(64), 0, st, (const u64*)workspace, slabs * id_lists(Q), Q, k, metric, queries, gallery,
                        E, (const int*)labels, dist, (int*)rows, (int*)row_labels);

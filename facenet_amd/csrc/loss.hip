@@ -7,15 +7,10 @@
 //  * softmax cross-entropy = SparseCategoricalCrossentropy(from_logits=True), apps/train_softmax.py:91.
 //  * center loss + its center update = facenet/facenet.py:204-217 (center_loss); prelogits norm = the
 //    loss.prelogits_norm_* keys of apps/configs/train_softmax.yaml:73-78 (formula: DESIGN.md section 11).
-#include "common.h"
+#include "pair_tiles.h"      // ord_f32, DotRange, pair_distance: shared with the validation, identification and clustering kernels
 #include "../../include/facenet_hip.h"
 
 namespace fn {
-
-__device__ __forceinline__ int f2ord_i(float f) {  // order-preserving float -> int
-    int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
 
 // out[i][j] for i<n, j<m ; range[0]=ord(min dot) via atomicMin, range[1]=ord(max dot) via atomicMax
 __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__ xa, const float* __restrict__ xb, float* __restrict__ out,
@@ -35,7 +30,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
 #pragma unroll
     for (int t = 0; t < 8; ++t) asq = __fmaf_rn(a[t], a[t], asq);
     asq = wave_sum(asq);
-    float lo = 3e38f, hi = -3e38f;
+    DotRange seen;
     for (int j = jb; j < min(m, jb + 16); ++j) {
         float d = 0.f, bsq = 0.f;
 #pragma unroll
@@ -50,17 +45,12 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
             bsq = wave_sum(bsq);
             r = fmaxf(__fmaf_rn(-2.f, d, asq + bsq), 0.f);
         } else {
-            lo = fminf(lo, d);
-            hi = fmaxf(hi, d);
-            const float s = fminf(fmaxf(d, -1.f), 1.f);   // statistics.py:45-46
-            r = (metric == 0) ? 2.f * (1.f - s) : acosf(s);  // :48-53
+            seen.add(d);
+            r = pair_distance(d, metric);
         }
         if (lane == 0) out[(long)i * m + j] = r;
     }
-    if (range && lane == 0 && metric != 2) {
-        atomicMin(&range[0], f2ord_i(lo));
-        atomicMax(&range[1], f2ord_i(hi));
-    }
+    if (range && lane == 0 && metric != 2) seen.write(range);    // d is wave-uniform, and this wave has evaluated a pair
 }
 
 __device__ __forceinline__ unsigned hash_mix(unsigned h, unsigned v) {

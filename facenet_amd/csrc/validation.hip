@@ -8,15 +8,10 @@
 // embedding chunks (fp32 FMA: thresholds are compared exactly, so no low-precision MFMA here), every distance is
 // binned once by upper_bound over the ascending thresholds into an LDS histogram, a prefix sum turns the histogram into
 // "count(sims < threshold[n])" for all n at once, and the weighted tp/fn or fp/tn contributions go out as fp64 atomics.
-#include "common.h"
+#include "pair_tiles.h"
 #include "../../include/facenet_hip.h"
 
 namespace fn {
-
-__device__ __forceinline__ int f2ord_i2(float f) {
-    int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
 
 constexpr int VT = 32;        // images per tile side
 constexpr int VE = 64;        // embedding chunk
@@ -30,11 +25,8 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
     __shared__ int sHist[VMAXT + 1];
     const int tid = threadIdx.x;
     // class pair (i >= k) from the linear block id
-    const long b = blockIdx.x;
-    int i = (int)((sqrtf(8.f * (float)b + 1.f) - 1.f) * 0.5f);
-    while ((long)i * (i + 1) / 2 > b) --i;
-    while ((long)(i + 1) * (i + 2) / 2 <= b) ++i;
-    const int k = (int)(b - (long)i * (i + 1) / 2);
+    int i, k;
+    tri_decode(blockIdx.x, i, k);
     const int a0 = cls_start[i], na = cls_start[i + 1] - a0;
     const int b0 = cls_start[k], nb = cls_start[k + 1] - b0;
     const long P = (i == k) ? (long)na * (na - 1) / 2 : (long)na * nb;
@@ -43,7 +35,7 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
     for (int t = tid; t <= T; t += 256) sHist[t] = 0;
     __syncthreads();
     const int ar = tid >> 3, bc = (tid & 7) * 4;         // thread -> row ar of the A tile, 4 consecutive rows of the B tile
-    float lo = 3e38f, hi = -3e38f;
+    DotRange seen;
     for (int ta = 0; ta < na; ta += VT)
         for (int tb = 0; tb < nb; tb += VT) {
             if (i == k && tb + VT - 1 <= ta) continue;   // tile entirely on/below the diagonal: no pair with b > a
@@ -67,25 +59,11 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
             for (int j = 0; j < 4; ++j) {
                 const int ia = ta + ar, ib = tb + bc + j;
                 if (ia >= na || ib >= nb || (i == k && ib <= ia)) continue;   // strict upper triangle (:32-34)
-                const float s = acc[j];
-                lo = fminf(lo, s);
-                hi = fmaxf(hi, s);
-                const float sc = fminf(fmaxf(s, -1.f), 1.f);                  // :45-46
-                const float d = (metric == 0) ? 2.f * (1.f - sc) : acosf(sc); // :48-53
-                int l = 0, h = T;                                             // first n with thr[n] > d  (d < thr[n] counts)
-                while (l < h) {
-                    const int m = (l + h) >> 1;
-                    if (sThr[m] > d) h = m; else l = m + 1;
-                }
-                atomicAdd(&sHist[l], 1);
+                seen.add(acc[j]);
+                atomicAdd(&sHist[threshold_bin(sThr, T, pair_distance(acc[j], metric))], 1);     // d < thr[n] counts
             }
         }
-    lo = -wave_max(-lo);
-    hi = wave_max(hi);
-    if ((tid & 63) == 0 && range) {
-        atomicMin(&range[0], f2ord_i2(lo));
-        atomicMax(&range[1], f2ord_i2(hi));
-    }
+    seen.publish(range, tid & 63);
     __syncthreads();
     if (tid == 0) {                                       // prefix: sHist[n] = count(sims < thr[n])
         int run = 0;
@@ -111,36 +89,12 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
 // Every pair adds 1 to touch[fa] and 1 to touch[fb] (fa != fb) or to touch[fa] and `same` (fa == fb): two LDS atomics
 // spread over the folds' rows, and total = (sum_f touch_f + same) / 2 comes out in the epilogue.
 //
-// Dot products run on v_mfma_f32_16x16x4_f32, which is bit for bit the ascending-k fmaf chain of confidence_kernel (a
-// zero-padded k adds fma(0, 0, acc) = acc), so both kernels bin identical distances.  One workgroup walks class pairs
-// with a stride (diagonal pairs and off-diagonal pairs in separate workgroups), covers each pair with 64x64 super-tiles
-// (wave w: rows 16w..16w+15 against four 16x16 column tiles, empty tiles skipped) and keeps the weighted fp64 tables in
+// Dot products run on v_mfma_f32_16x16x4_f32 (pair_tiles.h's staging and mfma_chunk), which is bit for bit the ascending-k fmaf
+// chain of confidence_kernel (a zero-padded k adds fma(0, 0, acc) = acc), so both kernels bin identical distances.
+// One workgroup walks class pairs with a stride (diagonal pairs and off-diagonal pairs in separate workgroups), covers each
+// pair with 64x64 super-tiles (wave w: rows 16w..16w+15 against four 16x16 column tiles, empty tiles skipped) and keeps the weighted fp64 tables in
 // LDS until it has seen all its pairs: the global fp64 atomics happen once per workgroup, not once per class pair.
-constexpr int OT = F32_TILE;    // rows / columns of a super-tile
-constexpr int OE = F32_CHUNK;   // embedding chunk
-constexpr int OLD = F32_LD;     // LDS row stride in floats
 constexpr int OMAXF = 16;       // folds
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int opos(int c) { return f32_chunk_pos(c); }     // common.h: shared with identify.hip
-
-__device__ __forceinline__ void stage_rows(float (*dst)[OLD], const float* __restrict__ src, int rows, int E, int e0, bool vec, int tid) {
-    if (vec) {                                            // E % 4 == 0: rows are 16-byte aligned
-        for (int t = tid; t < OT * (OE / 4); t += 256) {
-            const int r = t >> 3, c = (t & 7) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < rows && e0 + c < E) v = *reinterpret_cast<const float4*>(src + (long)r * E + e0 + c);
-            const int p = opos(c);                        // c % 4 == 0: the four elements are lane groups 0..3 of one step
-            dst[r][p] = v.x; dst[r][p + 4] = v.y; dst[r][p + 8] = v.z; dst[r][p + 12] = v.w;
-        }
-    } else {
-        for (int t = tid; t < OT * OE; t += 256) {
-            const int r = t >> 5, c = t & 31;
-            dst[r][opos(c)] = (r < rows && e0 + c < E) ? src[(long)r * E + e0 + c] : 0.f;
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __restrict__ emb, const int* __restrict__ cls_start,
                                                                const int* __restrict__ fold, const int* __restrict__ train_rows,
@@ -148,7 +102,7 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
                                                                const float* __restrict__ thr, int T, int metric, double* __restrict__ out,
                                                                int* __restrict__ range, int diag_groups, int off_groups) {
     extern __shared__ __align__(16) unsigned char dyn[];
-    __shared__ __align__(16) float sA[OT][OLD], sB[OT][OLD];
+    __shared__ __align__(16) float sA[F32_TILE][F32_LD], sB[F32_TILE][F32_LD];
     __shared__ float sThr[VMAXT];
     __shared__ double sP[OMAXF], sW[OMAXF];
     const int HS = T + 1;
@@ -162,17 +116,14 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
     const long stride = diag ? diag_groups : off_groups;
     const bool vec = (E & 3) == 0;
     const int lr = lane & 15, lg = lane >> 4;
-    float lo = 3e38f, hi = -3e38f;
+    DotRange seen;
     for (long b = diag ? (long)blockIdx.x : (long)blockIdx.x - diag_groups; b < npairs; b += stride) {
         int i, k;
         if (diag) {
             i = k = (int)b;
         } else {                                          // b = j (j + 1) / 2 + k with k <= j, i = j + 1 > k
-            int j = (int)((sqrtf(8.f * (float)b + 1.f) - 1.f) * 0.5f);
-            while ((long)j * (j + 1) / 2 > b) --j;
-            while ((long)(j + 1) * (j + 2) / 2 <= b) ++j;
-            k = (int)(b - (long)j * (j + 1) / 2);
-            i = j + 1;
+            tri_decode(b, i, k);
+            i += 1;
         }
         const int a0 = cls_start[i], na = cls_start[i + 1] - a0;
         const int b0 = cls_start[k], nb = cls_start[k + 1] - b0;
@@ -186,9 +137,9 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
             sP[tid] = (double)P;
             sW[tid] = (double)P * (diag ? (double)Cf : (double)Cf * (Cf - 1) * 0.5);
         }
-        for (int ta = 0; ta < na; ta += OT)
-            for (int tb = 0; tb < nb; tb += OT) {
-                if (diag && tb + OT - 1 <= ta) continue;  // super-tile entirely on/below the diagonal
+        for (int ta = 0; ta < na; ta += F32_TILE)
+            for (int tb = 0; tb < nb; tb += F32_TILE) {
+                if (diag && tb + F32_TILE - 1 <= ta) continue;  // super-tile entirely on/below the diagonal
                 const int r0 = ta + wave * 16;            // this wave's 16 rows
                 bool live[4];
 #pragma unroll
@@ -199,22 +150,12 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
                 f32x4 acc[4];
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int e0 = 0; e0 < E; e0 += OE) {
+                for (int e0 = 0; e0 < E; e0 += F32_CHUNK) {
                     __syncthreads();
                     stage_rows(sA, emb + (long)(a0 + ta) * E, na - ta, E, e0, vec, tid);
                     stage_rows(sB, emb + (long)(b0 + tb) * E, nb - tb, E, e0, vec, tid);
                     __syncthreads();
-#pragma unroll
-                    for (int blk = 0; blk < OE / 16; ++blk) {
-                        const f32x4 av = *reinterpret_cast<const f32x4*>(&sA[wave * 16 + lr][blk * 16 + lg * 4]);
-#pragma unroll
-                        for (int ct = 0; ct < 4; ++ct) {
-                            if (!live[ct]) continue;      // wave-uniform
-                            const f32x4 bv = *reinterpret_cast<const f32x4*>(&sB[ct * 16 + lr][blk * 16 + lg * 4]);
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc[ct], 0, 0, 0);
-                        }
-                    }
+                    mfma_chunk(sA, sB, wave * 16, acc, live);
                 }
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
@@ -227,17 +168,8 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
                         if (ia >= na || ib >= nb || (diag && ib <= ia)) continue;      // strict upper triangle (:32-34)
                         const int fa = fold[a0 + ia];
                         const float s = acc[ct][r];
-                        if (F >= 3 || fa == fb) {         // the pair is in at least one training part
-                            lo = fminf(lo, s);
-                            hi = fmaxf(hi, s);
-                        }
-                        const float sc = fminf(fmaxf(s, -1.f), 1.f);                    // :45-46
-                        const float d = (metric == 0) ? 2.f * (1.f - sc) : acosf(sc);   // :48-53
-                        int l = 0, h = T;                                               // first n with thr[n] > d
-                        while (l < h) {
-                            const int m = (l + h) >> 1;
-                            if (sThr[m] > d) h = m; else l = m + 1;
-                        }
+                        if (F >= 3 || fa == fb) seen.add(s);          // the pair is in at least one training part
+                        const int l = threshold_bin(sThr, T, pair_distance(s, metric));
                         atomicAdd(&sHist[fa * HS + l], 1);
                         atomicAdd(&sHist[(fa == fb ? F : fb) * HS + l], 1);
                     }
@@ -275,12 +207,7 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
             sAcc[(f * 2 + 1) * T + n] += (P - c) / sW[f];
         }
     }
-    lo = -wave_max(-lo);
-    hi = wave_max(hi);
-    if (lane == 0 && range) {
-        atomicMin(&range[0], f2ord_i2(lo));
-        atomicMax(&range[1], f2ord_i2(hi));
-    }
+    seen.publish(range, lane);
     __syncthreads();                                      // a workgroup whose pairs were all empty reads the zeros others wrote
     for (int t = tid; t < F * T; t += 256) {
         const int f = t / T, n = t - f * T;

@@ -18,6 +18,7 @@ DBSCAN on the self-join (fn_dbscan_*) and returns a `Clustering`; ``FacePipeline
 photographs without their embeddings leaving the device."""
 from __future__ import annotations
 
+import ctypes
 from pathlib import Path
 
 import numpy as np
@@ -26,7 +27,7 @@ import torch
 from . import _lib
 from .detectors.face_detector import image_processing_batch
 from .faceclass import _as_table, _ptr, _stream
-from .statistics import _decode_ord
+from .statistics import check_unit_range
 
 BATCH_SIZES = (1, 4, 16, 64, 256)
 
@@ -219,45 +220,51 @@ class Gallery:
         return (f"{self.__class__.__name__}\n" + f"Number of classes {self.nrof_classes} \n" + f"Number of images {self.nrof_images}\n" +
                 f"Embedding length {self.length}\n" + f"metric: {self.metric}\n")
 
-    def _search(self, queries, k, skip, slab_rows, atol):
-        """-> device (dist [Q, k], rows [Q, k]) after every check of `search`."""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+    def _queries(self, queries, skip, runs):
+        """The checks `search` and `within` share -> (Q, the queries as a device table, the int32 skip tensor or None); for
+        Q = 0 the last two are None, and nothing needs a device.  ``runs``: what the caller runs, for the error without one."""
         shape = tuple(queries.shape) if hasattr(queries, "shape") else np.shape(queries)
         if len(shape) != 2:
             raise ValueError(f"queries must be a 2-D [Q, E] array, got shape {shape}")
         if shape[1] != self.length:
             raise ValueError(f"embedding lengths differ: queries {shape[1]}, gallery {self.length}")
-        Q, G = shape[0], self.nrof_images
+        Q = shape[0]
         if skip is not None:
             skip = np.asarray(skip.cpu() if torch.is_tensor(skip) else skip)
             if skip.shape != (Q,) or skip.dtype.kind not in "iu":
                 raise ValueError(f"skip must be {Q} integers (a gallery row, or -1), got shape {skip.shape} of {skip.dtype}")
-        dev = self.device
+        if Q == 0:
+            return 0, None, None
+        if self.device.type != "cuda":
+            raise _lib.FacenetHipError(f"{runs} on the GPU; facenet_amd has no CPU fallback")
+        skip_dev = None if skip is None else torch.from_numpy(skip.astype(np.int32)).to(self.device)
+        return Q, _as_table(queries, self.device), skip_dev
+
+    def _workspace(self, sizer, what, *args):
+        """The int64 workspace tensor of the size that sizer(*args, &bytes), a fn_*_workspace entry, reports (at least 8 bytes)."""
+        nbytes = ctypes.c_longlong(0)
+        _lib.check(sizer(*args, ctypes.byref(nbytes)), what)
+        return torch.empty(max(1, (nbytes.value + 7) // 8), dtype=torch.int64, device=self.device)
+
+    def _search(self, queries, k, skip, slab_rows, atol):
+        """-> device (dist [Q, k], rows [Q, k]) after every check of `search`."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        Q, q, skip_dev = self._queries(queries, skip, "Gallery.search runs fn_gallery_search")
+        dev, G = self.device, self.nrof_images
         dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
         rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
         if Q == 0:
             return dist, rows
-        if dev.type != "cuda":
-            raise _lib.FacenetHipError("Gallery.search runs fn_gallery_search on the GPU; facenet_amd has no CPU fallback")
         lib = _lib.load()
-        q = _as_table(queries, dev)
-        skip_dev = None if skip is None else torch.from_numpy(skip.astype(np.int32)).to(dev)
-        import ctypes
-        nbytes = ctypes.c_longlong(0)
-        _lib.check(lib.fn_gallery_search_workspace(Q, G, k, int(slab_rows), ctypes.byref(nbytes)), "gallery_search_workspace")
-        ws = torch.empty(max(1, (nbytes.value + 7) // 8), dtype=torch.int64, device=dev)
+        ws = self._workspace(lib.fn_gallery_search_workspace, "gallery_search_workspace", Q, G, k, int(slab_rows))
         rng = None if atol is None else torch.zeros(2, dtype=torch.int32, device=dev)
         _lib.check(lib.fn_gallery_search(_ptr(q), Q, _ptr(self.embeddings), G, self.length, k, self.metric, _ptr(skip_dev), None, int(slab_rows),
                                          _ptr(ws), _ptr(dist), _ptr(rows), None, _ptr(rng), _stream(dev)),
                    "gallery_search")
-        if rng is None:
-            return dist, rows
-        lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())       # waits for the search
-        lim = 1 + atol
-        if lo < -lim or hi > lim:       # statistics.py:40-42
-            raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+        if rng is not None:
+            check_unit_range(rng, atol)         # waits for the search
         return dist, rows
 
     def search(self, queries, k=1, skip=None, slab_rows=0, atol=1.e-5):
@@ -311,40 +318,21 @@ class Gallery:
         eps = np.float32(eps)
         if np.isnan(eps):
             raise ValueError("eps must be a number, got NaN")
-        shape = tuple(queries.shape) if hasattr(queries, "shape") else np.shape(queries)
-        if len(shape) != 2:
-            raise ValueError(f"queries must be a 2-D [Q, E] array, got shape {shape}")
-        if shape[1] != self.length:
-            raise ValueError(f"embedding lengths differ: queries {shape[1]}, gallery {self.length}")
         if max_edges is not None and max_edges < 0:
             raise ValueError(f"max_edges must not be negative, got {max_edges}")
-        Q, G = shape[0], self.nrof_images
-        if skip is not None:
-            skip = np.asarray(skip.cpu() if torch.is_tensor(skip) else skip)
-            if skip.shape != (Q,) or skip.dtype.kind not in "iu":
-                raise ValueError(f"skip must be {Q} integers (a gallery row, or -1), got shape {skip.shape} of {skip.dtype}")
-        dev = self.device
+        Q, q, skip_dev = self._queries(queries, skip, "Gallery.within runs fn_radius_count")
+        dev, G = self.device, self.nrof_images
         offsets = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
         if Q == 0:
             return offsets, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
-        if dev.type != "cuda":
-            raise _lib.FacenetHipError("Gallery.within runs fn_radius_count on the GPU; facenet_amd has no CPU fallback")
         lib = _lib.load()
-        q = _as_table(queries, dev)
-        skip_dev = None if skip is None else torch.from_numpy(skip.astype(np.int32)).to(dev)
-        import ctypes
-        nbytes = ctypes.c_longlong(0)
-        _lib.check(lib.fn_radius_workspace(Q, G, int(slab_rows), ctypes.byref(nbytes)), "radius_workspace")
-        ws = torch.empty(max(2, (nbytes.value + 7) // 8), dtype=torch.int64, device=dev)
+        ws = self._workspace(lib.fn_radius_workspace, "radius_workspace", Q, G, int(slab_rows))
         rng = torch.zeros(2, dtype=torch.int32, device=dev)
         common = (_ptr(q), Q, _ptr(self.embeddings), G, self.length, self.metric, float(eps), _ptr(skip_dev), int(slab_rows), _ptr(ws))
         _lib.check(lib.fn_radius_count(*common, _ptr(offsets), _ptr(rng), _stream(dev)), "radius_count")
         nnz = int(offsets[Q].item())                                # waits for the count
         if atol is not None:
-            lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
-            lim = 1 + atol
-            if lo < -lim or hi > lim:       # statistics.py:40-42
-                raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+            check_unit_range(rng, atol)
         check_edges(nnz, max_edges)
         rows = torch.empty(nnz, dtype=torch.int32, device=dev)
         dist = torch.empty(nnz, dtype=torch.float32, device=dev)

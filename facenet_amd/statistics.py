@@ -15,6 +15,15 @@ def _decode_ord(i: int) -> float:
     return float(np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0])
 
 
+def check_unit_range(rng_words, atol):
+    """The two `range` words of a kernel (a device tensor; reading them waits for the kernel) -> the reference's ValueError when
+    some dot product left +-(1 + atol) (statistics.py:40-42).  A kernel that evaluated no pair leaves words that decode to
+    lo = +3.4e38 > hi = -3.4e38, which neither comparison takes for a violation: the empty case needs no rule of its own."""
+    lo, hi = (_decode_ord(v) for v in rng_words.cpu().tolist())
+    if lo < -(1 + atol) or hi > 1 + atol:
+        raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+
+
 def pairwise_similarities(xa, xb=None, metric: int = 0, atol: float = 1.e-5, device: str = "cuda"):
     """xa [n,E], xb [m,E] unit-norm rows -> 2(1 - xa.xb^T) (metric 0) or arccos (metric 1); with ``xb=None`` the strict
     upper triangle of xa against itself, flattened row-major (np.triu_indices order)."""
@@ -37,10 +46,7 @@ def pairwise_similarities(xa, xb=None, metric: int = 0, atol: float = 1.e-5, dev
             return sims.cpu().numpy()
     else:
         sims = out
-    lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
-    lim = 1 + atol
-    if lo < -lim or hi > lim:   # statistics.py:40-42 (the kernel reports min/max over the full matrix)
-        raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+    check_unit_range(rng, atol)         # the kernel reports min/max over the full matrix
     return sims.cpu().numpy()
 
 
@@ -154,9 +160,7 @@ class ConfidenceMatrix:
         _lib.check(lib.fn_confidence_counts(_ptr(calculator.emb), _ptr(calculator._cls), calculator.nrof_classes, E, _ptr(t_dev), thr.size,
                                             calculator.metric, _ptr(out), _ptr(rng), st), "confidence_counts")
         self.counts = out.cpu().numpy().reshape(4, thr.size)
-        lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
-        if hi >= lo and (lo < -(1 + atol) or hi > 1 + atol):   # some pair was evaluated and left [-1, 1]: statistics.py:40-42
-            raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+        check_unit_range(rng, atol)
 
     @classmethod
     def from_counts(cls, counts, threshold):
@@ -323,9 +327,7 @@ def confidence_counts_folds(calculator: SimilarityCalculator, fold_sorted, train
                                               calculator.nrof_classes, E, F, _ptr(t_dev), thr.size, calculator.metric, _ptr(out), _ptr(rng), st),
                "confidence_counts_folds")
     counts = out.cpu().numpy().reshape(F, 4, thr.size)
-    lo, hi = (_decode_ord(v) for v in rng.cpu().tolist())
-    if hi >= lo and (lo < -(1 + atol) or hi > 1 + atol):        # statistics.py:40-42
-        raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+    check_unit_range(rng, atol)
     return counts
 
 

@@ -276,6 +276,27 @@ def test_agrees_with_the_validation_kernel(metric):
     assert 2 * round(tp) == got["nnz"]
 
 
+@pytest.mark.parametrize("metric", [0, 1])
+@pytest.mark.parametrize("Q", [16, 17])
+def test_search_and_radius_report_the_same_distance_bits(Q, metric):
+    """Gallery.search(k = G) against Gallery.within(eps = inf) over the same rows: every query's row -> distance map is the same
+    bit for bit.  For metric 1 the search takes the arccos of a scalar fmaf chain, the radius fill that of the MFMA accumulator.
+    Q = 16 is the search's split path, Q = 17 its four-wave path with a second, nearly empty 16-row query tile; E = 36 is one
+    full 32-chunk and a 4-wide remainder."""
+    from facenet_amd.recognize import Gallery
+    G, E = 64, 36
+    x = np.random.default_rng(20 + Q).standard_normal((G, E))
+    x = (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)          # normalised in fp64, then cast
+    gal = Gallery(x, metric=metric, device=DEV)
+    dist, rows = gal.search(x[:Q], k=G)
+    offsets, cols, d = gal.within(x[:Q], np.inf)
+    assert offsets.tolist() == [G * i for i in range(Q + 1)] and (np.sort(rows, axis=1) == np.arange(G)).all()
+    for i in range(Q):
+        from_search = dict(zip(rows[i].tolist(), dist[i].view(np.uint32).tolist()))
+        from_radius = dict(zip(cols[G * i:G * (i + 1)].tolist(), d[G * i:G * (i + 1)].view(np.uint32).tolist()))
+        assert from_search == from_radius, (i, metric)
+
+
 def test_radius_argument_rules():
     lib = _lib.load()
     nbytes = C.c_longlong()
