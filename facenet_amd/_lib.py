@@ -145,6 +145,9 @@ _SIGNATURES = {
     "fn_dbscan_rounds": [_i, _p, _p, _p, _p, _p, _i, _p],
     "fn_dbscan_finish": [_i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p],
     "fn_softmax_xent_fwd_bwd": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _f, _i, _p],
+    "fn_margin_weight_rnorm": [_p, _i, _i, _f, _p, _p],
+    "fn_margin_softmax_fwd_bwd": [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _f, _f, _f, _f, _i, _p],
+    "fn_margin_wgrad_fix": [_p, _p, _p, _p, _i, _i, _p],
     "fn_center_loss_fwd_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p],
     "fn_center_update": [_p, _i, _i, _i, _p, _i, C.c_double, _p],
     "fn_f2f_row_norms": [_p, _i, _i, _p, _p],

@@ -68,10 +68,13 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
                         nrof_classes=nrof_classes, device=device, seed=cfg.seed)
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     # loss.center_* / prelogits_norm_* (train_softmax.yaml:73-78): center loss and prelogits-norm loss on the embedding;
-    # train.moving_average_decay (:28): the moving average of the weights
+    # train.moving_average_decay (:28): the moving average of the weights; loss.margin_*: the large-margin cosine softmax head
     trainer = Trainer(net, batch=local_batch, loss="softmax", lr=scheduler(0), world_size=world_size, process_group=process_group,
                       moving_average_decay=moving_average_decay(cfg), optimizer=optimizer,
-                      **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p")})
+                      **{k: _loss_key(cfg, k) for k in ("center_factor", "center_alfa", "prelogits_norm_factor", "prelogits_norm_p",
+                                                       "margin_scale", "margin_arc", "margin_cos")})
+    if rank == 0 and trainer.margin:                             # once; a plain softmax run logs exactly what it always did
+        log(f"margin softmax: scale {trainer.margin_scale:g}  arc {trainer.margin_arc:g}  cos {trainer.margin_cos:g}")
     if rank == 0 and optimizer != "ADAM":                        # once; an Adam run logs exactly what it always did
         log(f"optimizer: {optimizer}")
     if validation is not None and validation.model is None:      # ValidateCallback(model=network, ...) of :85-88

@@ -78,7 +78,9 @@ DEFAULTS = {   # apps/configs/config.yaml:4-15 and train_softmax.yaml:37-47 (the
               "learning_rate": {"value": None, "schedule": [[100, 0.05], [200, 0.005], [300, 0.0005]]},
               "optimizer": "ADAM"},         # train_softmax.yaml:25-26
     # apps/configs/train_softmax.yaml:73-78 (prelogits_hist_max only fed a TensorBoard histogram: not read)
-    "loss": {"alpha": 0.2, "center_factor": 0.0, "center_alfa": 0.95, "prelogits_norm_factor": 0.0, "prelogits_norm_p": 1.0},
+    # margin_scale / margin_arc / margin_cos: the large-margin cosine softmax head; 0: the plain softmax
+    "loss": {"alpha": 0.2, "center_factor": 0.0, "center_alfa": 0.95, "prelogits_norm_factor": 0.0, "prelogits_norm_p": 1.0,
+             "margin_scale": 0.0, "margin_arc": 0.0, "margin_cos": 0.0},
     # apps/configs/train_softmax.yaml:94-117: validation inside training.  The reference names a directory
     # of its author's machine as dataset.path; here null means no validation.  averaged: validate the moving average of the weights
     "validate": {"every_n_epochs": 10, "averaged": False,

@@ -7,6 +7,7 @@
 //  * softmax cross-entropy = SparseCategoricalCrossentropy(from_logits=True), apps/train_softmax.py:91.
 //  * center loss + its center update = facenet/facenet.py:204-217 (center_loss); prelogits norm = the
 //    loss.prelogits_norm_* keys of apps/configs/train_softmax.yaml:73-78 (formula: DESIGN.md section 11).
+//  * large-margin cosine softmax (NormFace / CosFace / ArcFace) on the normalised embedding and class rows: DESIGN.md section 21.
 #include "pair_tiles.h"      // ord_f32, DotRange, pair_distance: shared with the validation, identification and clustering kernels
 #include "../../include/facenet_hip.h"
 
@@ -428,6 +429,135 @@ __global__ __launch_bounds__(256) void center_update_kernel(const float* __restr
         cr[e] = c;
     }
 }
+// ---- large-margin cosine softmax: NormFace / CosFace / ArcFace ----------------------------------------
+// r[j] = 1 / sqrt(max(sum_e w[j][e]^2, eps)): one wave per class row (4 rows per workgroup), 16-byte loads, per-lane chain in
+// ascending e, then the butterfly.  sqrtf and the division are correctly rounded, so a one-hot row gives exactly 1.
+__global__ __launch_bounds__(256) void margin_rnorm_kernel(const float* __restrict__ w, int C, int E, float eps, float* __restrict__ rnorm) {
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= C) return;
+    const float* wr = w + (long)j * E;
+    float s = 0.f;
+    for (int e = 4 * lane; e < E; e += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(wr + e);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s += v[t] * v[t];
+    }
+    s = wave_sum(s);
+    if (lane == 0) rnorm[j] = 1.f / sqrtf(fmaxf(s, eps));
+}
+
+// cos m2, sin m2, th = cos(pi - m2), mm = sin(pi - m2) m2: computed once on the host in double from the fp32 m2, rounded to fp32
+struct MarginConsts {
+    float scale, cos_m, sin_m, th, mm, m_cos;
+};
+#define FN_MARGIN_T 0.99999904632568359375f      // 1 - 2^-20: keeps (1 - ct)(1 + ct) >= 2^-20, so dphi/dc < cos m2 + 725 sin m2
+
+// c = clamp(z r, -1, 1); the target column's phi and D = dphi/dc at ct = clamp(c, -T, T).  Every rounding is spelled out.
+__device__ __forceinline__ float margin_cosine(float z, float r) {
+#pragma clang fp contract(off)
+    return fminf(fmaxf(z * r, -1.f), 1.f);
+}
+__device__ __forceinline__ float margin_phi(float c, const MarginConsts& k, float& D) {
+#pragma clang fp contract(off)
+    const float ct = fminf(fmaxf(c, -FN_MARGIN_T), FN_MARGIN_T);
+    if (ct > k.th) {
+        const float a = 1.f - ct, b = 1.f + ct;
+        const float q = a * b;                  // a product, not 1 - ct^2: 1 - ct is exact near 1
+        const float sq = sqrtf(q);
+        const float u = ct * k.cos_m, v = sq * k.sin_m;
+        const float n = ct * k.sin_m;
+        D = k.cos_m + n / sq;
+        return (u - v) - k.m_cos;
+    }
+    D = 1.f;                                    // theta + m2 > pi: the linear continuation
+    return (ct - k.mm) - k.m_cos;
+}
+__device__ __forceinline__ float margin_logit(float z, float r, bool target, const MarginConsts& k) {
+#pragma clang fp contract(off)
+    const float c = margin_cosine(z, r);
+    float D;
+    return k.scale * (target ? margin_phi(c, k, D) : c);
+}
+
+// one workgroup per row, shaped like softmax_xent_kernel: l = s c (s phi in the label's column); loss += (lse - l[label]) / N;
+// g = (softmax - onehot) grad_scale s D; dz = g r (low precision, padded columns = 0); t[c] += g c (fixed point)
+template <typename T>
+__global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __restrict__ z, int ld, const float* __restrict__ rnorm,
+                                                             const int* __restrict__ labels, acc_t* __restrict__ loss,
+                                                             unsigned short* __restrict__ dz, int ld_d, acc_t* __restrict__ tacc, int N, int C,
+                                                             MarginConsts k, float grad_scale) {
+#pragma clang fp contract(off)
+    __shared__ float red[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* x = z + (long)row * ld;
+    const int lab = labels[row];
+    const bool lab_ok = lab >= 0 && lab < C;
+    float mx = -3e38f;
+    for (int c = tid; c < C; c += 256) mx = fmaxf(mx, margin_logit(x[c], rnorm[c], c == lab, k));
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float s = 0.f;
+    for (int c = tid; c < C; c += 256) s += __expf(margin_logit(x[c], rnorm[c], c == lab, k) - mx);
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    s = red[0] + red[1] + red[2] + red[3];
+    // an out-of-range class index never indexes the logits: the flag word makes the loss NaN, the row has no one-hot term
+    if (tid == 0) {
+        if (lab_ok) acc_add<ACC_GRAD>(loss, (logf(s) + mx - margin_logit(x[lab], rnorm[lab], true, k)) / (float)N);
+        else reinterpret_cast<volatile unsigned*>(loss)[-1] = 1u;
+    }
+    if (!dz && !tacc) return;
+    const float inv = 1.f / s;
+    unsigned short* d = dz ? dz + (long)row * ld_d : nullptr;
+    const int cols = dz ? ld_d : C;
+    for (int c = tid; c < cols; c += 256) {
+        float gz = 0.f;
+        if (c < C) {
+            const float r = rnorm[c], cv = margin_cosine(x[c], r);
+            float D = 1.f, l = cv;
+            if (c == lab) l = margin_phi(cv, k, D);
+            l = k.scale * l;
+            float g = (__expf(l - mx) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+            g = g * k.scale;
+            g = g * D;
+            if (tacc) acc_add<ACC_GRAD>(&tacc[c], g * cv);
+            gz = g * r;
+        }
+        if (d) d[c] = LP<T>::from_f32(gz);
+    }
+}
+
+// dw[j][e] -= (r_j^2 t_j) w[j][e] for j < C: one wave per class row, 16-byte accesses; lane 0 reads t[j] and leaves it zeroed
+__global__ __launch_bounds__(256) void margin_wgrad_fix_kernel(float* __restrict__ dw, const float* __restrict__ w, const float* __restrict__ rnorm,
+                                                               acc_t* __restrict__ tacc, int C, int E) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= C) return;
+    float tf = 0.f;
+    if (lane == 0) {
+        tf = acc_get<ACC_GRAD>(tacc[j]);
+        tacc[j] = 0;
+    }
+    tf = __shfl(tf, 0);
+    const float r = rnorm[j];
+    const float kf = (r * r) * tf;
+    const float* wr = w + (long)j * E;
+    float* dr = dw + (long)j * E;
+    for (int e = 4 * lane; e < E; e += 256) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + e);
+        f32x4 dv = *reinterpret_cast<const f32x4*>(dr + e);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float p = kf * wv[t];
+            dv[t] = dv[t] - p;
+        }
+        *reinterpret_cast<f32x4*>(dr + e) = dv;
+    }
+}
 }  // namespace fn
 using namespace fn;
 
@@ -502,4 +632,41 @@ extern "C" int fn_center_update(const float* rows, int ld, int M, int E, float* 
     const float k = (float)(1.0 - alfa);      // (1 - alfa) of facenet.py:213: a Python float, rounded to fp32 once
     hipLaunchKernelGGL(center_update_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, rows, ld, M, E, centers, C, k);
     return check_launch("center_update");
+}
+
+extern "C" int fn_margin_weight_rnorm(const float* w, int C, int E, float eps, float* rnorm, void* stream) {
+    FN_REQUIRE(w && rnorm && C > 0 && E > 0 && E % 4 == 0 && eps > 0.f, "margin_weight_rnorm: bad arguments (E must be a multiple of 4, eps > 0)");
+    FN_REQUIRE(((uintptr_t)w & 15) == 0, "margin_weight_rnorm: w must be 16-byte aligned");
+    hipLaunchKernelGGL(margin_rnorm_kernel, dim3(cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream, w, C, E, eps, rnorm);
+    return check_launch("margin_weight_rnorm");
+}
+
+extern "C" int fn_margin_softmax_fwd_bwd(const float* z, int ld, const float* rnorm, const int32_t* labels, float* loss, void* dz_lp, int ld_d,
+                                         fn_acc_t* t, int N, int C, float scale, float m_arc, float m_cos, float grad_scale, int dtype,
+                                         void* stream) {
+    FN_REQUIRE(((uintptr_t)loss & 7) == 0, "margin_softmax: loss must be an 8-byte aligned fp32[4]");
+    FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
+    FN_REQUIRE(z && rnorm && labels && loss && N > 0 && C > 0 && ld >= C && (!dz_lp || ld_d >= C), "margin_softmax: bad arguments");
+    const double pi = 3.14159265358979323846, m = (double)m_arc;
+    // (written so that a NaN setting is refused too)
+    FN_REQUIRE(scale > 0.f && m_arc >= 0.f && m < 0.5 * pi && m_cos >= 0.f,
+               "margin_softmax: need scale > 0, 0 <= m_arc < pi/2, m_cos >= 0 (got %g, %g, %g)", (double)scale, m, (double)m_cos);
+    const MarginConsts k = {scale, (float)cos(m), (float)sin(m), (float)cos(pi - m), (float)(sin(pi - m) * m), m_cos};
+    hipStream_t st = (hipStream_t)stream;
+    fill_words(loss, 0u, 0u, 4, st);
+    acc_t* lacc = reinterpret_cast<acc_t*>(loss + 2);
+    acc_t* tacc = reinterpret_cast<acc_t*>(t);
+    if (dtype == FN_BF16)
+        hipLaunchKernelGGL(margin_softmax_kernel<__bf16>, dim3(N), dim3(256), 0, st, z, ld, rnorm, labels, lacc, (unsigned short*)dz_lp, ld_d, tacc, N, C, k, grad_scale);
+    else
+        hipLaunchKernelGGL(margin_softmax_kernel<_Float16>, dim3(N), dim3(256), 0, st, z, ld, rnorm, labels, lacc, (unsigned short*)dz_lp, ld_d, tacc, N, C, k, grad_scale);
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(1), 0, st, loss);
+    return check_launch("margin_softmax");
+}
+
+extern "C" int fn_margin_wgrad_fix(float* dw, const float* w, const float* rnorm, fn_acc_t* t, int C, int E, void* stream) {
+    FN_REQUIRE(dw && w && rnorm && t && C > 0 && E > 0 && E % 4 == 0, "margin_wgrad_fix: bad arguments (E must be a multiple of 4)");
+    FN_REQUIRE(((uintptr_t)dw & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)t & 7) == 0, "margin_wgrad_fix: dw and w must be 16-byte aligned, t 8-byte");
+    hipLaunchKernelGGL(margin_wgrad_fix_kernel, dim3(cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream, dw, w, rnorm, reinterpret_cast<acc_t*>(t), C, E);
+    return check_launch("margin_wgrad_fix");
 }

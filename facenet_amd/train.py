@@ -8,6 +8,8 @@
   (a0,p0,n0,a1,...).  ``TripletMiner`` does the online selection in a PxK pool on device.
 * ``Trainer(loss='softmax', center_factor=..., prelogits_norm_factor=...)`` adds the reference's embedding regularisers
   (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
+* ``Trainer(loss='softmax', margin_scale=64, margin_arc=0.5)`` replaces the plain softmax head by the large-margin cosine softmax
+  (NormFace / CosFace / ArcFace) on the L2-normalised embedding and class rows.
 * ``Trainer(..., moving_average_decay=0.9999)`` keeps TF1's ``ExponentialMovingAverage(decay, global_step)`` of the trainable
   variables (train.moving_average_decay, apps/configs/train_softmax.yaml:28), fused into the optimiser pass.
 * ``Trainer(..., optimizer='RMSPROP')`` picks the update rule by the names of train.optimizer (apps/configs/train_softmax.yaml:25-26):
@@ -22,6 +24,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import json
+import math
 import os
 import warnings
 from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -297,9 +300,10 @@ def optimizer_name(cfg) -> str:
 
 
 def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: float, center_alfa: float, prelogits_norm_factor: float,
-                         prelogits_norm_p: float):
+                         prelogits_norm_p: float, margin_scale: float = 0.0, margin_arc: float = 0.0, margin_cos: float = 0.0):
     """What the Trainer refuses: an unknown loss, a batch or network that does not fit it, regulariser settings out of range
-    (loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p, train_softmax.yaml:73-78)."""
+    (loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p, train_softmax.yaml:73-78), margin settings out of
+    range or without a scale (loss.margin_scale / margin_arc / margin_cos)."""
     if loss not in ("triplet", "softmax"):
         raise ValueError(f"unknown loss {loss!r}")
     if loss == "triplet" and batch % 3:
@@ -314,6 +318,14 @@ def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: flo
         raise ValueError(f"prelogits_norm_p must be > 0, got {prelogits_norm_p}")
     if loss == "triplet" and (center_factor > 0 or prelogits_norm_factor > 0):
         raise ValueError("center loss and prelogits-norm loss need class labels: they belong to softmax training")
+    if not (margin_scale >= 0 and margin_arc >= 0 and margin_cos >= 0):
+        raise ValueError(f"margin_scale, margin_arc and margin_cos must be >= 0, got {margin_scale}, {margin_arc}, {margin_cos}")
+    if not float(np.float32(margin_arc)) < math.pi / 2:      # the kernel takes the fp32 value
+        raise ValueError(f"margin_arc must be < pi/2, got {margin_arc}")
+    if margin_scale == 0 and (margin_arc > 0 or margin_cos > 0):
+        raise ValueError("margin_arc and margin_cos need margin_scale > 0")
+    if loss == "triplet" and margin_scale > 0:
+        raise ValueError("the margin softmax needs class labels: it belongs to softmax training")
 
 
 def _streams_for(net: Network, n_streams: int) -> StreamSet:
@@ -329,7 +341,8 @@ class Trainer:
                  beta2: float = 0.999, epsilon: float = 0.1, l2: Optional[float] = None, world_size: int = 1, process_group=None,
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
                  center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0,
-                 moving_average_decay: Optional[float] = None, optimizer: str = "ADAM"):
+                 moving_average_decay: Optional[float] = None, optimizer: str = "ADAM", margin_scale: float = 0.0,
+                 margin_arc: float = 0.0, margin_cos: float = 0.0):
         self.group_wgrad = group_wgrad
         self.optimizer = check_optimizer(optimizer)        # beta1, beta2 and epsilon are Adam's; the other rules' constants: OPTIMIZERS
         self.rule = OPTIMIZERS[self.optimizer]
@@ -341,7 +354,11 @@ class Trainer:
         # the RCCL path is exercised on a one-GPU box (bench.py --exchange-self, tests/test_gpu_dp.py).
         self.exchange = world_size > 1 or process_group is not None
         self.segmented = self.exchange or force_segments
-        check_loss_arguments(net, batch, loss, center_factor, center_alfa, prelogits_norm_factor, prelogits_norm_p)
+        check_loss_arguments(net, batch, loss, center_factor, center_alfa, prelogits_norm_factor, prelogits_norm_p, margin_scale,
+                             margin_arc, margin_cos)
+        # NormFace / CosFace / ArcFace: settings, not state; margin_scale == 0 is the plain softmax head
+        self.margin_scale, self.margin_arc, self.margin_cos = float(margin_scale), float(margin_arc), float(margin_cos)
+        self.margin = margin_scale > 0
         self.center_factor, self.center_alfa = float(center_factor), float(center_alfa)
         self.prelogits_norm_factor, self.prelogits_norm_p = float(prelogits_norm_factor), float(prelogits_norm_p)
         self.regularized = center_factor > 0 or prelogits_norm_factor > 0
@@ -392,7 +409,10 @@ class Trainer:
         if loss == "triplet":
             self._build_triplet_loss(emb)
         else:
-            self._build_softmax_loss(emb)
+            if self.margin:
+                self._build_margin_loss(emb)
+            else:
+                self._build_softmax_loss(emb)
             if self.regularized:
                 self._build_regularizers()
         self.plan.build_backward(self.demb)
@@ -448,6 +468,56 @@ class Trainer:
         g.y, g.w, g.dx, g.out_f32 = _ptr(self.dlogits), _ptr(net.Wt_train, L.w_off), _ptr(self.demb), 1
         emit(self.loss_ops, "conv_dgrad:classifier", lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
              r=[region(self.dlogits), weight_region(net.Wt_train, L)], w=[region(self.demb)])
+
+    def _build_margin_loss(self, emb: torch.Tensor):
+        """The large-margin cosine softmax head: the classifier without bias on the L2-normalised embedding,
+        cosines through the class rows' reciprocal norms, the margin in the label's column; the weight gradient gets the term of
+        the row normalisation, the data gradient goes back through the embedding's normalisation.  The bias stays in P, is not
+        read and keeps a zero gradient."""
+        net, lib, batch, E, dev = self.net, self.lib, self.N, self.net.E, self.net.device
+        L = net.layers["classifier/logits"]
+        Cp, Cr = L.cout, L.cout_real
+        assert L.w_off % 4 == 0 and E % 4 == 0, "the class rows are read with 16-byte loads"
+        self.labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.embn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
+        self.dembn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
+        self.emb_lp = torch.zeros(batch, E, dtype=net.train_dtype, device=dev)
+        self.logits = torch.zeros(batch, Cp, dtype=torch.float32, device=dev)
+        self.dlogits = torch.zeros(batch, Cp, dtype=net.train_dtype, device=dev)
+        self.rnorm = torch.zeros(Cp, dtype=torch.float32, device=dev)
+        self.margin_t = torch.zeros(Cp, dtype=torch.int64, device=dev)       # zeroed once: margin_wgrad_fix leaves it zeroed
+        ops = self.loss_ops
+        emit(ops, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(emb), _ptr(self.embn), batch, E, 1e-10, r=[region(emb)], w=[region(self.embn)])
+        emit(ops, "cast_emb", lib.fn_cast_f32_to_lp, _ptr(self.embn), _ptr(self.emb_lp), batch * E, self.dt,
+             r=[region(self.embn)], w=[region(self.emb_lp)])
+        emit(ops, "margin_rnorm", lib.fn_margin_weight_rnorm, _ptr(net.P, L.w_off), Cr, E, 1e-10, _ptr(self.rnorm),
+             r=[weight_region(net.P, L)], w=[region(self.rnorm)])
+        d = self._cls_desc(L)
+        d.x, d.w, d.y, d.bias, d.out_f32 = _ptr(self.emb_lp), _ptr(net.W_train, L.w_off), _ptr(self.logits), None, 1
+        emit(ops, "conv_fwd:classifier", lib.fn_conv2d_fwd, C.byref(d), keep=(d,),
+             r=[region(self.emb_lp), weight_region(net.W_train, L)], w=[region(self.logits)])
+        emit(ops, "margin_softmax", lib.fn_margin_softmax_fwd_bwd, _ptr(self.logits), Cp, _ptr(self.rnorm), _ptr(self.labels),
+             _ptr(self.loss), _ptr(self.dlogits), Cp, _ptr(self.margin_t), batch, Cr, self.margin_scale, self.margin_arc,
+             self.margin_cos, 1.0 / batch, self.dt,
+             r=[region(self.logits), region(self.rnorm), region(self.labels), region(self.margin_t)],
+             w=[region(self.loss), region(self.dlogits), region(self.margin_t)])
+        # This weight gradient has a consumer inside the step, so it stays where it is: group_wgrads moves the launches that carry
+        # their descriptor in `keep` to the end of the segment, this one keeps its descriptor on the trainer.  One split (the
+        # reduction runs over the batch only): a single ordered sum, no float atomics between workgroups.
+        w = self._margin_wgrad_desc = self._cls_desc(L)
+        w.x, w.y, w.dw, w.splits = _ptr(self.emb_lp), _ptr(self.dlogits), _ptr(self.G, L.w_off), 1
+        emit(ops, "conv_wgrad:classifier", lib.fn_conv2d_wgrad, C.byref(w),
+             r=[region(self.emb_lp), region(self.dlogits)], w=[weight_region(self.G, L)])
+        emit(ops, "margin_wgrad_fix", lib.fn_margin_wgrad_fix, _ptr(self.G, L.w_off), _ptr(net.P, L.w_off), _ptr(self.rnorm),
+             _ptr(self.margin_t), Cr, E,
+             r=[weight_region(self.G, L), weight_region(net.P, L), region(self.rnorm), region(self.margin_t)],
+             w=[weight_region(self.G, L), region(self.margin_t)])
+        g = self._cls_desc(L)
+        g.y, g.w, g.dx, g.out_f32 = _ptr(self.dlogits), _ptr(net.Wt_train, L.w_off), _ptr(self.dembn), 1
+        emit(ops, "conv_dgrad:classifier", lib.fn_conv2d_dgrad, C.byref(g), keep=(g,),
+             r=[region(self.dlogits), weight_region(net.Wt_train, L)], w=[region(self.dembn)])
+        emit(ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(self.dembn), _ptr(self.demb), batch, E, 1e-10,
+             r=[region(emb), region(self.dembn)], w=[region(self.demb)])
 
     def _build_optimizer(self):
         """Step count and beta powers (fn_adam_tick) -> the update rule in one pass over P, with the moving average fused in when

@@ -408,6 +408,24 @@ int fn_dbscan_finish(int N, const int64_t* offsets, const int32_t* cols, const f
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
                             int C, float grad_scale, int dtype, void* stream);
 
+/* ---- large-margin cosine softmax: NormFace / CosFace / ArcFace ------------------------------------------
+ * The classifier runs on the L2-normalised embedding; z = xhat . w_j comes from fn_conv2d_fwd without bias.
+ * fn_margin_weight_rnorm: rnorm[j] = 1 / sqrt(max(sum_e w[j][e]^2, eps)) for the C rows of fp32 w [C][E] (E % 4 == 0, w 16-byte
+ *   aligned); a one-hot row gives exactly 1.
+ * fn_margin_softmax_fwd_bwd: c = clamp(z rnorm, -1, 1); in the label's column ct = clamp(c, -T, T), T = 1 - 2^-20, and
+ *   phi = ct cos m_arc - sqrt((1 - ct)(1 + ct)) sin m_arc - m_cos if ct > cos(pi - m_arc), else ct - sin(pi - m_arc) m_arc - m_cos;
+ *   logits l = scale c (scale phi in the label's column); loss (fp32[4] as above) = mean_i (logsumexp l_i - l_i[label]);
+ *   g = scale (softmax(l) - onehot) grad_scale D with D = dphi/dc at ct in the label's column (1 on the linear branch) and 1
+ *   elsewhere: both clamps are straight-through.  dz_lp (optional) [N][ld_d] = g rnorm in low precision, columns C..ld_d zero;
+ *   t (optional, fixed point, FN_ACC_GRAD_BITS) t[c] += sum_i g c.  Columns >= C of z and rnorm are never read.  A label outside
+ *   [0, C) gives a NaN loss and no one-hot term.  scale > 0, 0 <= m_arc < pi/2, m_cos >= 0, else FN_EINVAL.
+ * fn_margin_wgrad_fix: the gradient through the row normalisation, dw[j][e] -= rnorm[j]^2 t[j] w[j][e] for j < C (dw, w fp32
+ *   [.][E], 16-byte aligned, E % 4 == 0); t[0..C) is read and left zeroed for the next step. */
+int fn_margin_weight_rnorm(const float* w, int C, int E, float eps, float* rnorm, void* stream);
+int fn_margin_softmax_fwd_bwd(const float* z, int ld, const float* rnorm, const int32_t* labels, float* loss, void* dz_lp, int ld_d,
+                              fn_acc_t* t, int N, int C, float scale, float m_arc, float m_cos, float grad_scale, int dtype, void* stream);
+int fn_margin_wgrad_fix(float* dw, const float* w, const float* rnorm, fn_acc_t* t, int C, int E, void* stream);
+
 /* ---- embedding regularisers of softmax training ------------------------------------------------------
  * fn_center_loss_fwd_bwd: center loss of facenet/facenet.py:204-217 (center_loss) and the prelogits-norm loss named by
  * loss.prelogits_norm_factor / prelogits_norm_p of apps/configs/train_softmax.yaml:73-78, one launch (+ a one-thread finish).
