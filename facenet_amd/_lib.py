@@ -108,6 +108,8 @@ _SIGNATURES = {
     "fn_gather_images": [_p, _p, _p, _i, _i, _p],
     "fn_face_crop_workspace": [_p, _i, _i, C.POINTER(C.c_longlong)],
     "fn_face_crop_resize_u8": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, C.c_longlong, _p],
+    "fn_face_align_workspace": [_i, C.POINTER(C.c_longlong)],
+    "fn_face_align_u8": [_p, _i, _i, _p, _p, _i, _i, _p, _p, C.c_longlong, _p],
     "fn_bn_relu_train_fwd": [_p, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _i, _i, _p],
     "fn_bn_relu_train_bwd": [_p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "fn_maxpool3x3s2_fwd": [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p],

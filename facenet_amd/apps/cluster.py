@@ -3,7 +3,7 @@
 ``python -m facenet_amd.apps.cluster --config x.yaml``.
 
 Input, exactly one of: embeddings.path (the .npz of apps/embeddings.py: ``embeddings``, optionally ``labels`` / ``files``) or
-dataset.path (photographs; with the keys of apps/photo_embeddings.py: model.*, image.size, image.margin, detector,
+dataset.path (photographs; with the keys of apps/photo_embeddings.py: model.*, image.size, image.margin, image.align, detector,
 mtcnn.weights_file, every face goes detector -> crop -> network -> clustering on the device).  cluster.metric (0 or 1), exactly
 one of cluster.threshold (a number) and cluster.classifier (an .npz written by a FaceToFaceNormalizedEmbeddingsClassifier's
 ``save``), cluster.min_samples (>= 1; 1 is single linkage at the threshold).  ``file`` receives one .npz with a row per face:

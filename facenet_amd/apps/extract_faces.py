@@ -4,9 +4,11 @@ MI355X: every image of every class directory -> detector -> (optionally only sin
 antialiased resize -> ``<outdir>/<class>/<stem>.png`` (further faces of one image: ``<stem>_<n>.png``).  The reference stores
 the box sizes in an h5 file (h5py is not installed here): they go to ``sizes.json`` next to the thumbnails instead.
 ``python -m facenet_amd.apps.extract_faces --config x.yaml`` (keys: dataset.path, outdir, image.size, image.margin,
-detect_multiple_faces, detector, mtcnn.weights_file, image.device_resize).  With ``image.device_resize`` the thumbnails are cropped
-and resized on the device (`image_processing_batch`): the same pixels, and the frame is uploaded once for
-the detector and the resize."""
+detect_multiple_faces, detector, mtcnn.weights_file, image.device_resize, image.align).  With ``image.device_resize`` the thumbnails
+are cropped and resized on the device (`image_processing_batch`): the same pixels, and the frame is uploaded
+once for the detector and the resize.  With ``image.align`` (which implies the device route) every face is warped onto the
+five-point template by its landmarks instead (`image_processing_aligned_batch`) and the thumbnails are
+``image.size`` squares: an aligned training set for the margin-softmax losses."""
 from __future__ import annotations
 
 import json
@@ -18,15 +20,18 @@ from PIL import Image
 
 from facenet_amd import config as config_mod
 from facenet_amd import dataset
-from facenet_amd.detectors.face_detector import FaceDetector, image_processing, image_processing_batch
+from facenet_amd.detectors.face_detector import FaceDetector, image_processing, image_processing_aligned_batch, image_processing_batch
 
 
-def extract_faces(classes, outdir, detector, image_options, detect_multiple_faces: bool = False, log=print, device_resize: bool = False):
+def extract_faces(classes, outdir, detector, image_options, detect_multiple_faces: bool = False, log=print, device_resize: bool = False,
+                  align: bool = False):
     """classes: iterable of objects with .name and .files.  device_resize: crop and resize on the device instead of in PIL (the
-    same pixels).  Returns {'extracted': images that produced thumbnails, 'unread': files PIL could not open,
+    same pixels).  align: landmark-aligned image_options.size thumbnails from the device (implies device_resize).  Returns
+    {'extracted': images that produced thumbnails, 'unread': files PIL could not open,
     'sizes': {relative png path: [box height, box width]}}."""
     outdir = Path(outdir)
     stats = {"extracted": 0, "unread": 0, "sizes": {}}
+    device_resize = device_resize or align
     for cls in classes:
         cls_dir = outdir.joinpath(cls.name)
         cls_dir.mkdir(parents=True, exist_ok=True)
@@ -45,7 +50,10 @@ def extract_faces(classes, outdir, detector, image_options, detect_multiple_face
             if len(boxes) == 0 or (len(boxes) > 1 and not detect_multiple_faces):
                 continue
             stats["extracted"] += 1
-            thumbs = image_processing_batch(pixels, boxes, image_options).cpu().numpy() if device_resize else None
+            if align:
+                thumbs = image_processing_aligned_batch(pixels, boxes, image_options)[0].cpu().numpy()
+            else:
+                thumbs = image_processing_batch(pixels, boxes, image_options).cpu().numpy() if device_resize else None
             for n, box in enumerate(boxes):
                 name = target if n == 0 else target.parent.joinpath('{}_{}{}'.format(target.stem, n, target.suffix))
                 (Image.fromarray(thumbs[n]) if device_resize else image_processing(img, box, image_options)).save(name)
@@ -67,7 +75,7 @@ def main(**options):
     detector = FaceDetector(detector=cfg.detector if cfg.detector else 'pypimtcnn', weights_file=cfg.mtcnn.weights_file)
     print(detector)
     extract_faces(dbase.classes, Path(cfg.outdir).expanduser(), detector, cfg.image, bool(cfg.detect_multiple_faces),
-                  device_resize=bool(cfg.image.device_resize))
+                  device_resize=bool(cfg.image.device_resize), align=bool(cfg.image.align))
 
 
 if __name__ == '__main__':

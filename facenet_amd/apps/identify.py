@@ -2,7 +2,7 @@
 """Who is in every photograph of a data set: detector -> crop -> network -> gallery search on the device (FacePipeline.identify,
 DESIGN.md section 19): ``python -m facenet_amd.apps.identify --config x.yaml``.
 
-Keys: those of apps/photo_embeddings.py (dataset.path, model.*, image.size, image.margin, detector, mtcnn.weights_file, file)
+Keys: those of apps/photo_embeddings.py (dataset.path, model.*, image.size, image.margin, image.align, detector, mtcnn.weights_file, file)
 and gallery.path (required: the .npz of apps/embeddings.py with the known faces), gallery.metric (0 or 1), identify.k (neighbours
 kept per face, 1..64) and at most one of identify.threshold (a number) and identify.classifier (an .npz written by a
 FaceToFaceNormalizedEmbeddingsClassifier's ``save``); with neither every face gets its nearest gallery row's label.  Every image

@@ -2,7 +2,8 @@
 """Embeddings of every face in every photograph of a data set, detector -> crop -> network on the device (FacePipeline,
 DESIGN.md section 17): ``python -m facenet_amd.apps.photo_embeddings --config x.yaml``.
 
-Keys: dataset.path, model.* as in apps/embeddings.py, image.size, image.margin, detector, mtcnn.weights_file, file.  Every image
+Keys: dataset.path, model.* as in apps/embeddings.py, image.size, image.margin, image.align (landmark alignment instead of the box
+crop; off when absent), detector, mtcnn.weights_file, file.  Every image
 of the data set is read, and its faces go to ``file``, one .npz with a row per face: ``files`` (the photograph), ``face`` (the
 index within the photograph), ``boxes`` int64 [N, 4] = left, top, width, height, ``confidence`` float64 [N] and ``embeddings``
 float32 [N, E].  Images without a face, and files that cannot be read, contribute no row."""
@@ -55,7 +56,7 @@ def build_pipeline(options):
     detector = FaceDetector(detector=options.detector if options.detector else "pypimtcnn", weights_file=options.mtcnn.weights_file)
     model_cfg = Config(options.model.as_dict)
     model_cfg.image = Config({"size": options.image.size, "normalization": options.image.normalization or 0})
-    return FacePipeline(detector, FaceNet(model_cfg), options.image)
+    return FacePipeline(detector, FaceNet(model_cfg), options.image, align=bool(options.image.align))
 
 
 def write_photo_embeddings(options, pipeline=None, log=print):

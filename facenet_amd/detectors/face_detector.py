@@ -3,7 +3,11 @@ served by facenet_amd.detectors.mtcnn instead of the PyPI package.  The Faster-R
 (`detectors/frcnnv3`, a frozen TF1 graph whose weights are absent from the reference tree) is out of scope.
 
 `image_processing_batch` is `image_processing` for all boxes of one frame on the device (`fn_face_crop_resize_u8`, DESIGN.md
-section 17): the same pixels, bit for bit, without the frame or the thumbnails visiting the host."""
+section 17): the same pixels, bit for bit, without the frame or the thumbnails visiting the host.
+
+`image_processing_aligned_batch` is the optional landmark alignment: a least-squares similarity from the
+detector's five landmarks onto the ArcFace template (`similarity_from_landmarks`, host arithmetic) and one warp launch for all
+faces of the frame (`align_faces` -> `fn_face_align_u8`); boxes without usable landmarks keep the box path's pixels."""
 from __future__ import annotations
 
 import math
@@ -55,6 +59,17 @@ def check_crop_arguments(windows, side, ox, oy, out_side):
 _workspace = {}     # device -> int32 workspace of the tap tables, grown on demand
 
 
+def _device_frame(frame, what):
+    """uint8 [H, W, 3], an array or a device tensor -> the contiguous device tensor (an array is uploaded)."""
+    import torch
+    if not torch.is_tensor(frame):
+        arr = np.ascontiguousarray(frame)
+        frame = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to("cuda")
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_cuda:
+        raise ValueError(f"{what}: the frame must be uint8 [height, width, 3] (an array or a device tensor)")
+    return frame.contiguous()
+
+
 def crop_resize(frame, windows, side, ox=0, oy=0, out_side=None, stream=None):
     """`Image.fromarray(frame).crop(w).resize((side, side), LANCZOS)` for every window w -> device uint8 [F, S, S, 3]: rows / columns
     [oy, oy + S) x [ox, ox + S) of each result (S = out_side, the whole thumbnail by default).  frame: uint8 [H, W, 3], an array
@@ -67,12 +82,7 @@ def crop_resize(frame, windows, side, ox=0, oy=0, out_side=None, stream=None):
     out_side = side if out_side is None else out_side
     windows = np.ascontiguousarray(windows, dtype=np.int32)
     check_crop_arguments(windows, side, ox, oy, out_side)
-    if not torch.is_tensor(frame):
-        arr = np.ascontiguousarray(frame)
-        frame = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to("cuda")
-    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_cuda:
-        raise ValueError("face crop: the frame must be uint8 [height, width, 3] (an array or a device tensor)")
-    frame = frame.contiguous()
+    frame = _device_frame(frame, "face crop")
     lib = _lib.load()
     words = C.c_longlong(0)
     count = windows.shape[0]
@@ -103,14 +113,157 @@ def image_processing_batch(frame, boxes, options, centre_crop=False, stream=None
     return crop_resize(frame, windows, side, stream=stream)
 
 
-class BoundingBox:
-    """face_detector.py:29-60: integer box with an exclusive right / bottom edge."""
+# ---- landmark alignment (the definition is restated in tests/align_oracle.py) ---------------------------
+# the published five-point template of a 112 x 112 face, pixel-index coordinates, in MTCNN's landmark order
+ARCFACE_112 = ((38.2946, 51.6963), (73.5318, 51.5014), (56.0252, 71.7366), (41.5493, 92.3655), (70.7299, 92.2041))
+ALIGN_MAX_SIDE, ALIGN_MAX_SAMPLES = 256, 8     # FN_FACE_ALIGN_MAX_SIDE / FN_FACE_ALIGN_MAX_SAMPLES of include/facenet_hip.h
+ALIGN_MAX_ENTRY = float(1 << 24)               # every entry of an inverse transform stays below this in magnitude
+ALIGN_SIGMA = (1 / 16, 32.0)                   # source pixels per output pixel of an alignable face
 
-    def __init__(self, left, top, width, height, confidence=None):
+
+def align_template(size, margin=0):
+    """The template for a size x size output, float64 [5, 2] (x, y): the pixel centres of ARCFACE_112 scaled about the image
+    centre; `margin` (the `image.margin` of the box path) shrinks the face by 1 / (1 + margin)."""
+    return (np.asarray(ARCFACE_112, np.float64) + 0.5 - 56) * (size / 112) / (1 + margin) + size / 2 - 0.5
+
+
+class Alignment:
+    """The fitted transforms of F faces: ``inverse`` float64 [F, 6] (output pixel -> frame, rows (i0, i1, i2), (i3, i4, i5)),
+    ``samples`` int32 [F] (sub-samples per axis of the box prefilter), ``ok`` bool [F] (alignable), and per face the roll
+    ``angle`` in degrees, the ``scale`` from frame to output and the rms ``residual`` of the fit relative to the output size.
+    A face that is not alignable has NaN everywhere and 0 samples."""
+
+    def __init__(self, inverse, samples, ok, angle, scale, residual):
+        self.inverse, self.samples, self.ok = inverse, samples, ok
+        self.angle, self.scale, self.residual = angle, scale, residual
+
+    def __len__(self):
+        return len(self.ok)
+
+    def take(self, rows):
+        """The Alignment of a subset of the faces."""
+        return Alignment(np.ascontiguousarray(self.inverse[rows]), np.ascontiguousarray(self.samples[rows]), self.ok[rows], self.angle[rows],
+                         self.scale[rows], self.residual[rows])
+
+
+def align_samples(sigma):
+    """Sub-samples per axis of the box prefilter for `sigma` source pixels per output pixel: min(8, max(1, ceil(sigma)))."""
+    return np.clip(np.ceil(sigma), 1, ALIGN_MAX_SAMPLES).astype(np.int32)
+
+
+def _sum5(t):
+    """Left-to-right sum over the five landmarks of [F, 5] (the order of the definition)."""
+    return t[:, 0] + t[:, 1] + t[:, 2] + t[:, 3] + t[:, 4]
+
+
+def similarity_from_landmarks(landmarks, template, size=112):
+    """The least-squares proper similarity (rotation, uniform scale, translation; never a reflection) from each face's frame
+    landmarks [F, 5, 2] onto `template` [5, 2], in closed form and float64 -> Alignment.  `size` is the output side the template
+    was made for; only the residual uses it.  A face is alignable when its ten numbers are finite, its points do not coincide,
+    it takes 1/16 .. 32 source pixels per output pixel and every inverse entry stays below 2^24; the others get ok = False."""
+    p = np.asarray(landmarks, np.float64).reshape(-1, 5, 2)
+    q = np.asarray(template, np.float64).reshape(5, 2)
+    with np.errstate(all="ignore"):
+        px, py, qx, qy = p[:, :, 0], p[:, :, 1], q[None, :, 0], q[None, :, 1]
+        pmx, pmy, qmx, qmy = _sum5(px) / 5, _sum5(py) / 5, _sum5(qx) / 5, _sum5(qy) / 5
+        cx, cy, dx, dy = px - pmx[:, None], py - pmy[:, None], qx - qmx[:, None], qy - qmy[:, None]
+        den = _sum5(cx * cx + cy * cy)
+        a, b = _sum5(cx * dx + cy * dy) / den, _sum5(cx * dy - cy * dx) / den
+        tx, ty = qmx - (a * pmx - b * pmy), qmy - (b * pmx + a * pmy)
+        d = a * a + b * b
+        ia, ib = a / d, -b / d
+        inverse = np.stack([ia, -ib, -(ia * tx - ib * ty), ib, ia, -(ib * tx + ia * ty)], axis=1)
+        sigma = 1 / np.sqrt(d)
+        ex, ey = (a[:, None] * px - b[:, None] * py) + tx[:, None] - qx, (b[:, None] * px + a[:, None] * py) + ty[:, None] - qy
+        residual = np.sqrt(_sum5(ex * ex + ey * ey) / 5) / size
+        ok = (np.isfinite(p).all(axis=(1, 2)) & np.isfinite(den) & (den > 0) & np.isfinite(d) & (d > 0) &
+              (sigma >= ALIGN_SIGMA[0]) & (sigma <= ALIGN_SIGMA[1]) & (np.abs(inverse) < ALIGN_MAX_ENTRY).all(axis=1))
+        samples = np.where(ok, align_samples(np.where(ok, sigma, 1.0)), 0).astype(np.int32)
+        return Alignment(np.where(ok[:, None], inverse, np.nan), samples, ok, np.where(ok, np.degrees(np.arctan2(b, a)), np.nan),
+                         np.where(ok, np.sqrt(d), np.nan), np.where(ok, residual, np.nan))
+
+
+def check_align_arguments(inverse, samples, size):
+    """The limits of fn_face_align_u8 as ValueError, before anything is launched."""
+    inverse, samples = np.asarray(inverse), np.asarray(samples)
+    if inverse.ndim != 2 or inverse.shape[1] != 6 or not 0 < inverse.shape[0] <= 65535:
+        raise ValueError(f"face align: transforms of shape {inverse.shape}, [F, 6] with 1 <= F <= 65535 expected")
+    if samples.shape != (inverse.shape[0],):
+        raise ValueError(f"face align: samples of shape {samples.shape} for {inverse.shape[0]} faces")
+    if not 0 < size <= ALIGN_MAX_SIDE:
+        raise ValueError(f"face align: size {size} outside 1 .. {ALIGN_MAX_SIDE}")
+    if samples.min() < 1 or samples.max() > ALIGN_MAX_SAMPLES:
+        raise ValueError(f"face align: {samples.min()} .. {samples.max()} sub-samples per axis, 1 .. {ALIGN_MAX_SAMPLES} expected "
+                         "(0 marks a face that is not alignable)")
+    if not (np.abs(inverse) < ALIGN_MAX_ENTRY).all():        # a NaN fails the comparison too
+        raise ValueError("face align: every inverse entry must be finite and below 2^24 in magnitude (NaN marks a face that is not alignable)")
+
+
+_align_workspace = {}     # device -> int64 workspace of the transform tables, grown on demand
+
+
+def align_faces(frame, alignment, size, stream=None):
+    """Warp every face of `alignment` (all of them alignable) out of the frame -> device uint8 [F, size, size, 3], one
+    fn_face_align_u8 launch.  frame: uint8 [H, W, 3], an array or a device tensor."""
+    import ctypes as C
+
+    import torch
+
+    from .. import _lib
+    inverse = np.ascontiguousarray(alignment.inverse, dtype=np.float64)
+    samples = np.ascontiguousarray(alignment.samples, dtype=np.int32)
+    size = int(size)
+    check_align_arguments(inverse, samples, size)
+    frame = _device_frame(frame, "face align")
+    lib = _lib.load()
+    count = inverse.shape[0]
+    nbytes = C.c_longlong(0)
+    _lib.check(lib.fn_face_align_workspace(count, C.byref(nbytes)), "face_align_workspace")
+    work = _align_workspace.get(frame.device)
+    if work is None or work.numel() * 8 < nbytes.value:
+        work = _align_workspace[frame.device] = torch.empty(nbytes.value // 8, dtype=torch.int64, device=frame.device)
+    out = torch.empty(count, size, size, 3, dtype=torch.uint8, device=frame.device)
+    with torch.cuda.device(frame.device):
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(lib.fn_face_align_u8(frame.data_ptr(), frame.shape[0], frame.shape[1], inverse.ctypes.data, samples.ctypes.data, count, size,
+                                        out.data_ptr(), work.data_ptr(), work.numel() * 8, st), "face_align")
+    return out
+
+
+def image_processing_aligned_batch(frame, boxes, options, stream=None):
+    """The network's input for every box of one frame, aligned where that is possible -> (device uint8 [F, size, size, 3],
+    Alignment).  A box whose `landmarks` are alignable is warped onto `align_template(options.size, options.margin)`; every
+    other row holds the bytes of `image_processing_batch(frame, [box], options, centre_crop=True)`."""
+    import torch
+    size = int(options.size)
+    points = np.full((len(boxes), 5, 2), np.nan)
+    for i, box in enumerate(boxes):
+        if getattr(box, "landmarks", None) is not None:
+            points[i] = box.landmarks
+    alignment = similarity_from_landmarks(points, align_template(size, options.margin), size)
+    if len(boxes) == 0:
+        return image_processing_batch(frame, boxes, options, centre_crop=True), alignment
+    frame = _device_frame(frame, "face align")         # one upload for both routes
+    aligned, boxed = np.nonzero(alignment.ok)[0], np.nonzero(~alignment.ok)[0]
+    if len(boxed) == 0:
+        return align_faces(frame, alignment, size, stream), alignment
+    out = torch.empty(len(boxes), size, size, 3, dtype=torch.uint8, device=frame.device)
+    out[torch.from_numpy(boxed).to(frame.device)] = image_processing_batch(frame, [boxes[i] for i in boxed], options, centre_crop=True, stream=stream)
+    if len(aligned):
+        out[torch.from_numpy(aligned).to(frame.device)] = align_faces(frame, alignment.take(aligned), size, stream)
+    return out, alignment
+
+
+class BoundingBox:
+    """face_detector.py:29-60: integer box with an exclusive right / bottom edge.  `landmarks`: the detector's five points in
+    frame coordinates, float32 [5, 2] (x, y) in the order left eye, right eye, nose, mouth left, mouth right, or None."""
+
+    def __init__(self, left, top, width, height, confidence=None, landmarks=None):
         self.left, self.top = int(np.round(left)), int(np.round(top))
         self.right, self.bottom = int(np.round(left + width)) + 1, int(np.round(top + height)) + 1
         self.width, self.height = self.right - self.left - 1, self.bottom - self.top - 1
         self.confidence = confidence
+        self.landmarks = None if landmarks is None else np.asarray(landmarks, np.float32).reshape(5, 2)
 
     def info(self, mode=False):
         fields = [self.left, self.top, self.width, self.height, self.confidence]
@@ -128,12 +281,19 @@ class MTCNN:
     """face_detector.py:63-78."""
 
     def __init__(self, **kwargs):
-        self.__detector = _mtcnn.MTCNN(**kwargs).detect_faces
+        self.__detector = _mtcnn.MTCNN(**kwargs).detect_boxes
         self.mode = 'RGB'
 
     def detector(self, image):
-        return [BoundingBox(left=f['box'][0], top=f['box'][1], width=f['box'][2], height=f['box'][3], confidence=f['confidence'])
-                for f in self.__detector(image)]
+        """The boxes of `detect_faces` (its truncation to integers and its max(0, ...)), each with the float landmarks that
+        `detect_faces` truncates."""
+        total, points = self.__detector(image)
+        boxes = []
+        for box, kp in zip(total, points.T):
+            x, y = max(0, int(box[0])), max(0, int(box[1]))
+            boxes.append(BoundingBox(left=x, top=y, width=int(box[2] - x), height=int(box[3] - y), confidence=box[-1],
+                                     landmarks=np.stack([kp[0:5], kp[5:10]], axis=1)))
+        return boxes
 
 
 class FaceDetector:

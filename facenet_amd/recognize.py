@@ -5,6 +5,8 @@
 centre cut of `image.size`), whose uint8 output goes straight to `FaceNet.evaluate`.  The network plans one launch list (and
 captures one graph) per batch size, so the face batch is zero-padded up to one of `BATCH_SIZES`: photos with 1, 2 or 3 faces
 share a plan.  Inference has no coupling between the images of a batch, so the padding rows change nothing.
+``align=True`` (default: the `image.align` key, off when absent) replaces the box crop with the landmark alignment of DESIGN.md
+section 22 (`image_processing_aligned_batch`); ``max_residual`` then drops faces whose landmarks fit the template badly.
 
 ``Gallery(embeddings, labels, names, files, metric)`` answers "who is this?" (DESIGN.md section 19): it keeps the known faces'
 embeddings on the device and ``search`` returns each query's k nearest rows from one fn_gallery_search call, whose distances
@@ -25,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .detectors.face_detector import image_processing_batch
+from .detectors.face_detector import image_processing_aligned_batch, image_processing_batch
 from .faceclass import _as_table, _ptr, _stream
 from .statistics import check_unit_range
 
@@ -41,9 +43,11 @@ def padded_batch(n: int) -> int:
 
 
 class FacePipeline:
-    def __init__(self, detector, facenet, image_options, device="cuda:0"):
+    def __init__(self, detector, facenet, image_options, device="cuda:0", align=None, max_residual=None):
         self.detector, self.facenet, self.image_options = detector, facenet, image_options
         self.device = torch.device(device)
+        self.align = bool(getattr(image_options, "align", False)) if align is None else bool(align)
+        self.max_residual = max_residual
 
     def _frame(self, image):
         """uint8 [H, W, 3] in the detector's channel order -> the one device copy of it."""
@@ -53,10 +57,27 @@ class FacePipeline:
         return torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(self.device)
 
     def crops(self, image):
-        """-> (list of BoundingBox, device uint8 [F, size, size, 3])."""
+        """-> (list of BoundingBox, device uint8 [F, size, size, 3]); with `align`, the faces that `aligned_crops` keeps."""
+        if self.align:
+            return self.aligned_crops(image)[:2]
         frame = self._frame(image)
         boxes = self.detector.detect(frame)
         return boxes, image_processing_batch(frame, boxes, self.image_options, centre_crop=True)
+
+    def aligned_crops(self, image):
+        """-> (list of BoundingBox, device uint8 [F, size, size, 3], Alignment): every detected face warped onto the five-point
+        template by its own landmarks (`image_processing_aligned_batch`; a face that is not alignable keeps the box path's
+        pixels).  With `max_residual`, aligned faces whose landmarks fit the template worse than that are dropped here, before
+        any network launch."""
+        frame = self._frame(image)
+        boxes = self.detector.detect(frame)
+        crops, alignment = image_processing_aligned_batch(frame, boxes, self.image_options)
+        if self.max_residual is not None and len(boxes):
+            keep = np.nonzero(~(alignment.residual > self.max_residual))[0]          # NaN (not aligned) stays
+            if len(keep) < len(boxes):
+                boxes, alignment = [boxes[i] for i in keep], alignment.take(keep)
+                crops = crops[torch.from_numpy(keep).to(crops.device)]
+        return boxes, crops, alignment
 
     def embed(self, crops):
         """device uint8 [F, size, size, 3] -> float32 [F, E] through FaceNet.evaluate at the padded batch size."""

@@ -218,6 +218,19 @@ int fn_augment_u8(const uint8_t* src, const long long* offsets, const int32_t* h
 int fn_face_crop_workspace(const int32_t* windows, int F, int side, long long* words);
 int fn_face_crop_resize_u8(const uint8_t* frame, int H, int W, const int32_t* windows, int F, int side, int ox, int oy, int S, uint8_t* dst,
                            int32_t* workspace, long long workspace_words, void* stream);
+/* Landmark alignment: F faces of one HWC u8 frame [H,W,3] in device memory, each warped through its own
+ * inverse similarity transform onto dst u8 [F,S,S,3].  `inverse` is HOST memory, F x (i0, i1, i2, i3, i4, i5): sub-sample
+ * (uu, vv) of the output reads the frame at x = (i0 uu + i1 vv) + i2, y = (i3 uu + i4 vv) + i5 with bilinear taps that are 0
+ * outside the frame; `samples` is HOST memory, F x n: output pixel (u, v) is the mean, rounded half to even, of its n x n
+ * sub-samples uu = u + ((i + 0.5) / n - 0.5), likewise vv (a box prefilter; n = 1 is the plain bilinear warp).  All fp64 without
+ * contraction.  Limits: F <= 65535, S <= FN_FACE_ALIGN_MAX_SIDE, 1 <= n <= FN_FACE_ALIGN_MAX_SAMPLES, every inverse entry
+ * finite and below 2^24 in magnitude.  `workspace` is 8-byte aligned device memory of at least the bytes
+ * fn_face_align_workspace reports; both tables are copied into it on `stream`, then one launch follows. */
+#define FN_FACE_ALIGN_MAX_SIDE 256
+#define FN_FACE_ALIGN_MAX_SAMPLES 8
+int fn_face_align_workspace(int F, long long* bytes);
+int fn_face_align_u8(const uint8_t* frame, int H, int W, const double* inverse, const int32_t* samples, int F, int S, uint8_t* dst,
+                     void* workspace, long long workspace_bytes, void* stream);
 /* gather rows of a u8 image pool by index (triplet batch assembly): out[i] = pool[idx[i]].  bytes_per_image must be a multiple
  * of 16 (the images are copied as 16-byte vectors; fn_crop_or_pad_u8 / fn_augment_u8 refuse odd sizes likewise, so a 299 x 299 x 3
  * pool is not supported); anything else is rejected before the launch. */
