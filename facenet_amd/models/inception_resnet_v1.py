@@ -44,8 +44,8 @@ class InceptionResnetV1:
         key = (n, training)
         if key not in self._plans:
             plan = self.network.plan(n, training=training)
-            if n >= 16:     # batches worth the ~0.3 s: time the tile variants of every convolution once (train.autotune_convs)
-                from ..train import autotune_convs
+            if n >= 16:     # batches worth the ~0.3 s: time the tile variants of every convolution once (grouping.autotune_convs)
+                from ..grouping import autotune_convs
                 if not training:
                     self.network.refresh_folded(self.network.stream())
                 autotune_convs(plan.fwd, self.network)

@@ -63,15 +63,8 @@ def _tensors(net, plan):
     return out
 
 
-TRAINER_TENSORS = ("G", "hyper", "loss", "demb", "embn", "dembn", "emb_lp", "logits", "dlogits", "labels", "reg_terms", "centers",
-                   "center_rows", "shadow")
-
-
 def _trainer_tensors(tr):
-    out = {"tr." + k: getattr(tr, k) for k in TRAINER_TENSORS if isinstance(getattr(tr, k, None), torch.Tensor)}
-    for j, s in enumerate(tr.slots):
-        out[f"tr.slot{j}"] = s
-    return out
+    return {"tr." + k: t for k, t in tr.tensors.items()}
 
 
 def _spans(tensors):
@@ -228,14 +221,23 @@ CASES = {
     "trainer_triplet_force_segments": ({}, _trainer(force_segments=True)),
     **{f"trainer_softmax_regularized_{name.lower()}": ({}, _trainer("softmax", optimizer=name, **REGULARIZED))
        for name in ("ADAGRAD", "ADADELTA", "ADAM", "RMSPROP", "MOM")},
+    "trainer_softmax_margin_arcface": ({}, _trainer("softmax", margin_scale=64, margin_arc=0.5)),
+    "trainer_softmax_margin_regularized_rmsprop": ({}, _trainer("softmax", margin_scale=30, margin_arc=0.3, margin_cos=0.1, optimizer="RMSPROP",
+                                                                **REGULARIZED)),
+    "trainer_softmax_regularized_force_segments": ({}, _trainer("softmax", force_segments=True, **REGULARIZED)),
 }
 
 
-def digest(key):
-    """{"ops": launches, "sha256": of the canonical JSON} of one case, lowered under the case's environment."""
+def lowered(key):
+    """The canonical signature of one case, lowered under the case's environment."""
     env, build = CASES[key]
     with _environ(dict(dict.fromkeys(OPTION_VARS), **env)):      # every option the case does not set is at its default
-        sig = build()
+        return build()
+
+
+def digest(key, sig=None):
+    """{"ops": launches, "sha256": of the canonical JSON} of one case (``sig``: its signature, when already lowered)."""
+    sig = lowered(key) if sig is None else sig
     n = len(sig["launches"] if isinstance(sig, dict) else sig)
     return {"ops": n, "sha256": hashlib.sha256(json.dumps(sig, sort_keys=True).encode()).hexdigest()}
 

@@ -1,10 +1,12 @@
 """Fingerprint of what a training step launches and computes, for before / after comparisons of engine.py and train.py.
 
 Grouping needs the compiled library, so the host pin (tests/plan_signature.py) cannot see grouped step lists.  This builds
-three trainers with fixed seeds and FACENET_AUTOTUNE=0 -- batch-90 triplet; softmax with center loss, prelogits norm, the moving
-average and RMSPROP; triplet with force_segments -- and prints one JSON line each: the names of ``step_ops`` and the SHA-256 of
+four trainers with fixed seeds and FACENET_AUTOTUNE=0 -- batch-90 triplet; softmax with center loss, prelogits norm, the moving
+average and RMSPROP; triplet with force_segments; the margin softmax with center loss under Adam -- and prints one JSON line
+each: the names of ``step_ops`` and the SHA-256 of
 P, S_mean, S_var and the optimizer slots after five captured steps.  Training is bit-reproducible, so two revisions that lower
-to the same launches print byte-identical output (profiles/lowering_refactor_step_compare_*.txt)."""
+to the same launches print byte-identical output (profiles/lowering_refactor_step_compare_*.txt,
+profiles/trainer_split_step_compare_*.txt)."""
 import hashlib
 import json
 import os
@@ -47,3 +49,5 @@ run("triplet_90", 90, loss="triplet")
 run("softmax_center_rmsprop_ema", 30, classes=10, loss="softmax", center_factor=0.01, prelogits_norm_factor=5e-4,
     moving_average_decay=0.9999, optimizer="RMSPROP")
 run("triplet_force_segments", 30, loss="triplet", force_segments=True)
+run("softmax_margin_center_adam", 30, classes=10, loss="softmax", margin_scale=30, margin_arc=0.5, center_factor=0.01,
+    optimizer="ADAM")
