@@ -23,6 +23,8 @@ DEFAULTS = {   # apps/configs/validate.yaml of the reference
     "dataset": {"path": "~/datasets/vggface2/test_extracted_160", "h5file": None, "nrof_classes": None, "min_nrof_images": None,
                 "max_nrof_images": None},
     "model": {"path": None},
+    # validate.far_targets (not set here: absent means None): a list of false-accept rates; the exact VerificationCurve at these
+    # rates is appended to the report
     "validate": {"nrof_folds": 10, "metric": 0, "far_target": 0.001},
     "file": None,
 }
@@ -51,12 +53,13 @@ def load_options(path=None, overrides: dict = None) -> Config:
 
 
 def validate(options, log=print):
-    """Returns the FaceToFaceValidation; ``options`` as ``load_options`` builds them."""
+    """Returns the FaceToFaceValidation; ``options`` as ``load_options`` builds them.  ``report.curve`` is the VerificationCurve
+    that ``validate.far_targets`` asks for, None without the key."""
     from facenet_amd import dataset
     from facenet_amd.api import FaceNet
     from facenet_amd.apps.train_classifier import write_text_log
     from facenet_amd.facenet import evaluate_embeddings
-    from facenet_amd.statistics import FaceToFaceValidation
+    from facenet_amd.statistics import FaceToFaceValidation, verification_curve
 
     start = time.monotonic()
     options.file.parent.mkdir(parents=True, exist_ok=True)
@@ -77,6 +80,10 @@ def validate(options, log=print):
     report = FaceToFaceValidation(embeddings, labels, options.validate)
     report.write_report(options.file)
     log(report)
+    report.curve = verification_curve(embeddings, labels, options.validate)
+    if report.curve is not None:
+        write_text_log(options.file, report.curve)
+        log(report.curve)
 
     with options.file.open("at") as f:
         f.write("elapsed time: {:.3f}\n".format(time.monotonic() - start))

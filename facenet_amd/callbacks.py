@@ -62,7 +62,9 @@ class ValidateCallback:
 
     ``model``: callable from uint8 images to unit-norm embeddings (``None``: the training app attaches its trainer);
     ``dataset``: an iterable of (images, labels) that can be walked repeatedly; ``config.validate``: metric, nrof_folds,
-    far_target.  ``history`` collects (epoch, FaceToFaceValidation.dict, seconds embedding, seconds statistics).
+    far_target, and far_targets (optional: the exact VerificationCurve at these rates follows the report and is set on it as
+    ``report.curve``; without the key the report object is left as the statistic made it).
+    ``history`` collects (epoch, FaceToFaceValidation.dict, seconds embedding, seconds statistics).
 
     Data parallel: every rank embeds the batches ``rank::world``, the embeddings are all-gathered in data-set order, rank 0
     computes, logs and writes the report; ``on_epoch_end`` is collective."""
@@ -150,16 +152,25 @@ class ValidateCallback:
         if statistic is None:
             from .statistics import FaceToFaceValidation as statistic
         report = statistic(embeddings, labels, self.config.validate)
+        from .statistics import verification_curve
+        curve = verification_curve(embeddings, labels, self.config.validate)        # None unless validate.far_targets is set
+        if curve is not None:
+            report.curve = curve
         t2 = time.perf_counter()
         self.embeddings, self.labels = embeddings, labels
         self.history.append((epoch1, report.dict, t1 - t0, t2 - t1))
         self.log(str(report))
+        if curve is not None:
+            self.log(str(curve))
         self.log(f"validation: embedding {t1 - t0:.3f} s, statistics {t2 - t1:.3f} s")
         path = getattr(self._model, "path", None)
         if path:
             path = Path(path).expanduser()
             path.mkdir(parents=True, exist_ok=True)
             report.write_report(path / "report.txt")
+            if curve is not None:
+                from .apps.train_classifier import write_text_log
+                write_text_log(path / "report.txt", curve)
         return report
 
     def on_epoch_end(self, epoch, logs=None):

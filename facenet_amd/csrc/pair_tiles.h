@@ -1,6 +1,9 @@
 // The exact-fp32 pair machinery: ONE definition of everything that decides a bit of a pair's distance or of the `range` words, for
-// the kernels that compare distances exactly (loss.hip: fn_pairwise_sqdist; validation.hip: the confusion counts; identify.hip:
-// the k nearest rows; cluster.hip: every row within a radius; faceclass.hip takes tri_decode alone).  DESIGN.md section 16.
+// the kernels that compare distances exactly (validation.hip: the confusion counts; identify.hip: the k nearest rows; cluster.hip:
+// every row within a radius; faceclass.hip takes tri_decode alone).  DESIGN.md section 16.  loss.hip's fn_pairwise_sqdist takes
+// ord_f32, DotRange and pair_distance from here but NOT the dot product: it sums s by wavefront reduction, so its distances agree
+// with the chain's to rounding, not in bits.
+// verification.hip histograms the bit patterns of d themselves (the exact TAR at FAR, EER and ROC: DESIGN.md section 23).
 //
 // What it guarantees: a dot product s is the ascending-e fmaf chain from 0.0f (v_mfma_f32_16x16x4_f32 fed through mfma_chunk is
 // that chain bit for bit, and so is dot_chain); sc = min(max(s, -1), 1); d = 2 (1 - sc) (metric 0) or arccos(sc) (metric 1); the

@@ -401,3 +401,295 @@ class FaceToFaceValidation:
         from pathlib import Path
         with Path(file).expanduser().open('at') as f:
             f.write(self._text(64 * '-' + '\n' + '{} {}\n'.format(self.__class__.__name__, datetime.datetime.now())))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The exact verification curve: TAR at FAR, EER, ROC and AUC over ALL pairs.  A distance is the
+# same bits in every pass (csrc/pair_tiles.h), so the (m + 1)-th smallest impostor distance is found by radix selection
+# over recomputed distances: fn_pair_key_histogram counts the pairs of a few key windows, the host narrows a key interval
+# per target and asks for finer windows.  The descent itself is a pure function of (windows) -> counts.
+# ------------------------------------------------------------------------------------------------------------------
+KEY_BINS = 1024                  # bins per window of fn_pair_key_histogram
+KEY_WINDOWS = 8                  # windows per launch
+KEY_TOP = {0: 0x40800000, 1: 0x40490FDB}       # the key of the largest distance: 4.0 and fp32 pi (FaceToFaceValidation._UPPER)
+# The first pass: the octaves [2, 4), [1, 2), ... [2^-6, 2^-5), 1024 bins of 2^13 keys each.  One window that is linear in the key
+# over [0, 4] has bins half a unit wide at d = 2: a useless ROC and a descent of four passes (shift 21, 11, 1, 0); from an octave
+# bin it takes three (13, 3, 0).  What lies below 2^-6 is one "below" count, and a target there takes four passes.
+FIRST_WINDOWS = ([0x40000000 - (j << 23) for j in range(KEY_WINDOWS)], [13] * KEY_WINDOWS)
+
+
+def f32_key(x) -> int:
+    """The bit pattern of an fp32 value >= +0 as an integer: keys order as the values do."""
+    return int(np.array([x], dtype=np.float32).view(np.uint32)[0])
+
+
+def key_f32(key: int) -> float:
+    return float(np.array([key], dtype=np.uint32).view(np.float32)[0])
+
+
+class KeyTarget:
+    """One key the descent looks for: the largest key k with ``low(cumG(k), cumI(k))``, cumG / cumI the numbers of genuine /
+    impostor pairs whose key is below k.  ``low`` is true at key 0, false above the largest key and never true after it was
+    false.  The key lies in [klo, khi]; at_lo / at_hi are (cumG, cumI) at klo and at khi + 1."""
+
+    __slots__ = ("low", "klo", "khi", "at_lo", "at_hi")
+
+    def __init__(self, low, top: int, totals):
+        self.low, self.klo, self.khi, self.at_lo, self.at_hi = low, 0, int(top), (0, 0), tuple(int(v) for v in totals)
+
+    @property
+    def found(self):
+        return self.klo == self.khi
+
+
+def window_counts(counts):
+    """uint64 [2, KEY_BINS + 2] of one window -> uint64 [2, KEY_BINS + 1]: the pairs below each of the window's bin edges."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    cum = np.empty((2, KEY_BINS + 1), dtype=np.uint64)
+    cum[:, 0] = counts[:, KEY_BINS]
+    cum[:, 1:] = counts[:, KEY_BINS, None] + np.cumsum(counts[:, :KEY_BINS], axis=1, dtype=np.uint64)
+    return cum
+
+
+def narrow(target: KeyTarget, lo: int, shift: int, cum):
+    """Intersect the target's interval with what one window's edge counts say (edge b is the key lo + (b << shift))."""
+    at = lambda b: (int(cum[0, b]), int(cum[1, b]))
+    if not target.low(*at(0)):
+        b = -1                                           # the key is below the window
+    else:
+        b, top = 0, KEY_BINS                             # the last edge that is still low
+        while b < top:
+            mid = (b + top + 1) // 2
+            if target.low(*at(mid)):
+                b = mid
+            else:
+                top = mid - 1
+    if b >= 0 and lo + (b << shift) > target.klo:
+        target.klo, target.at_lo = lo + (b << shift), at(b)
+    if b < KEY_BINS and lo + ((b + 1) << shift) - 1 < target.khi:
+        target.khi, target.at_hi = lo + ((b + 1) << shift) - 1, at(b + 1)
+    if target.klo > target.khi:
+        raise RuntimeError("key descent: the counts of two passes contradict each other")
+
+
+def key_descent(histogram, targets, first=None) -> int:
+    """Find every target.  ``histogram(lo, shift)`` -> uint64 [R, 2, KEY_BINS + 2] as fn_pair_key_histogram fills it, for R <= 8
+    windows.  Targets are refined together in groups of 8, one window each: the window starts at klo and takes the smallest
+    shift that covers [klo, khi], so an interval of n keys shrinks to n / 1024 per pass.  Every window of a pass informs every
+    open target.  ``first``: (lo, shift, counts) of a pass that has been run already.  -> the number of passes run."""
+    def apply(lo, shift, counts):
+        for r in range(len(lo)):
+            cum = window_counts(counts[r])
+            for t in targets:
+                if not t.found:
+                    narrow(t, int(lo[r]), int(shift[r]), cum)
+
+    if first is not None:
+        apply(*first)
+    passes = 0
+    for g in range(0, len(targets), KEY_WINDOWS):
+        group = targets[g:g + KEY_WINDOWS]
+        while True:
+            todo = [t for t in group if not t.found]
+            if not todo:
+                break
+            lo = [t.klo for t in todo]
+            shift = [max(0, (t.khi - t.klo).bit_length() - 10) for t in todo]        # the smallest with (khi - klo) >> shift < 1024
+            apply(lo, shift, np.asarray(histogram(lo, shift)))
+            passes += 1
+    return passes
+
+
+class VerificationCurve:
+    """The exact verification curve of a set of embeddings: every unordered pair of distinct rows is evaluated once, genuine when
+    both rows carry one label and impostor otherwise; d is the distance ``Gallery`` and ``ConfidenceMatrix`` compute, bit for
+    bit (``pairwise_similarities`` sums in another order: equal to rounding only), and a pair is accepted at threshold t when
+    d < t (strict fp32), as every consumer decides.  ``tar_at_far`` gives the largest threshold whose false accepts stay within f
+    times the impostor pairs; integers are exact, ratios are formed from them."""
+
+    def __init__(self, embeddings, labels, metric=0, device: str = "cuda", atol: float = 1.e-5):
+        if metric not in KEY_TOP:
+            raise ValueError('Undefined similarity metric {}'.format(metric))
+        sizes = [int(c) for c in np.unique(np.asarray(labels), return_counts=True)[1]]
+        n = sum(sizes)
+        genuine = sum(c * (c - 1) // 2 for c in sizes)
+        self._init(self._device_histogram, genuine, n * (n - 1) // 2 - genuine, metric)      # rejects an empty population: no launch
+        calc = SimilarityCalculator(embeddings, labels, metric=metric, device=device)
+        emb = calc.emb
+        if emb.shape[1] % 4:       # zeros add fma(0, 0, acc) = acc: no bit of a dot product changes
+            emb = torch.nn.functional.pad(emb, (0, 4 - emb.shape[1] % 4)).contiguous()
+        self._emb, self._cls, self._classes, self._atol = emb, calc._cls, calc.nrof_classes, atol
+
+    @classmethod
+    def from_histogram(cls, histogram, nrof_genuine: int, nrof_impostor: int, metric=0):
+        """A curve over any ``histogram(lo, shift)`` that counts like fn_pair_key_histogram (the tests' NumPy stand-in)."""
+        self = cls.__new__(cls)
+        self._init(histogram, nrof_genuine, nrof_impostor, metric)
+        return self
+
+    def _init(self, histogram, nrof_genuine, nrof_impostor, metric):
+        if metric not in KEY_TOP:
+            raise ValueError('Undefined similarity metric {}'.format(metric))
+        self.metric, self.nrof_genuine, self.nrof_impostor = metric, int(nrof_genuine), int(nrof_impostor)
+        if self.nrof_genuine < 1 or self.nrof_impostor < 1:
+            raise ValueError("a verification curve needs genuine and impostor pairs, got {} and {}".format(self.nrof_genuine,
+                                                                                                            self.nrof_impostor))
+        self._histogram = histogram
+        self.nrof_passes = 0          # launches so far
+        self.nrof_groups = 0          # groups of <= 8 targets refined so far
+        self._first = None            # (lo, shift, counts) of the first pass
+        self._far, self._eer, self._asked, self._buffer = {}, None, {}, None
+
+    def _device_histogram(self, lo, shift):
+        """One launch.  `out` and the two `range` words share one buffer, allocated once per curve: a pass costs one fill and one
+        transfer to the host, its only synchronisation."""
+        import ctypes
+        lib = _lib.load()
+        R, words = len(lo), len(lo) * 2 * (KEY_BINS + 2)
+        dev = self._emb.device
+        if self._buffer is None:
+            self._buffer = torch.empty(KEY_WINDOWS * 2 * (KEY_BINS + 2) + 1, dtype=torch.int64, device=dev)
+        buf = self._buffer[:words + 1]
+        buf.zero_()
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.fn_pair_key_histogram(_ptr(self._emb), _ptr(self._cls), self._classes, self._emb.shape[1], self.metric,
+                                             (ctypes.c_uint32 * R)(*lo), (ctypes.c_int32 * R)(*shift), R, _ptr(buf), _ptr(buf, words), st),
+                   "pair_key_histogram")
+        host = buf.cpu()
+        check_unit_range(host[words:].view(torch.int32), self._atol)
+        return host[:words].numpy().view(np.uint64).reshape(R, 2, KEY_BINS + 2)
+
+    # ---- the passes --------------------------------------------------------------------------------------------------------
+    def _first_pass(self):
+        if self._first is None:
+            lo, shift = FIRST_WINDOWS
+            counts = np.asarray(self._histogram(lo, shift))
+            self.nrof_passes += 1
+            if [int(v) for v in counts[0, :, KEY_BINS + 1]] != [self.nrof_genuine, self.nrof_impostor]:
+                raise RuntimeError("pair_key_histogram counted {} pairs, the labels give {}".format(
+                    counts[0, :, KEY_BINS + 1].tolist(), [self.nrof_genuine, self.nrof_impostor]))
+            self._first = (lo, shift, counts)
+        return self._first
+
+    def _target(self, low):
+        return KeyTarget(low, KEY_TOP[self.metric], (self.nrof_genuine, self.nrof_impostor))
+
+    def _resolve(self, ranks=()):
+        """Find the thresholds of the impostor ranks that are not known yet, and the EER with them."""
+        new = []
+        if self._eer is None:
+            Gn, I = self.nrof_genuine, self.nrof_impostor
+            self._eer = self._target(lambda g, i: i * Gn < (Gn - g) * I)
+            new.append(self._eer)
+        for m in ranks:
+            if m not in self._far:
+                self._far[m] = self._target(lambda g, i, m=m: i <= m)
+                new.append(self._far[m])
+        if new:
+            first = self._first_pass()
+            self.nrof_passes += key_descent(self._histogram, new, first=first)
+            self.nrof_groups += -(-len(new) // KEY_WINDOWS)
+
+    # ---- the public interface ----------------------------------------------------------------------------------------------
+    def tar_at_far(self, fars):
+        """One record per false-accept rate f, ascending in [0, 1]: m = int(f * impostor pairs) in exact arithmetic, ``threshold``
+        the (m + 1)-th smallest impostor distance (the largest fp32 t with at most m impostor pairs d < t; +inf when m reaches
+        the number of impostor pairs), ``false_accepts`` / ``true_accepts`` the impostor / genuine pairs with d < threshold (ties
+        may leave false_accepts below m), ``far`` and ``tar`` their shares."""
+        from fractions import Fraction
+        fars = [float(f) for f in np.atleast_1d(np.asarray(fars, dtype=np.float64))]
+        if any(not 0.0 <= f <= 1.0 for f in fars):
+            raise ValueError("false-accept rates must lie in [0, 1], got {}".format(fars))
+        if any(b < a for a, b in zip(fars, fars[1:])):
+            raise ValueError("false-accept rates must be ascending, got {}".format(fars))
+        Gn, I = self.nrof_genuine, self.nrof_impostor
+        ranks = [int(Fraction(f) * I) for f in fars]
+        self._resolve([m for m in ranks if m < I])
+        records = []
+        for f, m in zip(fars, ranks):
+            if m < I:
+                t, (ta, fa) = key_f32(self._far[m].klo), self._far[m].at_lo
+            else:
+                t, ta, fa = float("inf"), Gn, I
+            self._asked[f] = {"far_target": f, "threshold": t, "false_accepts": fa, "true_accepts": ta, "far": fa / I, "tar": ta / Gn}
+            records.append(dict(self._asked[f]))
+        return records
+
+    def threshold_at_far(self, f) -> float:
+        return self.tar_at_far([f])[0]["threshold"]
+
+    def eer(self):
+        """``eer_threshold``: the smallest fp32 t whose false-accept share reaches its false-reject share (compared in
+        integers); ``far`` and ``frr`` there, ``eer`` their mean."""
+        self._resolve()
+        Gn, I = self.nrof_genuine, self.nrof_impostor
+        ta, fa = self._eer.at_hi                              # one key above the last one that is still low
+        far, frr = fa / I, (Gn - ta) / Gn
+        return {"eer": (far + frr) / 2, "eer_threshold": key_f32(self._eer.klo + 1), "far": far, "frr": frr, "false_accepts": fa,
+                "true_accepts": ta}
+
+    def roc_counts(self):
+        """(keys, true_accepts, false_accepts), Python integers: the pairs with a key below each bin edge of the first pass, key 0
+        and the key above the largest distance included."""
+        lo, shift, counts = self._first_pass()
+        at = {0: (0, 0), KEY_TOP[self.metric] + 1: (self.nrof_genuine, self.nrof_impostor)}
+        for r in range(len(lo)):
+            cum = window_counts(counts[r])
+            for b in range(KEY_BINS + 1):
+                key = lo[r] + (b << shift[r])
+                if key <= KEY_TOP[self.metric]:
+                    at[key] = (int(cum[0, b]), int(cum[1, b]))
+        keys = sorted(at)
+        return keys, [at[k][0] for k in keys], [at[k][1] for k in keys]
+
+    def roc(self):
+        """(far, tar, threshold), ascending: the exact shares of impostor / genuine pairs with d < threshold at every bin edge of
+        the first pass (float64, float64, float32 arrays)."""
+        keys, ta, fa = self.roc_counts()
+        return (np.array([v / self.nrof_impostor for v in fa]), np.array([v / self.nrof_genuine for v in ta]),
+                np.array(keys, dtype=np.uint32).view(np.float32))
+
+    def auc(self):
+        """(auc, auc_lo, auc_hi): the share of (genuine, impostor) pairs of pairs the genuine one of which is nearer, ties counted
+        1/2, lies in [auc_lo, auc_hi]: pairs of pairs that share a bin of the first pass are left out of auc_lo and counted in
+        auc_hi; auc is the midpoint.  Exact integers up to the last division."""
+        from fractions import Fraction
+        _, ta, fa = self.roc_counts()
+        Gn, I = self.nrof_genuine, self.nrof_impostor
+        above = sum((ta[b + 1] - ta[b]) * (I - fa[b + 1]) for b in range(len(ta) - 1))
+        tied = sum((ta[b + 1] - ta[b]) * (fa[b + 1] - fa[b]) for b in range(len(ta) - 1))
+        lo, hi = Fraction(above, Gn * I), Fraction(above + tied, Gn * I)
+        return float((lo + hi) / 2), float(lo), float(hi)
+
+    def dict(self):
+        auc, auc_lo, auc_hi = self.auc()
+        out = {"metric": self.metric, "nrof_genuine": self.nrof_genuine, "nrof_impostor": self.nrof_impostor, "auc": auc,
+               "auc_lo": auc_lo, "auc_hi": auc_hi}
+        out.update(self.eer())
+        out["tar_at_far"] = [dict(self._asked[f]) for f in sorted(self._asked)]
+        return out
+
+    def __repr__(self):
+        d = self.dict()
+        text = ('{}\nmetric: {}\n\ngenuine pairs: {}\nimpostor pairs: {}\nArea under curve (AUC): {:1.5f} [{:1.5f}, {:1.5f}]\n'
+                'Equal error rate (EER): {:1.5f}\nThreshold: {:2.5f}\n\n').format(
+                    self.__class__.__name__, d["metric"], d["nrof_genuine"], d["nrof_impostor"], d["auc"], d["auc_lo"], d["auc_hi"],
+                    d["eer"], d["eer_threshold"])
+        for r in d["tar_at_far"]:
+            text += ('TAR @ FAR = {}\nTrue accept rate (TAR):  {:1.5f} ({} of {})\nFalse accept rate (FAR): {:.3e} ({} of {})\n'
+                     'Threshold: {:2.5f}\n\n').format(r["far_target"], r["tar"], r["true_accepts"], d["nrof_genuine"], r["far"],
+                                                      r["false_accepts"], d["nrof_impostor"], r["threshold"])
+        return text
+
+
+def verification_curve(embeddings, labels, config, device: str = "cuda"):
+    """The curve ``config.far_targets`` asks for (a list of false-accept rates, ascending), evaluated; None when the key is unset:
+    the one helper of apps/validate.py and ValidateCallback."""
+    from .config import Config
+    fars = getattr(config, "far_targets", None)
+    if fars is None or isinstance(fars, Config):        # a Config reads a missing key as an empty Config
+        return None
+    curve = VerificationCurve(embeddings, labels, metric=config.metric, device=device)
+    curve.tar_at_far(sorted(float(f) for f in np.atleast_1d(fars)))
+    curve.eer()
+    return curve

@@ -366,6 +366,18 @@ int fn_confidence_counts_folds(const float* emb, const int32_t* cls_start, const
                                const int32_t* train_classes, int C, int E, int F, const float* thresholds, int T, int metric,
                                double* out, int32_t* range, void* stream);
 
+/* ---- the exact verification curve: windowed histograms of the keys of ALL pairs, per population.  emb,
+ * cls_start, C, metric and range: as fn_confidence_counts; E a multiple of 4 in [4, 512]; emb and out 16-byte aligned.  A pair of
+ * rows of one class is genuine (population 0), any other pair an impostor (population 1); every unordered pair of distinct rows is
+ * evaluated once.  Its key k is the bit pattern of its fp32 distance d (d >= +0, so keys order as distances do), d the very bits
+ * of fn_confidence_counts, fn_gallery_search and fn_radius_*.  lo uint32 [R], shift int32 [R]: HOST arrays,
+ * 1 <= R <= 8 windows of 1024 bins, 0 <= shift <= 22; a pair lands in bin (k - lo[r]) >> shift[r] of window r when k >= lo[r] and
+ * that bin is < 1024.  out uint64 [R][2][1024 + 2], zeroed by the caller: per window and population the 1024 bins, the number of
+ * pairs with k < lo[r], the population's number of pairs.  Counts are added with 64-bit integer atomics: the result does not
+ * depend on scheduling.  The call allocates nothing and does not synchronise. */
+int fn_pair_key_histogram(const float* emb, const int32_t* cls_start, int C, int E, int metric, const uint32_t* lo,
+                          const int32_t* shift, int R, unsigned long long* out, int32_t* range, void* stream);
+
 /* ---- 1:N identification: for each of Q query rows the k nearest of G gallery rows; the [Q, G] distance
  * matrix never reaches memory.  s(q, g) is the same fp32 fmaf chain as fn_confidence_counts (exact fp32 MFMA), sc = s clipped to
  * [-1, 1]; rows are ranked by ascending (2 (1 - sc), gallery row) for both metrics, equal distances going to the lower row; dist
