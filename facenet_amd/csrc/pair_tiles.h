@@ -10,7 +10,12 @@
 // callers compare d with the strict fp32 <.  `range` receives ord_f32 of the smallest and largest RAW s of the pairs a kernel
 // evaluated, and keeps its initial words (which decode to hi < lo) when it evaluated none.
 //
+// Which pairs are evaluated is defined here too: the gallery walk (identify.hip, cluster.hip) and the class-pair walk
+// (validation.hip's confidence_folds_kernel, verification.hip's pair_key_histogram_kernel; confidence_kernel keeps its own scalar
+// walk: it is the independent reference of the exactness tests).
+//
 // A new consumer of the gallery walk supplies a prologue (its per-row state) and on_tile(c0, acc), the epilogue of one super-tile.
+// A new consumer of the class-pair walk supplies what it does with a valid pair's dot product, inside the loops that section shows.
 #pragma once
 #include "common.h"
 
@@ -206,7 +211,90 @@ __device__ __forceinline__ void walk_gallery(float (*sA)[F32_LD], float (*sB)[F3
     }
 }
 
+// ---- the class-pair walk -------------------------------------------------------------------------------------------------------
+// Which row pairs of a pool sorted by class are evaluated, and in which population.  The grid is class_pair_groups' (host, below):
+// the first diag_groups workgroups of 256 threads walk the diagonal class pairs (i, i) with that stride and evaluate the strict
+// upper triangle (genuine pairs); the other off_groups walk the off-diagonal pairs (i, k), i > k, with theirs and evaluate the
+// whole rectangle (impostor pairs).  So `diag` is workgroup-uniform.  A class pair is covered with 64 x 64 super-tiles; wave w
+// multiplies its rows 16 w .. 16 w + 15 with four 16 x 16 column tiles, and a column tile without a pair is neither read nor live.
+//
+//     for (ClassPair p(C, diag_groups, off_groups); p.next(cls_start);)       all threads; the caller's per-pair state goes here
+//         for (PairTile t; t.next(p);) {                                      all threads
+//             t.dots(p, sA, sB, emb, E, vec);                                 all threads: it holds the barriers of the chunk loop
+//             for ct: if (t.live[ct]) for r: if (t.ok(p, ct, r)) ... t.acc[ct][r], t.ia(r), t.ib(ct) ...      wave-level
+//         }
+//
+// live[] is wave-uniform; ok() is per lane.  A consumer supplies what it does with a valid pair's dot product and nothing else.
+struct ClassPair {
+    bool diag;                               // this workgroup's population: genuine (strict upper triangle) or impostor
+    long b, npairs, stride;
+    int i, k, a0, na, b0, nb;                // classes i >= k: rows a0 .. a0 + na - 1 against rows b0 .. b0 + nb - 1
+    __device__ __forceinline__ ClassPair(int C, int diag_groups, int off_groups) {
+        diag = (int)blockIdx.x < diag_groups;
+        npairs = diag ? (long)C : (long)C * (C - 1) / 2;
+        stride = diag ? diag_groups : off_groups;
+        b = (diag ? (long)blockIdx.x : (long)blockIdx.x - diag_groups) - stride;
+    }
+    __device__ __forceinline__ bool next(const int* __restrict__ cls_start) {
+        while ((b += stride) < npairs) {
+            if (diag) {
+                i = k = (int)b;
+            } else {                         // b = j (j + 1) / 2 + k with k <= j, i = j + 1 > k
+                tri_decode(b, i, k);
+                i += 1;
+            }
+            a0 = cls_start[i], na = cls_start[i + 1] - a0;
+            b0 = cls_start[k], nb = cls_start[k + 1] - b0;
+            if (!(diag && na < 2)) return true;      // else: no pair at all
+        }
+        return false;
+    }
+};
+
+struct PairTile {
+    int ta = 0, tb = -F32_TILE, r0;          // the super-tile's first row and column within the classes; this wave's first row
+    bool live[4];
+    f32x4 acc[4];                            // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register
+    __device__ __forceinline__ bool next(const ClassPair& p) {     // row-major; a super-tile entirely on/below the diagonal is left out
+        do {
+            if ((tb += F32_TILE) >= p.nb) ta += F32_TILE, tb = 0;
+            if (ta >= p.na || p.nb < 1) return false;
+        } while (p.diag && tb + F32_TILE - 1 <= ta);
+        return true;
+    }
+    __device__ __forceinline__ void dots(const ClassPair& p, float (*sA)[F32_LD], float (*sB)[F32_LD], const float* __restrict__ emb, int E, bool vec) {
+        const int tid = threadIdx.x, wave = tid >> 6;
+        r0 = ta + wave * 16;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+            const int c0 = tb + ct * 16;
+            live[ct] = r0 < p.na && c0 < p.nb && !(p.diag && c0 + 15 <= r0);
+            acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        for (int e0 = 0; e0 < E; e0 += F32_CHUNK) {
+            __syncthreads();
+            stage_rows(sA, emb + (long)(p.a0 + ta) * E, p.na - ta, E, e0, vec, tid);
+            stage_rows(sB, emb + (long)(p.b0 + tb) * E, p.nb - tb, E, e0, vec, tid);
+            __syncthreads();
+            mfma_chunk(sA, sB, wave * 16, acc, live);
+        }
+    }
+    __device__ __forceinline__ int ia(int r) const { return r0 + ((threadIdx.x & 63) >> 4) * 4 + r; }
+    __device__ __forceinline__ int ib(int ct) const { return tb + ct * 16 + (threadIdx.x & 15); }
+    __device__ __forceinline__ bool ok(const ClassPair& p, int ct, int r) const {
+        return ia(r) < p.na && ib(ct) < p.nb && !(p.diag && ib(ct) <= ia(r));      // strict upper triangle (statistics.py:32-34)
+    }
+};
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
+// The grid of the class-pair walk: diag_groups + off_groups workgroups.  false: more classes than the walk takes.
+static inline bool class_pair_groups(int C, int* diag_groups, int* off_groups) {
+    const long off_pairs = (long)C * (C - 1) / 2;
+    *diag_groups = C < 256 ? C : 256;
+    *off_groups = (int)(off_pairs < 2048 ? off_pairs : 2048);
+    return C < 65536;
+}
+
 // Slab height (a multiple of 64) and count.  Chosen by the library: about 8192 workgroups in all (32 per CU: the tail of the
 // last round stays small), but never slabs of fewer than 512 rows, whose first super-tiles (the search's thresholds still open,
 // every value a survivor) would weigh too much; with many query tiles this is one slab.

@@ -91,9 +91,9 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
 //
 // Dot products run on v_mfma_f32_16x16x4_f32 (pair_tiles.h's staging and mfma_chunk), which is bit for bit the ascending-k fmaf
 // chain of confidence_kernel (a zero-padded k adds fma(0, 0, acc) = acc), so both kernels bin identical distances.
-// One workgroup walks class pairs with a stride (diagonal pairs and off-diagonal pairs in separate workgroups), covers each
-// pair with 64x64 super-tiles (wave w: rows 16w..16w+15 against four 16x16 column tiles, empty tiles skipped) and keeps the weighted fp64 tables in
-// LDS until it has seen all its pairs: the global fp64 atomics happen once per workgroup, not once per class pair.
+// Which pairs a workgroup evaluates is pair_tiles.h's class-pair walk (ClassPair, PairTile).  The kernel keeps the per-pair
+// histograms, and the weighted fp64 tables in LDS until the workgroup has seen all its pairs: the global fp64 atomics happen once
+// per workgroup, not once per class pair.
 constexpr int OMAXF = 16;       // folds
 
 __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __restrict__ emb, const int* __restrict__ cls_start,
@@ -111,70 +111,39 @@ __global__ __launch_bounds__(256) void confidence_folds_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int t = tid; t < T; t += 256) sThr[t] = thr[t];
     for (int t = tid; t < F * 2 * T; t += 256) sAcc[t] = 0.0;
-    const bool diag = (int)blockIdx.x < diag_groups;
-    const long npairs = diag ? (long)C : (long)C * (C - 1) / 2;
-    const long stride = diag ? diag_groups : off_groups;
     const bool vec = (E & 3) == 0;
-    const int lr = lane & 15, lg = lane >> 4;
     DotRange seen;
-    for (long b = diag ? (long)blockIdx.x : (long)blockIdx.x - diag_groups; b < npairs; b += stride) {
-        int i, k;
-        if (diag) {
-            i = k = (int)b;
-        } else {                                          // b = j (j + 1) / 2 + k with k <= j, i = j + 1 > k
-            tri_decode(b, i, k);
-            i += 1;
-        }
-        const int a0 = cls_start[i], na = cls_start[i + 1] - a0;
-        const int b0 = cls_start[k], nb = cls_start[k + 1] - b0;
-        if (diag && na < 2) continue;                     // no pair at all
+    ClassPair p(C, diag_groups, off_groups);
+    const bool diag = p.diag;
+    while (p.next(cls_start)) {
         __syncthreads();                                  // the previous pair's epilogue has read the histograms
         for (int t = tid; t < (F + 1) * HS; t += 256) sHist[t] = 0;
         if (tid < F) {                                    // statistics.py:91-101,126-127 for the training part of fold tid
-            const long ma = train_rows[(long)i * F + tid], mb = train_rows[(long)k * F + tid];
+            const long ma = train_rows[(long)p.i * F + tid], mb = train_rows[(long)p.k * F + tid];
             const long P = diag ? ma * (ma - 1) / 2 : ma * mb;
             const int Cf = train_classes[tid];
             sP[tid] = (double)P;
             sW[tid] = (double)P * (diag ? (double)Cf : (double)Cf * (Cf - 1) * 0.5);
         }
-        for (int ta = 0; ta < na; ta += F32_TILE)
-            for (int tb = 0; tb < nb; tb += F32_TILE) {
-                if (diag && tb + F32_TILE - 1 <= ta) continue;  // super-tile entirely on/below the diagonal
-                const int r0 = ta + wave * 16;            // this wave's 16 rows
-                bool live[4];
+        for (PairTile t; t.next(p);) {
+            t.dots(p, sA, sB, emb, E, vec);
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const int c0 = tb + ct * 16;
-                    live[ct] = r0 < na && c0 < nb && !(diag && c0 + 15 <= r0);
-                }
-                f32x4 acc[4];
+            for (int ct = 0; ct < 4; ++ct) {
+                if (!t.live[ct]) continue;
+                const int ib = t.ib(ct);
+                const int fb = ib < p.nb ? fold[p.b0 + ib] : 0;
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int e0 = 0; e0 < E; e0 += F32_CHUNK) {
-                    __syncthreads();
-                    stage_rows(sA, emb + (long)(a0 + ta) * E, na - ta, E, e0, vec, tid);
-                    stage_rows(sB, emb + (long)(b0 + tb) * E, nb - tb, E, e0, vec, tid);
-                    __syncthreads();
-                    mfma_chunk(sA, sB, wave * 16, acc, live);
-                }
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    if (!live[ct]) continue;
-                    const int ib = tb + ct * 16 + lr;     // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register
-                    const int fb = ib < nb ? fold[b0 + ib] : 0;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ia = r0 + lg * 4 + r;
-                        if (ia >= na || ib >= nb || (diag && ib <= ia)) continue;      // strict upper triangle (:32-34)
-                        const int fa = fold[a0 + ia];
-                        const float s = acc[ct][r];
-                        if (F >= 3 || fa == fb) seen.add(s);          // the pair is in at least one training part
-                        const int l = threshold_bin(sThr, T, pair_distance(s, metric));
-                        atomicAdd(&sHist[fa * HS + l], 1);
-                        atomicAdd(&sHist[(fa == fb ? F : fb) * HS + l], 1);
-                    }
+                for (int r = 0; r < 4; ++r) {
+                    if (!t.ok(p, ct, r)) continue;
+                    const int fa = fold[p.a0 + t.ia(r)];
+                    const float s = t.acc[ct][r];
+                    if (F >= 3 || fa == fb) seen.add(s);          // the pair is in at least one training part
+                    const int l = threshold_bin(sThr, T, pair_distance(s, metric));
+                    atomicAdd(&sHist[fa * HS + l], 1);
+                    atomicAdd(&sHist[(fa == fb ? F : fb) * HS + l], 1);
                 }
             }
+        }
         __syncthreads();
         for (int l = tid; l <= T; l += 256) {             // total = (sum of the touch rows + same) / 2
             int s = sHist[F * HS + l];
@@ -228,13 +197,11 @@ extern "C" int fn_confidence_counts_folds(const float* emb, const int32_t* cls_s
                    F >= 2 && F <= OMAXF,
                "confidence_counts_folds: bad arguments (T <= 256, 2 <= folds <= 16)");
     FN_REQUIRE(metric == 0 || metric == 1, "Undefined similarity metric %d", metric);   // statistics.py:258-260
-    FN_REQUIRE(C < 65536, "confidence_counts_folds: too many classes");
+    int diag_groups, off_groups;
+    FN_REQUIRE(class_pair_groups(C, &diag_groups, &off_groups), "confidence_counts_folds: too many classes");
     hipStream_t st = (hipStream_t)stream;
     fill_words(out, 0u, 0u, 2 * F * 4 * T, st);
     if (range) fill_words(range, 0x7f7fffffu, 0x80800000u, 2, st);
-    const long off_pairs = (long)C * (C - 1) / 2;
-    const int diag_groups = C < 256 ? C : 256;
-    const int off_groups = (int)(off_pairs < 2048 ? off_pairs : 2048);
     const size_t dyn = (size_t)((((F + 1) * (T + 1) * 4) + 15) & ~15) + (size_t)F * 2 * T * sizeof(double);
     if (dyn > 40 * 1024) {   // beyond the default 64 KiB per workgroup together with the static tiles
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(confidence_folds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);

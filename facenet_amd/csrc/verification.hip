@@ -4,11 +4,10 @@
 // radix selection over recomputed distances: the host narrows a key interval per target from the counts of one pass and asks for
 // the next, finer windows.  The [n, n] matrix is never written and nothing is sorted.
 //
-// The decomposition is confidence_folds_kernel's: a workgroup walks class pairs with a stride, diagonal pairs (genuine: the strict
-// upper triangle) and off-diagonal pairs (impostor) in separate workgroups, so a workgroup's population is uniform; each pair is
-// covered with 64x64 super-tiles, wave w rows 16w..16w+15 against four 16x16 column tiles.  Counters are uint32 in LDS, R x 1024 of
-// them (32 KB at most, one population), kept over all the workgroup's pairs and flushed with 64-bit integer atomics, non-zero bins
-// only; "below the window" and the total are counted in registers.
+// Which pairs a workgroup evaluates is pair_tiles.h's class-pair walk (ClassPair, PairTile), as in confidence_folds_kernel: a
+// workgroup's population is uniform, genuine or impostor.  Counters are uint32 in LDS, R x 1024 of them (32 KB at most, one
+// population), kept over all the workgroup's pairs and flushed with 64-bit integer atomics, non-zero bins only; "below the window"
+// and the total are counted in registers.
 #include "pair_tiles.h"
 #include "../../include/facenet_hip.h"
 
@@ -64,90 +63,56 @@ __global__ __launch_bounds__(256) void pair_key_histogram_kernel(const float* __
                                                                  int diag_groups, int off_groups) {
     extern __shared__ __align__(16) unsigned sCnt[];                                   // [R][KB]
     __shared__ __align__(16) float sA[F32_TILE][F32_LD], sB[F32_TILE][F32_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     for (int t = tid; t < R * KB; t += 256) sCnt[t] = 0;
-    const bool diag = (int)blockIdx.x < diag_groups;
-    const int pop = diag ? 0 : 1;
-    const long npairs = diag ? (long)C : (long)C * (C - 1) / 2;
-    const long stride = diag ? diag_groups : off_groups;
-    const int lr = lane & 15, lg = lane >> 4;
+    ClassPair p(C, diag_groups, off_groups);
+    const int pop = p.diag ? 0 : 1;
     unsigned below[KMAXR], total = 0;
 #pragma unroll
     for (int r = 0; r < KMAXR; ++r) below[r] = 0;
     unsigned long pending = 0;                            // an upper bound of what any counter holds: workgroup-uniform
     DotRange seen;
-    for (long b = diag ? (long)blockIdx.x : (long)blockIdx.x - diag_groups; b < npairs; b += stride) {
-        int i, k;
-        if (diag) {
-            i = k = (int)b;
-        } else {                                          // b = j (j + 1) / 2 + k with k <= j, i = j + 1 > k
-            tri_decode(b, i, k);
-            i += 1;
-        }
-        const int a0 = cls_start[i], na = cls_start[i + 1] - a0;
-        const int b0 = cls_start[k], nb = cls_start[k + 1] - b0;
-        if (diag && na < 2) continue;                     // no pair at all
-        for (int ta = 0; ta < na; ta += F32_TILE)
-            for (int tb = 0; tb < nb; tb += F32_TILE) {
-                if (diag && tb + F32_TILE - 1 <= ta) continue;  // super-tile entirely on/below the diagonal
-                // A uint32 counter could wrap.  No test reaches this (it takes 2^32 pairs in one workgroup); it is safe by reading:
-                // `pending` is workgroup-uniform and key_flush has a barrier on both sides.
-                if (pending + F32_TILE * F32_TILE > 0xffffffffUL) {
-                    key_flush(sCnt, below, total, R, pop, out);
-                    pending = 0;
-                }
-                pending += F32_TILE * F32_TILE;
-                const int r0 = ta + wave * 16;            // this wave's 16 rows
-                bool live[4];
+    while (p.next(cls_start))
+        for (PairTile t; t.next(p);) {
+            // A uint32 counter could wrap.  No test reaches this (it takes 2^32 pairs in one workgroup); it is safe by reading:
+            // `pending` is workgroup-uniform and key_flush has a barrier on both sides.
+            if (pending + F32_TILE * F32_TILE > 0xffffffffUL) {
+                key_flush(sCnt, below, total, R, pop, out);
+                pending = 0;
+            }
+            pending += F32_TILE * F32_TILE;
+            t.dots(p, sA, sB, emb, E, true);              // fn_pair_key_histogram requires E % 4 == 0
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const int c0 = tb + ct * 16;
-                    live[ct] = r0 < na && c0 < nb && !(diag && c0 + 15 <= r0);
-                }
-                f32x4 acc[4];
+            for (int ct = 0; ct < 4; ++ct) {
+                if (!t.live[ct]) continue;
+                unsigned key[4];
+                bool ok[4];
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int e0 = 0; e0 < E; e0 += F32_CHUNK) {
-                    __syncthreads();
-                    stage_rows(sA, emb + (long)(a0 + ta) * E, na - ta, E, e0, true, tid);
-                    stage_rows(sB, emb + (long)(b0 + tb) * E, nb - tb, E, e0, true, tid);
-                    __syncthreads();
-                    mfma_chunk(sA, sB, wave * 16, acc, live);
+                for (int r = 0; r < 4; ++r) {
+                    ok[r] = t.ok(p, ct, r);
+                    const float s = t.acc[ct][r];
+                    if (ok[r]) {
+                        seen.add(s);
+                        ++total;
+                    }
+                    key[r] = __float_as_uint(pair_distance(s, metric));
                 }
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    if (!live[ct]) continue;
-                    const int ib = tb + ct * 16 + lr;     // C/D layout: column = lane & 15, row = 4 (lane >> 4) + register
-                    unsigned key[4];
-                    bool ok[4];
+                for (int q = 0; q < KMAXR; ++q) {
+                    if (q >= R) break;
+                    unsigned bin[4];                      // >= KB: no bin of this window
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int ia = r0 + lg * 4 + r;
-                        ok[r] = ia < na && ib < nb && !(diag && ib <= ia);      // strict upper triangle
-                        const float s = acc[ct][r];
-                        if (ok[r]) {
-                            seen.add(s);
-                            ++total;
-                        }
-                        key[r] = __float_as_uint(pair_distance(s, metric));
+                        const bool under = key[r] < w.lo[q];
+                        bin[r] = (ok[r] && !under) ? (key[r] - w.lo[q]) >> w.shift[q] : 0xffffffffu;
+                        if (ok[r] && under) ++below[q];
                     }
 #pragma unroll
-                    for (int q = 0; q < KMAXR; ++q) {
-                        if (q >= R) break;
-                        unsigned bin[4];                  // >= KB: no bin of this window
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const bool under = key[r] < w.lo[q];
-                            bin[r] = (ok[r] && !under) ? (key[r] - w.lo[q]) >> w.shift[q] : 0xffffffffu;
-                            if (ok[r] && under) ++below[q];
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (bin[r] < KB) atomicAdd(&sCnt[q * KB + bin[r]], 1u);
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        if (bin[r] < KB) atomicAdd(&sCnt[q * KB + bin[r]], 1u);
                 }
             }
-    }
+        }
     key_flush(sCnt, below, total, R, pop, out);
     seen.publish(range, lane);
 }
@@ -162,7 +127,8 @@ extern "C" int fn_pair_key_histogram(const float* emb, const int32_t* cls_start,
     FN_REQUIRE(E >= 4 && E % 4 == 0 && E <= 512, "%s: the embedding length must be a multiple of 4 in [4, 512] (E %d)", what, E);
     FN_REQUIRE(metric == 0 || metric == 1, "Undefined similarity metric %d", metric);   // statistics.py:55
     FN_REQUIRE(emb && cls_start && lo && shift && out && C >= 1, "%s: bad arguments", what);
-    FN_REQUIRE(C < 65536, "%s: too many classes (C %d, at most 65535)", what, C);
+    int diag_groups, off_groups;
+    FN_REQUIRE(class_pair_groups(C, &diag_groups, &off_groups), "%s: too many classes (C %d, at most 65535)", what, C);
     FN_REQUIRE(((uintptr_t)emb | (uintptr_t)out) % 16 == 0, "%s: emb and out must be 16-byte aligned", what);
     KeyWindows w = {};
     for (int r = 0; r < R; ++r) {
@@ -172,9 +138,6 @@ extern "C" int fn_pair_key_histogram(const float* emb, const int32_t* cls_start,
     }
     hipStream_t st = (hipStream_t)stream;
     if (range) fill_words(range, 0x7f7fffffu, 0x80800000u, 2, st);
-    const long off_pairs = (long)C * (C - 1) / 2;
-    const int diag_groups = C < 256 ? C : 256;
-    const int off_groups = (int)(off_pairs < 2048 ? off_pairs : 2048);
     const size_t dyn = (size_t)R * KB * sizeof(unsigned);
     hipLaunchKernelGGL(pair_key_histogram_kernel, dim3((unsigned)(diag_groups + off_groups)), dim3(256), dyn, st, emb, cls_start, C, E, metric, w,
                        R, out, (int*)range, diag_groups, off_groups);

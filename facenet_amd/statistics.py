@@ -138,6 +138,14 @@ def _ratio_or_one(num, den):
     return np.divide(num, den, out=np.ones_like(den), where=den > 0)
 
 
+def _ascending_f32(thresholds):
+    """The thresholds as the count kernels take them: fp32 [T], ascending (their binning is a search over them)."""
+    thr = np.array(thresholds, ndmin=1).astype(np.float32)
+    if thr.size > 1 and not np.all(np.diff(thr) >= 0):
+        raise ValueError("thresholds must be ascending")
+    return thr
+
+
 class ConfidenceMatrix:
     """Interface of statistics.py:111-175 (attributes tp / tn / fp / fn / threshold, the six rate properties).  The
     class-balanced counts for ALL thresholds come from one fn_confidence_counts launch into ``counts`` [4, T]; every rate is
@@ -148,9 +156,7 @@ class ConfidenceMatrix:
     def __init__(self, calculator: SimilarityCalculator, threshold, atol: float = 1.e-5):
         lib = _lib.load()
         self.threshold = np.array(threshold, ndmin=1)
-        thr = self.threshold.astype(np.float32)
-        if thr.size > 1 and not np.all(np.diff(thr) >= 0):
-            raise ValueError("thresholds must be ascending")
+        thr = _ascending_f32(self.threshold)
         dev = calculator.emb.device
         t_dev = torch.as_tensor(thr, device=dev)
         out = torch.zeros(4 * thr.size, dtype=torch.float64, device=dev)
@@ -309,9 +315,7 @@ def confidence_counts_folds(calculator: SimilarityCalculator, fold_sorted, train
     """[F, 4, T] count tables (tp / tn / fp / fn) of the F training parts from ONE fn_confidence_counts_folds launch over the
     calculator's rows (sorted by class); raises the reference's ValueError when a pair of some training part leaves [-1, 1]."""
     lib = _lib.load()
-    thr = np.array(thresholds, ndmin=1).astype(np.float32)
-    if thr.size > 1 and not np.all(np.diff(thr) >= 0):
-        raise ValueError("thresholds must be ascending")
+    thr = _ascending_f32(thresholds)
     F = int(len(train_classes))
     n, E = calculator.emb.shape
     if np.shape(train_rows) != (calculator.nrof_classes, F) or np.shape(fold_sorted) != (n,):

@@ -10,6 +10,7 @@ Scaled by 1 + 2^-5 the dots become k / E0 (1 + 2^-4 + 2^-10): at most 18 signifi
 Random unit rows: with the same fp32 inputs upcast to fp64, |s32 - s64| <= gamma_E sum |a_i b_i| (Higham, Accuracy and Stability of
 Numerical Algorithms, 2nd ed., eq. 3.5), which turns into an interval for the fp32 distance; a (pair, threshold) whose fp32
 threshold lies in that interval is *ambiguous* and is the only thing a comparison with fp64 may excuse."""
+import functools
 from fractions import Fraction
 
 import numpy as np
@@ -53,6 +54,16 @@ def lattice_classes(sizes, seed, flips, E_pad=0, scale=1.0, E0=64):
     emb[:, :E0] = S.astype(np.float32) * amp
     starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     return emb, starts, (E0 - S @ S.T) // 2
+
+
+@functools.lru_cache(maxsize=None)
+def many_class_pool():
+    """-> (sizes, emb [825, 20], starts, H): 300 classes of sizes cycling 1, 2, 3, 5; the cycle shifts by one from class 256 on, so
+    that a diagonal workgroup of the class-pair walk (stride 256) meets a one-row class and then a populated one, or the reverse.
+    1 050 genuine and 338 850 impostor pairs; 44 850 off-diagonal class pairs over 2048 workgroups, 300 diagonal ones over 256.
+    Shared by its callers: not to be written to."""
+    sizes = [(1, 2, 3, 5)[(c + (c >= 256)) % 4] for c in range(300)]
+    return (sizes,) + lattice_classes(sizes, seed=12, flips=8, E_pad=4, E0=16)
 
 
 def exact_dots(H, E0=64, scale=1.0):

@@ -222,9 +222,8 @@ def many_classes():
     """300 classes of sizes cycling 1, 2, 3, 5; the cycle shifts by one from class 256 on, so that a diagonal workgroup (stride 256)
     meets a one-row class and then a populated one, or the reverse.  44 850 off-diagonal class pairs over 2048 workgroups.  Folds by
     hand: a one-row class has no training row in its fold; every 8th class is held out whole in one fold."""
-    C, F = 300, 4
-    sizes = [(1, 2, 3, 5)[(c + (c >= 256)) % 4] for c in range(C)]
-    emb, starts, H = pl.lattice_classes(sizes, seed=12, flips=8, E_pad=4, E0=16)
+    F = 4
+    sizes, emb, starts, H = pl.many_class_pool()
     cls = pl._class_of(starts)
     fold = (cls + np.arange(len(cls)) - starts[cls]) % F                            # class c, position p: fold (c + p) % 4
     whole = cls % 8 == 5

@@ -126,6 +126,19 @@ def test_histogram_words_lattice_rows():
     assert int(top[B + 1]) - int(top[B]) - int(top[:B].sum()) == np.count_nonzero(gen == vo.f32_key(4.0)) > 0
 
 
+def test_histogram_words_many_class_pairs_per_workgroup():
+    """300 classes: every workgroup of the class-pair walk takes several class pairs (44 850 off-diagonal ones over 2048
+    workgroups, 300 diagonal ones over 256), so its counters and its below / total registers carry over from pair to pair."""
+    _, emb, starts, H = pl.many_class_pool()
+    gen, imp = vo.lattice_keys(H, starts, 16)
+    assert (len(starts) - 1, len(gen), len(imp)) == (300, 1050, 338850)
+    for lo, shift in (([0], [21]), mixed_windows(gen, imp), st.FIRST_WINDOWS):
+        got, rng = run_hist(emb, starts, 0, lo, shift)
+        assert_same_words(got, vo.histogram(gen, imp, lo, shift))
+        assert rng == pl.want_range(pl.exact_dots(H, 16), starts)
+        assert (int(got[0, 0, B + 1]), int(got[0, 1, B + 1])) == (1050, 338850)
+
+
 def test_single_class_and_single_rows():
     emb, starts, H = pl.lattice_classes([70], seed=13, flips=32)
     got, _ = run_hist(emb, starts, 0, [0], [21])
