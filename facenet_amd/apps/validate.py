@@ -24,7 +24,8 @@ DEFAULTS = {   # apps/configs/validate.yaml of the reference
                 "max_nrof_images": None},
     "model": {"path": None},
     # validate.far_targets (not set here: absent means None): a list of false-accept rates; the exact VerificationCurve at these
-    # rates is appended to the report
+    # rates is appended to the report.  validate.fpir_targets (likewise absent): a list of false-positive
+    # identification rates, and validate.fpir_rank (default 1); the open-set IdentificationCurve at these rates follows (section 24)
     "validate": {"nrof_folds": 10, "metric": 0, "far_target": 0.001},
     "file": None,
 }
@@ -54,12 +55,13 @@ def load_options(path=None, overrides: dict = None) -> Config:
 
 def validate(options, log=print):
     """Returns the FaceToFaceValidation; ``options`` as ``load_options`` builds them.  ``report.curve`` is the VerificationCurve
-    that ``validate.far_targets`` asks for, None without the key."""
+    that ``validate.far_targets`` asks for and ``report.identification`` the IdentificationCurve that ``validate.fpir_targets`` asks
+    for, each None without its key."""
     from facenet_amd import dataset
     from facenet_amd.api import FaceNet
     from facenet_amd.apps.train_classifier import write_text_log
     from facenet_amd.facenet import evaluate_embeddings
-    from facenet_amd.statistics import FaceToFaceValidation, verification_curve
+    from facenet_amd.statistics import FaceToFaceValidation, identification_curve, verification_curve
 
     start = time.monotonic()
     options.file.parent.mkdir(parents=True, exist_ok=True)
@@ -84,6 +86,10 @@ def validate(options, log=print):
     if report.curve is not None:
         write_text_log(options.file, report.curve)
         log(report.curve)
+    report.identification = identification_curve(embeddings, labels, options.validate)
+    if report.identification is not None:
+        write_text_log(options.file, report.identification)
+        log(report.identification)
 
     with options.file.open("at") as f:
         f.write("elapsed time: {:.3f}\n".format(time.monotonic() - start))

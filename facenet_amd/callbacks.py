@@ -63,7 +63,8 @@ class ValidateCallback:
     ``model``: callable from uint8 images to unit-norm embeddings (``None``: the training app attaches its trainer);
     ``dataset``: an iterable of (images, labels) that can be walked repeatedly; ``config.validate``: metric, nrof_folds,
     far_target, and far_targets (optional: the exact VerificationCurve at these rates follows the report and is set on it as
-    ``report.curve``; without the key the report object is left as the statistic made it).
+    ``report.curve``; fpir_targets / fpir_rank, optional: the open-set IdentificationCurve follows likewise as
+    ``report.identification``; without a key the report object is left as the statistic made it).
     ``history`` collects (epoch, FaceToFaceValidation.dict, seconds embedding, seconds statistics).
 
     Data parallel: every rank embeds the batches ``rank::world``, the embeddings are all-gathered in data-set order, rank 0
@@ -156,12 +157,18 @@ class ValidateCallback:
         curve = verification_curve(embeddings, labels, self.config.validate)        # None unless validate.far_targets is set
         if curve is not None:
             report.curve = curve
+        from .statistics import identification_curve
+        identification = identification_curve(embeddings, labels, self.config.validate)      # None unless validate.fpir_targets is set
+        if identification is not None:
+            report.identification = identification
         t2 = time.perf_counter()
         self.embeddings, self.labels = embeddings, labels
         self.history.append((epoch1, report.dict, t1 - t0, t2 - t1))
         self.log(str(report))
         if curve is not None:
             self.log(str(curve))
+        if identification is not None:
+            self.log(str(identification))
         self.log(f"validation: embedding {t1 - t0:.3f} s, statistics {t2 - t1:.3f} s")
         path = getattr(self._model, "path", None)
         if path:
@@ -171,6 +178,9 @@ class ValidateCallback:
             if curve is not None:
                 from .apps.train_classifier import write_text_log
                 write_text_log(path / "report.txt", curve)
+            if identification is not None:
+                from .apps.train_classifier import write_text_log
+                write_text_log(path / "report.txt", identification)
         return report
 
     def on_epoch_end(self, epoch, logs=None):

@@ -17,11 +17,16 @@ with a threshold (a number, or a trained FaceToFaceNormalizedEmbeddingsClassifie
 ``Gallery.within`` is the range query: every gallery row nearer than eps as a CSR, from fn_radius_count /
 fn_radius_fill, with the same distances and the same strict fp32 < as validation and identification.  ``Gallery.cluster`` runs
 DBSCAN on the self-join (fn_dbscan_*) and returns a `Clustering`; ``FacePipeline.cluster`` does so for the faces of a list of
-photographs without their embeddings leaving the device."""
+photographs without their embeddings leaving the device.
+
+``Gallery.mates`` is the search of the open-set evaluation: every probe's nearest mate, nearest impostor and
+the rank of that mate at any depth, from fn_mate_search on the same walk and the same bits; ``statistics.IdentificationCurve``
+turns them into FNIR at FPIR."""
 from __future__ import annotations
 
 import ctypes
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -168,6 +173,17 @@ class Clustering:
                 f"Number of noise images {self.nrof_noise}\n" + f"eps: {self.eps} min_samples: {self.min_samples}\n")
 
 
+class MateSearch(NamedTuple):
+    """What `Gallery.mates` returns, one entry per query row: the nearest mate's distance (float32) and gallery row (int32), the
+    nearest impostor's, and ``ranks`` int32 (None when not asked for): the impostor rows nearer than the nearest mate.  Row -1,
+    distance +inf and rank -1 where there is no such row."""
+    mate_dist: object
+    mate_rows: object
+    impostor_dist: object
+    impostor_rows: object
+    ranks: object
+
+
 def _class_names(labels, files):
     """label -> the name of the directory that holds one of its files (the class directories of dataset.Database)."""
     names = {}
@@ -210,6 +226,7 @@ class Gallery:
         self.names = names
         self.files = None if files is None else np.asarray(files, dtype=str)
         self.embeddings = _as_table(embeddings, self.device)
+        self._codes = None         # `_label_codes`
 
     @classmethod
     def from_file(cls, path, metric=0, device="cuda"):
@@ -304,6 +321,69 @@ class Gallery:
     def leave_one_out(self, k=1):
         """Every gallery row's k nearest OTHER rows, device tensors: ``search(gallery, k, skip=arange(G))``."""
         return self.search(self.embeddings, k, skip=np.arange(self.nrof_images, dtype=np.int32))
+
+    def _label_codes(self):
+        """(the gallery's sorted unique labels int64 [C], device int32 [G] dense codes 0 .. C - 1), built once: fn_mate_search
+        compares int32 codes, whatever non-negative int64 the labels are."""
+        if self._codes is None:
+            uniq, inverse = np.unique(self.labels, return_inverse=True)
+            codes = torch.from_numpy(inverse.reshape(-1).astype(np.int32))
+            self._codes = (uniq, codes.to(self.device) if self.device.type == "cuda" else codes)
+        return self._codes
+
+    def query_codes(self, labels, Q):
+        """Query labels -> int32 [Q] codes of the gallery's table: -1 for -1 and for a label the gallery does not hold."""
+        labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+        if labels.shape != (Q,) or (Q and labels.dtype.kind not in "iu"):        # (an empty list has no integer type)
+            raise ValueError(f"labels must be {Q} integers (the probe's identity, or -1), got shape {labels.shape} of {labels.dtype}")
+        labels = labels.astype(np.int64)
+        if Q and labels.min() < -1:
+            raise ValueError("a query label must not be below -1: -1 is a probe known to be absent from the gallery")
+        uniq = self._label_codes()[0]
+        at = np.minimum(np.searchsorted(uniq, labels), len(uniq) - 1)
+        return np.where(uniq[at] == labels, at, -1).astype(np.int32)
+
+    def _mates(self, queries, labels, skip, ranks, slab_rows, atol):
+        """-> device (dist float32 [Q, 2], rows int32 [Q, 2], ranks int32 [Q] or None) after every check of `mates`."""
+        shape = tuple(queries.shape) if hasattr(queries, "shape") else np.shape(queries)
+        if len(shape) == 2 and shape[1] == self.length:        # (else `_queries` raises)
+            codes = self.query_codes(labels, shape[0])         # before anything needs a device
+        Q, q, skip_dev = self._queries(queries, skip, "Gallery.mates runs fn_mate_search")
+        dev, G = self.device, self.nrof_images
+        dist = torch.empty((Q, 2), dtype=torch.float32, device=dev)
+        rows = torch.empty((Q, 2), dtype=torch.int32, device=dev)
+        rank = torch.empty(Q, dtype=torch.int32, device=dev) if ranks else None
+        if Q == 0:
+            return dist, rows, rank
+        lib = _lib.load()
+        ws = self._workspace(lib.fn_mate_search_workspace, "mate_search_workspace", Q, G, int(slab_rows))
+        rng = None if atol is None else torch.zeros(2, dtype=torch.int32, device=dev)
+        qcodes = torch.from_numpy(codes).to(dev)
+        _lib.check(lib.fn_mate_search(_ptr(q), Q, _ptr(qcodes), _ptr(self.embeddings), G, _ptr(self._label_codes()[1]), self.length, self.metric,
+                                      _ptr(skip_dev), int(slab_rows), _ptr(ws), _ptr(dist), _ptr(rows), _ptr(rank), _ptr(rng), _stream(dev)),
+                   "mate_search")
+        if rng is not None:
+            check_unit_range(rng, atol)         # waits for the search
+        return dist, rows, rank
+
+    def mates(self, queries, labels, skip=None, ranks=True, slab_rows=0, atol=1.e-5):
+        """The open-set evaluation search: for every query row its nearest MATE (the nearest gallery row
+        that carries the query's label) and its nearest IMPOSTOR (the nearest row of any other label) -> `MateSearch`; NumPy in
+        gives NumPy out, a device tensor in gives device tensors out.  ``labels`` [Q]: the probes' identities in the gallery's
+        own labels; -1, or a label the gallery does not hold, is a probe without a mate: every row is its impostor.  ``ranks``:
+        also the number of impostor rows nearer than the nearest mate (-1 without a mate), the 0-based rank of the first mate in
+        the full ordering, at any depth; it costs a second walk of the gallery.  Where there is no such row: row -1, distance
+        +inf.  Equal distances go to the lower row; the distances are `search`'s bit for bit.  ``skip``, ``slab_rows``,
+        ``atol``: as `search`."""
+        dist, rows, rank = self._mates(queries, labels, skip, ranks, slab_rows, atol)
+        out = (dist[:, 0], rows[:, 0], dist[:, 1], rows[:, 1], rank)
+        if not torch.is_tensor(queries):
+            out = tuple(None if t is None else t.cpu().numpy() for t in out)
+        return MateSearch(*out)
+
+    def leave_one_out_mates(self, ranks=True):
+        """Every gallery row as a probe against all OTHER rows, device tensors: ``mates(gallery, labels, skip=arange(G))``."""
+        return self.mates(self.embeddings, self.labels, skip=np.arange(self.nrof_images, dtype=np.int32), ranks=ranks)
 
     def threshold_of(self, threshold=None, classifier=None):
         """The fp32 threshold of `identify`: the number given, a classifier's trained one, or None (closed set)."""

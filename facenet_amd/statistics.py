@@ -697,3 +697,158 @@ def verification_curve(embeddings, labels, config, device: str = "cuda"):
     curve.tar_at_far(sorted(float(f) for f in np.atleast_1d(fars)))
     curve.eer()
     return curve
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Open-set 1:N identification: FNIR at FPIR, the detection-and-identification rate and the CMC at any
+# rank, from each probe's nearest mate, nearest impostor and rank (Gallery.mates / fn_mate_search).  The 1:N sibling of
+# VerificationCurve: integers are exact, ratios are formed from them.
+# ------------------------------------------------------------------------------------------------------------------
+class IdentificationCurve:
+    """The leave-one-out open-set identification curve of a set of embeddings (ISO/IEC 19795-1, the FNIR at FPIR of 1:N
+    evaluations).  Every row is a probe against all other rows.  MATED searches: the probes whose class has another image
+    (``nrof_mated`` = M); such a probe is a hit at (threshold t, rank R) when fewer than R impostor rows are nearer than its
+    nearest mate and that mate's distance d < t (strict fp32, as `Gallery.identify` decides).  NON-MATED searches: the same
+    probe against the gallery without its whole identity, whose top candidate is exactly the nearest impostor
+    (``nrof_nonmated`` = N probes that have one: all of them with two or more classes); it is a false positive when that
+    distance d < t.  Distances are `Gallery.search`'s bit for bit."""
+
+    def __init__(self, embeddings, labels, metric=0, device: str = "cuda", atol: float = 1.e-5):
+        if metric not in KEY_TOP:
+            raise ValueError('Undefined similarity metric {}'.format(metric))
+        labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+        _, inverse, sizes = np.unique(labels, return_inverse=True, return_counts=True)
+        n = len(labels)
+        self._check(int(np.count_nonzero(sizes[inverse.reshape(-1)] > 1)) if n else 0, n if len(sizes) > 1 else 0)      # no launch
+        from .recognize import Gallery
+        gallery = Gallery(embeddings, labels=inverse.reshape(-1).astype(np.int64), metric=metric, device=device)
+        found = gallery.mates(gallery.embeddings, gallery.labels, skip=np.arange(n, dtype=np.int32), ranks=True, atol=atol)
+        self._init(*(t.cpu().numpy() for t in found), metric)
+
+    @classmethod
+    def from_search(cls, mate_dist, impostor_dist, ranks, metric=0, impostor_rows=None):
+        """The curve over host arrays, one entry per probe: what `Gallery.mates` returned for a real probe set, or the tests'
+        NumPy stand-in.  A probe is mated when ranks >= 0 and non-mated scored when its impostor distance is finite."""
+        self = cls.__new__(cls)
+        if metric not in KEY_TOP:
+            raise ValueError('Undefined similarity metric {}'.format(metric))
+        mate_dist, impostor_dist, ranks = np.asarray(mate_dist), np.asarray(impostor_dist), np.asarray(ranks)
+        if not (mate_dist.ndim == 1 and mate_dist.shape == impostor_dist.shape == ranks.shape) or ranks.dtype.kind not in "iu":
+            raise ValueError("from_search: mate_dist, impostor_dist and integer ranks must be 1-D and of equal length, got {}, {} and {} of {}"
+                             .format(mate_dist.shape, impostor_dist.shape, ranks.shape, ranks.dtype))
+        if impostor_rows is None:
+            impostor_rows = np.full(ranks.shape, -1, np.int32)
+        self._check(int(np.count_nonzero(ranks >= 0)), int(np.count_nonzero(np.isfinite(impostor_dist.astype(np.float32)))))
+        self._init(mate_dist, np.full(ranks.shape, -1, np.int32), impostor_dist, impostor_rows, ranks, metric)
+        return self
+
+    @staticmethod
+    def _check(mated, nonmated):
+        if mated < 1 or nonmated < 1:
+            raise ValueError("an identification curve needs mated and non-mated searches, got {} and {}".format(mated, nonmated))
+
+    def _init(self, mate_dist, mate_rows, impostor_dist, impostor_rows, ranks, metric):
+        self.metric = metric
+        self.mate_dist, self.impostor_dist = np.asarray(mate_dist, dtype=np.float32), np.asarray(impostor_dist, dtype=np.float32)
+        self.mate_rows, self.impostor_rows = np.asarray(mate_rows), np.asarray(impostor_rows)
+        self.ranks = np.asarray(ranks).astype(np.int64)
+        self.nrof_probes = len(self.ranks)
+        self.nrof_mated = int(np.count_nonzero(self.ranks >= 0))
+        self._sorted = np.sort(self.impostor_dist[np.isfinite(self.impostor_dist)])          # the non-mated scores, ascending
+        self.nrof_nonmated = len(self._sorted)
+        self._asked = {}
+
+    @staticmethod
+    def _rank(rank):
+        if isinstance(rank, bool) or not isinstance(rank, (int, np.integer)) or rank < 1:
+            raise ValueError("rank must be an integer of at least 1, got {!r}".format(rank))
+        return int(rank)
+
+    def _counts(self, threshold, rank):
+        t = np.float32(threshold)
+        false_positives = int(np.searchsorted(self._sorted, t, side="left"))                  # #{d < t}
+        hits = int(np.count_nonzero((self.ranks >= 0) & (self.ranks < rank) & (self.mate_dist < t)))
+        M, N = self.nrof_mated, self.nrof_nonmated
+        return {"threshold": float(t), "rank": rank, "false_positives": false_positives, "hits": hits, "fpir": false_positives / N,
+                "dir": hits / M, "fnir": 1 - hits / M}
+
+    def fnir_at_fpir(self, fpirs, rank=1):
+        """One record per false-positive identification rate f, ascending in [0, 1]: m = int(f * N) in exact arithmetic,
+        ``threshold`` the (m + 1)-th smallest nearest-impostor distance (the largest fp32 t with at most m false positives; +inf
+        when m reaches N), ``false_positives`` the non-mated searches with d < threshold (ties may leave it below m), ``hits``
+        the mated searches with the mate within ``rank`` and nearer than the threshold; ``fpir``, ``dir`` (the detection and
+        identification rate) and ``fnir`` = 1 - dir their shares."""
+        from fractions import Fraction
+        rank = self._rank(rank)
+        fpirs = [float(f) for f in np.atleast_1d(np.asarray(fpirs, dtype=np.float64))]
+        if any(not 0.0 <= f <= 1.0 for f in fpirs):
+            raise ValueError("false-positive identification rates must lie in [0, 1], got {}".format(fpirs))
+        if any(b < a for a, b in zip(fpirs, fpirs[1:])):
+            raise ValueError("false-positive identification rates must be ascending, got {}".format(fpirs))
+        records = []
+        for f in fpirs:
+            m = int(Fraction(f) * self.nrof_nonmated)
+            t = self._sorted[m] if m < self.nrof_nonmated else np.float32(np.inf)
+            record = {"fpir_target": f}
+            record.update(self._counts(t, rank))
+            self._asked[(f, rank)] = record
+            records.append(dict(record))
+        return records
+
+    def dir_at(self, threshold, rank=1):
+        """The counts of `fnir_at_fpir` at a threshold of the caller's: a classifier's, or `VerificationCurve.threshold_at_far`."""
+        rank = self._rank(rank)
+        if np.isnan(np.float32(threshold)):
+            raise ValueError("threshold must be a number, got NaN")
+        return self._counts(threshold, rank)
+
+    def cmc(self, k):
+        """-> (curve float64 [k], left_out): curve[r] is the share of mated probes whose first mate has rank <= r, at any depth;
+        for k <= 64 it is `statistics.cmc` of the leave-one-out search."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("k must be an integer of at least 1, got {!r}".format(k))
+        mated = self.ranks[self.ranks >= 0]
+        found = np.cumsum(np.bincount(np.minimum(mated, k), minlength=k + 1)[:k])
+        return found / np.float64(self.nrof_mated), self.nrof_probes - self.nrof_mated
+
+    def mislabelled(self):
+        """The probes whose nearest impostor precedes their nearest mate, as (row, impostor row, mate distance, impostor
+        distance), nearest impostor first: the label-noise shortlist of a data set."""
+        bad = np.nonzero(self.ranks > 0)[0]
+        bad = bad[np.lexsort((bad, self.impostor_dist[bad]))]
+        return [(int(i), int(self.impostor_rows[i]), float(self.mate_dist[i]), float(self.impostor_dist[i])) for i in bad]
+
+    def dict(self):
+        curve, left_out = self.cmc(1)
+        return {"metric": self.metric, "nrof_probes": self.nrof_probes, "nrof_mated": self.nrof_mated, "nrof_nonmated": self.nrof_nonmated,
+                "left_out": left_out, "rank1": float(curve[0]), "nrof_mislabelled": int(np.count_nonzero(self.ranks > 0)),
+                "fnir_at_fpir": [dict(self._asked[key]) for key in sorted(self._asked)]}
+
+    def __repr__(self):
+        d = self.dict()
+        text = ('{}\nmetric: {}\n\nmated searches: {}\nnon-mated searches: {}\nRank-1 identification rate (closed set): {:1.5f}\n'
+                'Probes nearer to an impostor than to a mate: {}\n\n').format(self.__class__.__name__, d["metric"], d["nrof_mated"],
+                                                                             d["nrof_nonmated"], d["rank1"], d["nrof_mislabelled"])
+        for r in d["fnir_at_fpir"]:
+            text += ('FNIR @ FPIR = {} (rank {})\nFalse negative identification rate (FNIR): {:1.5f} ({} of {} missed)\n'
+                     'False positive identification rate (FPIR): {:.3e} ({} of {})\nThreshold: {:2.5f}\n\n').format(
+                         r["fpir_target"], r["rank"], r["fnir"], d["nrof_mated"] - r["hits"], d["nrof_mated"], r["fpir"],
+                         r["false_positives"], d["nrof_nonmated"], r["threshold"])
+        return text
+
+
+def identification_curve(embeddings, labels, config, device: str = "cuda"):
+    """The curve ``config.fpir_targets`` asks for (a list of false-positive identification rates; ``config.fpir_rank``, default 1),
+    evaluated; None when the key is unset: the one helper of apps/validate.py and ValidateCallback."""
+    from .config import Config
+    fpirs = getattr(config, "fpir_targets", None)
+    if fpirs is None or isinstance(fpirs, Config):        # a Config reads a missing key as an empty Config
+        return None
+    rank = getattr(config, "fpir_rank", None)
+    rank = 1 if rank is None or isinstance(rank, Config) else IdentificationCurve._rank(rank)
+    fpirs = sorted(float(f) for f in np.atleast_1d(fpirs))
+    if any(not 0.0 <= f <= 1.0 for f in fpirs):           # before any launch
+        raise ValueError("false-positive identification rates must lie in [0, 1], got {}".format(fpirs))
+    curve = IdentificationCurve(embeddings, labels, metric=config.metric, device=device)
+    curve.fnir_at_fpir(fpirs, rank=rank)
+    return curve

@@ -394,6 +394,25 @@ int fn_gallery_search(const float* queries, int Q, const float* gallery, int G, 
                       const int32_t* labels, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* row_labels,
                       float* range, void* stream);
 
+/* ---- open-set 1:N evaluation: per probe its nearest mate, its nearest impostor and the rank of that mate;
+ * the [Q, G] matrix never reaches memory.  s, sc, d0 = 2 (1 - sc) and the key bits(d0) << 32 | row are those of fn_gallery_search,
+ * fn_radius_*, fn_confidence_counts* and fn_pair_key_histogram bit for bit.  queries, gallery, E, metric, skip, slab_rows and the
+ * alignment rule: as fn_gallery_search.  query_labels int32 [Q] (>= -1) and gallery_labels int32 [G] (>= 0) must be given; the
+ * caller guarantees their ranges.  Gallery row g is admissible for query q when g != skip[q]; an admissible row is a mate when
+ * gallery_labels[g] == query_labels[q] and an impostor otherwise; a query label of -1 is a probe known to be absent: every row is
+ * its impostor.  rows int32 [Q, 2]: the mate / the impostor with the smallest key (equal distances go to the lower row); dist fp32
+ * [Q, 2]: that row's distance in the gallery's metric (2 (1 - sc) for metric 0, acosf(sc) for metric 1); row -1 and dist +inf
+ * where there is no such row.  rank int32 [Q] or NULL: the number of admissible impostor rows whose key is smaller than the
+ * nearest mate's, i.e. the 0-based rank of the first mate in the full ordering, -1 without a mate; it costs a second walk of the
+ * gallery, which NULL leaves out.  range (2 words or NULL): ordered-int min/max of s over all Q x G pairs, skipped pairs
+ * included.  workspace: at least the bytes fn_mate_search_workspace reports for the same Q, G and slab_rows.  The result depends
+ * neither on slab_rows nor on scheduling.  There is no small-Q mode: this is an evaluation over many probes.  The caller owns
+ * every buffer; the call allocates nothing and does not synchronise. */
+int fn_mate_search_workspace(int Q, int G, int slab_rows, long long* bytes);
+int fn_mate_search(const float* queries, int Q, const int32_t* query_labels, const float* gallery, int G,
+                   const int32_t* gallery_labels, int E, int metric, const int32_t* skip, int slab_rows, void* workspace,
+                   float* dist, int32_t* rows, int32_t* rank, int32_t* range, void* stream);
+
 /* ---- face clustering ------------------------------------------------------------------------------------
  * Radius search: every (query, gallery row) pair with d < eps as a CSR; the [Q, G] matrix never reaches memory.  s, sc and d
  * (2 (1 - sc) for metric 0, acosf(sc) for metric 1) are those of fn_gallery_search and fn_confidence_counts bit for bit, and the
