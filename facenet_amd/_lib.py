@@ -141,6 +141,9 @@ _SIGNATURES = {
     "fn_pair_key_histogram": [_p, _p, _i, _i, _i, C.POINTER(_u), C.POINTER(C.c_int32), _i, _p, _p, _p],
     "fn_gallery_search_workspace": [_i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_gallery_search": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    "fn_kmeans_update": [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p],
+    "fn_ivf_search_workspace": [_i, _i, _i, _i, _i, C.POINTER(C.c_longlong)],
+    "fn_ivf_search": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "fn_mate_search_workspace": [_i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_mate_search": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p],
     "fn_radius_workspace": [_i, _i, _i, C.POINTER(C.c_longlong)],

@@ -5,7 +5,9 @@ DESIGN.md section 19): ``python -m facenet_amd.apps.identify --config x.yaml``.
 Keys: those of apps/photo_embeddings.py (dataset.path, model.*, image.size, image.margin, image.align, detector, mtcnn.weights_file, file)
 and gallery.path (required: the .npz of apps/embeddings.py with the known faces), gallery.metric (0 or 1), identify.k (neighbours
 kept per face, 1..64) and at most one of identify.threshold (a number) and identify.classifier (an .npz written by a
-FaceToFaceNormalizedEmbeddingsClassifier's ``save``); with neither every face gets its nearest gallery row's label.  Every image
+FaceToFaceNormalizedEmbeddingsClassifier's ``save``); with neither every face gets its nearest gallery row's label.
+identify.nlist (``--nlist``; unset: off) searches through an inverted-file index of that many k-means lists (at most one per
+gallery row), built once from the gallery (Gallery.ivf), of which every face probes identify.nprobe (``--nprobe``, default 8).  Every image
 of the data set is read and its faces go to ``file``, one .npz with a row per face: ``files``, ``face``, ``boxes`` int64 [N, 4],
 ``confidence`` float64 [N] as photo_embeddings writes them, ``labels`` int64 [N] (-1: nobody nearer than the threshold),
 ``names`` [N] ('' for -1 or a gallery without names), ``distances`` float32 [N, k] and ``rows`` int32 [N, k] (gallery rows by
@@ -22,7 +24,7 @@ from facenet_amd.apps import photo_embeddings
 from facenet_amd.config import Config, _merge
 
 DEFAULTS = dict(photo_embeddings.DEFAULTS, gallery={"path": None, "metric": 0},
-                identify={"threshold": None, "classifier": None, "k": 1})
+                identify={"threshold": None, "classifier": None, "k": 1, "nlist": None, "nprobe": None})
 
 
 def load_options(path=None, overrides: dict = None) -> Config:
@@ -48,6 +50,12 @@ def load_options(path=None, overrides: dict = None) -> Config:
         c.identify.classifier = Path(c.identify.classifier).expanduser()
     if not isinstance(c.identify.k, int) or not 1 <= c.identify.k <= 64:
         raise ValueError(f"identify.k must be an integer in [1, 64], got {c.identify.k!r}")
+    for key in ("nlist", "nprobe"):
+        value = getattr(c.identify, key)
+        if value is not None and (isinstance(value, bool) or not isinstance(value, int) or value < 1):
+            raise ValueError(f"identify.{key} must be an integer of at least 1, got {value!r}")
+    if c.identify.nprobe is not None and c.identify.nlist is None:
+        raise ValueError("identify.nprobe needs identify.nlist")
     if c.file:
         c.file = Path(c.file).expanduser()
     else:
@@ -66,7 +74,12 @@ def load_gallery(options):
     classifier = None
     if options.identify.classifier is not None:
         classifier = FaceToFaceNormalizedEmbeddingsClassifier().load(options.identify.classifier)
-    return gallery, gallery.threshold_of(options.identify.threshold, classifier)
+    threshold = gallery.threshold_of(options.identify.threshold, classifier)
+    if options.identify.nlist is not None:
+        gallery = gallery.ivf(min(options.identify.nlist, gallery.nrof_images))
+        if options.identify.nprobe is not None:
+            gallery.nprobe = options.identify.nprobe
+    return gallery, threshold
 
 
 def write_identified(options, pipeline=None, gallery=None, threshold=None, log=print):
@@ -117,8 +130,11 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
 
 @click.command()
 @click.option("--config", default=None, type=Path, help="Path to yaml config file with used options for the application.")
+@click.option("--nlist", default=None, type=int, help="Search through an inverted-file index of this many lists (identify.nlist).")
+@click.option("--nprobe", default=None, type=int, help="Lists every face probes (identify.nprobe); needs --nlist or identify.nlist.")
 def main(**options):
-    write_identified(load_options(options["config"]))
+    given = {key: options[key] for key in ("nlist", "nprobe") if options[key] is not None}
+    write_identified(load_options(options["config"], {"identify": given} if given else None))
 
 
 if __name__ == "__main__":

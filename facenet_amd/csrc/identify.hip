@@ -14,44 +14,11 @@
 // candidates) and appends the survivors to the row's list; a list that cannot take another column tile is cut to its k
 // smallest by the wave that owns the row.  Rows belong to one wave: selection needs no workgroup barrier.
 // gallery_merge_kernel: one wave per query cuts the slabs' k-lists to the final k and writes distances, rows and labels.
-#include "pair_tiles.h"
+// The key, the lists and the cuts are topk_select.h's, shared with the probed-list search of ivf.hip.
+#include "topk_select.h"
 #include "../../include/facenet_hip.h"
 
 namespace fn {
-
-constexpr int IMAXK = 64;
-constexpr int IMERGE_CAP = 128;      // merge list: up to 64 kept + 64 new keys
-constexpr unsigned long long INONE = ~0ull;
-
-typedef unsigned long long u64;
-
-// list capacity of a row for a given k: the k kept keys and one column tile (16) of survivors, in steps of 16
-__host__ __device__ __forceinline__ int id_cap(int k) { return ((k + 15) / 16) * 16 + 16; }
-
-// Cut a list of n <= 128 unique keys (LDS, owned by the calling wave) to its min(n, k) smallest, ascending, by counting ranks;
-// when n >= k the k-th smallest becomes the row's threshold.  Returns the new length.  Single wave: LDS operations of one wave
-// execute in program order, so the reads of the rank loop precede the writes below for every lane.
-__device__ __forceinline__ int id_prune(u64* __restrict__ list, int n, int k, u64* __restrict__ thr, int lane) {
-    const u64 a = lane < n ? list[lane] : INONE;
-    const u64 b = lane + 64 < n ? list[lane + 64] : INONE;
-    int ra = 0, rb = 0;
-    for (int j = 0; j < n; ++j) {
-        const u64 v = list[j];       // one address for the wave: broadcast
-        ra += v < a;
-        rb += v < b;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < n && ra < k) {
-        list[ra] = a;
-        if (ra == k - 1) *thr = a;
-    }
-    if (lane + 64 < n && rb < k) {
-        list[rb] = b;
-        if (rb == k - 1) *thr = b;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return n < k ? n : k;
-}
 
 __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __restrict__ queries, int Q, const float* __restrict__ gallery, int G,
                                                              int E, int k, const int* __restrict__ skip, int slab_rows, int split, u64* __restrict__ partial,
@@ -81,41 +48,9 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
         skip_row[r] = (skip && q < Q) ? skip[q] : -1;
     }
     DotRange seen;
-    // selection after each super-tile: C/D layout column = lane & 15, row = 4 (lane >> 4) + register
+    // selection after each super-tile (topk_select.h); the key's low word is the gallery row itself
     walk_gallery(sA, sB, queries + (long)q0 * E, nq, gallery, g0, g1, E, wave_live, qwave * 16, split ? wave * 16 : -1, [&](int c0, f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            if (split && ct > 0) break;                        // split: accumulator 0 holds column tile `wave`
-            const int tcol = c0 + (split ? wave : ct) * 16;
-            if (tcol >= g1) continue;                          // beyond the slab: zero-padded columns, never candidates
-            const int col = tcol + lr;
-            bool appended = false;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = wave * 16 + lg * 4 + r;         // the list; the query row is qwave * 16 + lg * 4 + r
-                const float s = acc[ct][r];
-                if (qwave * 16 + lg * 4 + r >= nq || col >= g1) continue;          // padding rows and zero-padded columns are never candidates
-                seen.add(s);
-                if (col == skip_row[r]) continue;
-                const u64 key = ((u64)__float_as_uint(pair_distance(s, 0)) << 32) | (unsigned)col;
-                if (key < sThr[row]) {
-                    const int slot = atomicAdd(&sCnt[row], 1);  // < cap: a row holds <= cap - 16 before a column tile adds <= 16
-                    sList[row * cap + slot] = key;
-                    appended = true;
-                }
-            }
-            if (__ballot(appended) == 0ull) continue;          // the common case once the thresholds are tight
-            __builtin_amdgcn_wave_barrier();
-            const int cnt = lane < 16 ? sCnt[wave * 16 + lane] : 0;
-            u64 full = __ballot(cnt > cap - 16);
-            while (full) {
-                const int row = wave * 16 + __builtin_ctzll(full);
-                full &= full - 1;
-                const int n = id_prune(sList + row * cap, sCnt[row], k, &sThr[row], lane);
-                if (lane == 0) sCnt[row] = n;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        id_select_tile(c0, acc, g1, nq, qwave, wave, split, skip_row, seen, sList, sThr, sCnt, cap, k, [](int col) { return col; });
     });
     seen.publish(range, lane);
     __syncthreads();                                           // also orders the list initialisation for an empty slab walk
@@ -123,8 +58,7 @@ __global__ __launch_bounds__(256, 4) void gallery_search_kernel(const float* __r
     for (int r = 0; r < 16; ++r) {                             // ascending k-list of every list of this wave -> partial[pslab][q][k]
         const int qrow = qwave * 16 + r, row = wave * 16 + r;
         if (qrow >= nq) break;
-        const int n = id_prune(sList + row * cap, sCnt[row], k, &sThr[row], lane);
-        if (lane < k) partial[(pslab * Q + q0 + qrow) * k + lane] = lane < n ? sList[row * cap + lane] : INONE;
+        id_emit(sList, sThr, sCnt, row, cap, k, lane, partial + (pslab * Q + q0 + qrow) * k);
     }
 }
 
@@ -137,26 +71,11 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(const u64* __restrict
     __shared__ u64 sList[IMERGE_CAP];
     __shared__ u64 sThr;
     const int q = blockIdx.x, lane = threadIdx.x;
-    if (lane == 0) sThr = INONE;
-    __builtin_amdgcn_wave_barrier();
-    int n = 0;
     const long total = (long)slabs * k;
-    for (long base = 0; base < total; base += 64) {
-        const long idx = base + lane;
-        u64 key = INONE;
-        if (idx < total) {
-            const long sl = idx / k;
-            key = partial[(sl * Q + q) * k + (idx - sl * k)];
-        }
-        const bool keep = key < sThr;                          // all ones never passes
-        const u64 m = __ballot(keep);
-        if (m == 0ull) continue;
-        if (keep) sList[n + __popcll(m & ((1ull << lane) - 1ull))] = key;
-        n += __popcll(m);
-        __builtin_amdgcn_wave_barrier();
-        if (n > IMERGE_CAP - 64) n = id_prune(sList, n, k, &sThr, lane);
-    }
-    n = id_prune(sList, n, k, &sThr, lane);
+    const int n = id_merge(sList, &sThr, total, k, lane, [&](long idx) {
+        const long sl = idx / k;
+        return partial[(sl * Q + q) * k + (idx - sl * k)];
+    });
     if (lane >= k) return;
     const long o = (long)q * k + lane;
     if (lane >= n) {                                           // fewer than k admissible rows

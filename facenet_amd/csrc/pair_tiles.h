@@ -1,5 +1,5 @@
 // The exact-fp32 pair machinery: ONE definition of everything that decides a bit of a pair's distance or of the `range` words, for
-// the kernels that compare distances exactly (validation.hip: the confusion counts; identify.hip: the k nearest rows;
+// the kernels that compare distances exactly (validation.hip: the confusion counts; identify.hip and ivf.hip: the k nearest rows;
 // opensearch.hip: the nearest mate and impostor; cluster.hip: every row within a radius; faceclass.hip takes tri_decode alone).
 // DESIGN.md section 16.  loss.hip's fn_pairwise_sqdist takes ord_f32, DotRange and pair_distance from here but NOT the dot
 // product: it sums s by wavefront reduction, so its distances agree with the chain's to rounding, not in bits.
@@ -10,7 +10,7 @@
 // callers compare d with the strict fp32 <.  `range` receives ord_f32 of the smallest and largest RAW s of the pairs a kernel
 // evaluated, and keeps its initial words (which decode to hi < lo) when it evaluated none.
 //
-// Which pairs are evaluated is defined here too: the gallery walk (identify.hip, opensearch.hip, cluster.hip) and the class-pair
+// Which pairs are evaluated is defined here too: the gallery walk (identify.hip, ivf.hip, opensearch.hip, cluster.hip) and the class-pair
 // walk (validation.hip's confidence_folds_kernel, verification.hip's pair_key_histogram_kernel; confidence_kernel keeps its own
 // scalar walk: it is the independent reference of the exactness tests).
 //

@@ -21,7 +21,10 @@ photographs without their embeddings leaving the device.
 
 ``Gallery.mates`` is the search of the open-set evaluation: every probe's nearest mate, nearest impostor and
 the rank of that mate at any depth, from fn_mate_search on the same walk and the same bits; ``statistics.IdentificationCurve``
-turns them into FNIR at FPIR."""
+turns them into FNIR at FPIR.
+
+``Gallery.kmeans`` and ``Gallery.ivf`` (`ivf.py`): spherical k-means on the device and the inverted-file
+index it trains; an `ivf.IVFGallery` searches only the lists a query probes, with `search`'s bits."""
 from __future__ import annotations
 
 import ctypes
@@ -321,6 +324,18 @@ class Gallery:
     def leave_one_out(self, k=1):
         """Every gallery row's k nearest OTHER rows, device tensors: ``search(gallery, k, skip=arange(G))``."""
         return self.search(self.embeddings, k, skip=np.arange(self.nrof_images, dtype=np.int32))
+
+    def kmeans(self, nlist, iters=10, seed=0):
+        """Spherical k-means of the gallery's rows into ``nlist`` groups on the device -> (centroids fp32
+        [nlist, E], assign int32 [G], info): `ivf.kmeans`.  Reproducible bit for bit for a given seed."""
+        from .ivf import kmeans
+        return kmeans(self, nlist, iters, seed)
+
+    def ivf(self, nlist, iters=10, seed=0):
+        """The inverted-file index of this gallery over the k-means of its rows -> `ivf.IVFGallery`, whose searches walk only
+        the lists a query probes."""
+        from .ivf import ivf
+        return ivf(self, nlist, iters, seed)
 
     def _label_codes(self):
         """(the gallery's sorted unique labels int64 [C], device int32 [G] dense codes 0 .. C - 1), built once: fn_mate_search

@@ -394,6 +394,33 @@ int fn_gallery_search(const float* queries, int Q, const float* gallery, int G, 
                       const int32_t* labels, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* row_labels,
                       float* range, void* stream);
 
+/* ---- the inverted-file index ------------------------------------------------------------------------------
+ * fn_kmeans_update: the centroid step of spherical k-means.  rows fp32 [N, E] (E a multiple of 4 in [4, 512]); order int32 [N]: the
+ * row numbers sorted by (list, row), both ascending; list_start int32 [L + 1]: list c's members are order[list_start[c] ..
+ * list_start[c + 1]); prev fp32 [L, E]: the previous centroids.  sum[c][e] is the sequential fp64 sum, from 0.0, of (double)
+ * rows[m][e] over the members m of c in ascending row order; n2[c] is the sequential fp64 sum, from 0.0 and over ascending e, of
+ * the products sum[c][e] * sum[c][e], each rounded to fp64 before it is added (no fused multiply-add); centroids[c][e] =
+ * (float)(sum[c][e] / sqrt(n2[c])), IEEE fp64 square root and division, one rounding to fp32.  A list without a member, or with
+ * n2 == 0, keeps prev[c] bit for bit and gets kept[c] = 1; every other list kept[c] = 0.  centroids fp32 [L, E] must not be
+ * prev; kept int32 [L].  No atomics: a call is reproducible bit for bit.
+ *
+ * fn_ivf_search: fn_gallery_search over the lists each query probes.  lists fp32 [G, E]: the gallery rows stored list by list;
+ * ids int32 [G]: the original row of each stored row, ascending within a list; list_start int32 [L + 1].  probes int32
+ * [Q, nprobe]: the lists query q walks; -1 (or any value outside [0, L)) is none, the other entries of a row must be distinct.
+ * s, sc, the key bits(2 (1 - sc)) << 32 | ORIGINAL row, the order and dist are fn_gallery_search's bit for bit; rows int32 [Q, k]
+ * holds original rows and skip int32 [Q] (or NULL) names one; a query with fewer than k admissible rows in its lists gets row -1,
+ * dist +inf in the tail.  Given the index the result depends on nothing else; with every list probed it is fn_gallery_search's on
+ * the unpermuted gallery.  range (2 words or NULL): ordered-int min/max of s over the pairs evaluated, skipped pairs included.
+ * queries, lists and the workspace 16-byte aligned; 1 <= k <= 64; E a multiple of 4 in [4, 512]; L <= 2^20; Q nprobe <= 2^28.
+ * workspace: at least the bytes fn_ivf_search_workspace reports for the same Q, L, nprobe, E and k (it holds one copy of a query
+ * row and one k-list per (query, probe) pair).  The caller owns every buffer; no call here allocates or synchronises. */
+int fn_kmeans_update(const float* rows, int N, int E, const int32_t* order, const int32_t* list_start, int L, const float* prev,
+                     float* centroids, int32_t* kept, void* stream);
+int fn_ivf_search_workspace(int Q, int L, int nprobe, int E, int k, long long* bytes);
+int fn_ivf_search(const float* queries, int Q, const float* lists, const int32_t* ids, int G, const int32_t* list_start, int L, int E,
+                  const int32_t* probes, int nprobe, int k, int metric, const int32_t* skip, void* workspace, float* dist,
+                  int32_t* rows, int32_t* range, void* stream);
+
 /* ---- open-set 1:N evaluation: per probe its nearest mate, its nearest impostor and the rank of that mate;
  * the [Q, G] matrix never reaches memory.  s, sc, d0 = 2 (1 - sc) and the key bits(d0) << 32 | row are those of fn_gallery_search,
  * fn_radius_*, fn_confidence_counts* and fn_pair_key_histogram bit for bit.  queries, gallery, E, metric, skip, slab_rows and the
