@@ -19,9 +19,10 @@ import numpy as np
 import torch
 
 from facenet_amd import _lib
+from facenet_amd._call import as_table, ptr, stream
 from facenet_amd.config import Config, _merge
 from facenet_amd.faceclass import (ClassifierTrainer, FaceToFaceDistanceClassifier, FaceToFaceNormalizedEmbeddingsClassifier,
-                                   _as_table, _ptr, _stream, check_optimizer, row_norms)
+                                   check_optimizer, row_norms)
 from facenet_amd.facenet import Embeddings, equal_batches_input_pipeline
 
 # apps/configs/train_classifier.yaml of the reference (embeddings.path names an .npz here) and config.yaml's seed
@@ -122,14 +123,14 @@ def pair_counts(embeddings, classifier, table=None, norms=None) -> np.ndarray:
     dev = classifier.device
     sizes = [len(e) for e in embeddings]
     if table is None:
-        table = _as_table(np.concatenate([np.asarray(e, dtype=np.float32) for e in embeddings]), dev)
+        table = as_table(np.concatenate([np.asarray(e, dtype=np.float32) for e in embeddings]), dev)
     if norms is None and classifier.mode == FaceToFaceDistanceClassifier.mode:
         norms = row_norms(table)
     starts = torch.as_tensor(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), device=dev)
     C = len(sizes)
     out = torch.empty(C * (C + 1) // 2, dtype=torch.int64, device=dev)
-    _lib.check(_lib.load().fn_f2f_pair_counts(_ptr(table), _ptr(norms), _ptr(starts), C, table.shape[1], classifier.mode,
-                                              _ptr(classifier.params), _ptr(out), _stream(dev)), "f2f_pair_counts")
+    _lib.check(_lib.load().fn_f2f_pair_counts(ptr(table), ptr(norms), ptr(starts), C, table.shape[1], classifier.mode,
+                                              ptr(classifier.params), ptr(out), stream(dev)), "f2f_pair_counts")
     return out.cpu().numpy()
 
 

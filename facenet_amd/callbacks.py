@@ -13,6 +13,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ._call import host_array
+
 # A validation set whose decoded uint8 images (nrof_images * size * size * 3 bytes) fit in this many bytes stays on the device
 # after the first pass; a larger one is streamed from disk on every pass.  The reference's 26 489-image set is 2.0 GB.
 RESIDENT_BYTES = 4 << 30
@@ -109,7 +111,7 @@ class ValidateCallback:
         for j, (images, labels) in enumerate(self.dataset):
             if j % self.world != self.rank:
                 continue
-            labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+            labels = host_array(labels)
             if kept is not None:
                 x = torch.as_tensor(images)
                 x = x.to(self.device, copy=True) if self.device is not None else x.clone()    # a copy: pipelines may reuse buffers

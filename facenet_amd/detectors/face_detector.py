@@ -74,25 +74,22 @@ def crop_resize(frame, windows, side, ox=0, oy=0, out_side=None, stream=None):
     """`Image.fromarray(frame).crop(w).resize((side, side), LANCZOS)` for every window w -> device uint8 [F, S, S, 3]: rows / columns
     [oy, oy + S) x [ox, ox + S) of each result (S = out_side, the whole thumbnail by default).  frame: uint8 [H, W, 3], an array
     or a device tensor."""
-    import ctypes as C
-
     import torch
 
-    from .. import _lib
+    from .. import _call, _lib
     out_side = side if out_side is None else out_side
     windows = np.ascontiguousarray(windows, dtype=np.int32)
     check_crop_arguments(windows, side, ox, oy, out_side)
     frame = _device_frame(frame, "face crop")
     lib = _lib.load()
-    words = C.c_longlong(0)
     count = windows.shape[0]
-    _lib.check(lib.fn_face_crop_workspace(windows.ctypes.data, count, side, C.byref(words)), "face_crop_workspace")
+    words = _call.workspace_size(lib.fn_face_crop_workspace, "face_crop_workspace", windows.ctypes.data, count, side)
     work = _workspace.get(frame.device)
-    if work is None or work.numel() < words.value:
-        work = _workspace[frame.device] = torch.empty(words.value, dtype=torch.int32, device=frame.device)
+    if work is None or work.numel() < words:
+        work = _workspace[frame.device] = torch.empty(words, dtype=torch.int32, device=frame.device)
     out = torch.empty(count, out_side, out_side, 3, dtype=torch.uint8, device=frame.device)
     with torch.cuda.device(frame.device):
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        st = _call.stream() if stream is None else stream
         _lib.check(lib.fn_face_crop_resize_u8(frame.data_ptr(), frame.shape[0], frame.shape[1], windows.ctypes.data, count, side, ox, oy,
                                               out_side, out.data_ptr(), work.data_ptr(), work.numel(), st), "face_crop_resize")
     return out
@@ -205,11 +202,9 @@ _align_workspace = {}     # device -> int64 workspace of the transform tables, g
 def align_faces(frame, alignment, size, stream=None):
     """Warp every face of `alignment` (all of them alignable) out of the frame -> device uint8 [F, size, size, 3], one
     fn_face_align_u8 launch.  frame: uint8 [H, W, 3], an array or a device tensor."""
-    import ctypes as C
-
     import torch
 
-    from .. import _lib
+    from .. import _call, _lib
     inverse = np.ascontiguousarray(alignment.inverse, dtype=np.float64)
     samples = np.ascontiguousarray(alignment.samples, dtype=np.int32)
     size = int(size)
@@ -217,14 +212,13 @@ def align_faces(frame, alignment, size, stream=None):
     frame = _device_frame(frame, "face align")
     lib = _lib.load()
     count = inverse.shape[0]
-    nbytes = C.c_longlong(0)
-    _lib.check(lib.fn_face_align_workspace(count, C.byref(nbytes)), "face_align_workspace")
+    nbytes = _call.workspace_size(lib.fn_face_align_workspace, "face_align_workspace", count)
     work = _align_workspace.get(frame.device)
-    if work is None or work.numel() * 8 < nbytes.value:
-        work = _align_workspace[frame.device] = torch.empty(nbytes.value // 8, dtype=torch.int64, device=frame.device)
+    if work is None or work.numel() * 8 < nbytes:
+        work = _align_workspace[frame.device] = torch.empty(nbytes // 8, dtype=torch.int64, device=frame.device)
     out = torch.empty(count, size, size, 3, dtype=torch.uint8, device=frame.device)
     with torch.cuda.device(frame.device):
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        st = _call.stream() if stream is None else stream
         _lib.check(lib.fn_face_align_u8(frame.data_ptr(), frame.shape[0], frame.shape[1], inverse.ctypes.data, samples.ctypes.data, count, size,
                                         out.data_ptr(), work.data_ptr(), work.numel() * 8, st), "face_align")
     return out

@@ -16,7 +16,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _call, _lib
+from .._call import ptr
 
 # name, KH, KW, Cin, Cout, prelu | pool: k, stride, same
 _P = [("conv", "conv1", 3, 3, 3, 10, "prelu1"), ("pool", 2, 2, True), ("conv", "conv2", 3, 3, 10, 16, "prelu2"),
@@ -31,10 +32,6 @@ _SPECS = {"pnet": _P, "rnet": _R, "onet": _O}
 
 def _pad8(c):
     return (c + 7) // 8 * 8
-
-
-def _ptr(t):
-    return t.data_ptr()
 
 
 class InvalidImage(Exception):
@@ -112,13 +109,12 @@ class _Network:
         for kind, L, src, dst, g in plan["steps"]:
             if kind == "pool":
                 a, b, c, oa, ob, pa, pb = g
-                _lib.check(lib.fn_maxpool2d_fwd(_ptr(src), c, _ptr(dst), c, n, a, b, c, L["k"], L["stride"], pa, pb, oa, ob, self.code, stream), "maxpool2d")
+                _lib.check(lib.fn_maxpool2d_fwd(ptr(src), c, ptr(dst), c, n, a, b, c, L["k"], L["stride"], pa, pb, oa, ob, self.code, stream), "maxpool2d")
             else:
                 a, b, oa, ob = g
                 d = _lib.ConvDesc(N=n, H=a, W=b, Cin=L["Cin"], OH=oa, OW=ob, Cout=L["Cout"], KH=L["KH"], KW=L["KW"], stride=1, pad_h=0, pad_w=0,
                                   dtype=self.code, ld_x=L["Cin"], ld_y=L["Cout"], out_f32=1 if L["f32"] else 0, scale=1.0,
-                                  x=_ptr(src), w=_ptr(L["w"]), y=_ptr(dst), bias=_ptr(L["bias"]),
-                                  prelu=_ptr(L["prelu"]) if L["prelu"] is not None else None)
+                                  x=ptr(src), w=ptr(L["w"]), y=ptr(dst), bias=ptr(L["bias"]), prelu=ptr(L["prelu"]))
                 _lib.check(lib.fn_conv2d_fwd(d, stream), f"mtcnn {self.net} conv")
         return plan["out"]
 
@@ -163,7 +159,7 @@ class _DeviceNms:
 
     def run(self, jobs):
         """jobs: [(boxes float64 [n, >=5], threshold, by_min)] -> [int64 indices of the kept boxes, best first]."""
-        lib, st = _lib.load(), torch.cuda.current_stream(self.device).cuda_stream
+        lib, st = _lib.load(), _call.stream(self.device)
         out = [None] * len(jobs)
         dev = [k for k, (b, _, _) in enumerate(jobs) if self.HOST_MAX < b.shape[0] <= self.MAX_N]
         for k, (b, thr, by_min) in enumerate(jobs):
@@ -287,7 +283,7 @@ class MTCNN:
 
     def pnet_maps(self, frame, level):
         """Testing aid: (offsets [A,B,4], face probability [A,B]) of one pyramid level in the network's [x][y] orientation."""
-        st = torch.cuda.current_stream(self.device).cuda_stream
+        st = _call.stream(self.device)
         H, W = frame.shape[:2]
         pyr = self._pyramid(H, W)
         lv = pyr["levels"][level]
@@ -302,10 +298,10 @@ class MTCNN:
         lv = pyr["levels"][i]
         H, W = frame.shape[:2]
         pnet = self._nets["pnet"]
-        _lib.check(lib.fn_area_resize_frame(_ptr(frame), H, W, lv["hs"], lv["ws"], _ptr(pyr["rows"]), _ptr(lv["plan"]["x"]), pnet.code, st), "area_resize_frame")
+        _lib.check(lib.fn_area_resize_frame(ptr(frame), H, W, lv["hs"], lv["ws"], ptr(pyr["rows"]), ptr(lv["plan"]["x"]), pnet.code, st), "area_resize_frame")
         out = pnet.run(lv["plan"], 1, st)
-        _lib.check(lib.fn_mtcnn_candidates(_ptr(out), lv["A"] * lv["B"], pnet.out_channels, float(self._steps_threshold[0] if threshold is None else threshold),
-                                           _ptr(rec) + 32, _ptr(rec), rec.shape[0] - 1, i, 1 if reset else 0, st), "mtcnn_candidates")
+        _lib.check(lib.fn_mtcnn_candidates(ptr(out), lv["A"] * lv["B"], pnet.out_channels, float(self._steps_threshold[0] if threshold is None else threshold),
+                                           ptr(rec) + 32, ptr(rec), rec.shape[0] - 1, i, 1 if reset else 0, st), "mtcnn_candidates")
         return out
 
     def _stage1(self, frame):
@@ -324,7 +320,7 @@ class MTCNN:
                 torch.cuda.synchronize(self.device)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    st = torch.cuda.current_stream(self.device).cuda_stream
+                    st = _call.stream(self.device)
                     pyr["outs"] = [self._run_level(pyr["frame"], pyr, i, st, pyr["rec"], reset=(i == 0)) for i in range(len(levels))]
                 pyr["graph"] = g
             pyr["frame"].copy_(frame)
@@ -371,7 +367,7 @@ class MTCNN:
     # -- stages 2 and 3 ------------------------------------------------------------------------------------------------
     def _refine(self, frame, boxes, net, size):
         """Crops of `boxes` -> network -> fp32 head rows [n, C] on the host."""
-        lib, st = _lib.load(), torch.cuda.current_stream(self.device).cuda_stream
+        lib, st = _lib.load(), _call.stream(self.device)
         H, W = frame.shape[:2]
         n = boxes.shape[0]
         cap = 64
@@ -380,7 +376,7 @@ class MTCNN:
         network = self._nets[net]
         plan = network._plan("crops", cap, size, size)
         win = torch.from_numpy(_windows(boxes)).to(self.device)
-        _lib.check(lib.fn_area_resize_crop(_ptr(frame), H, W, _ptr(win), n, size, size, 0, _ptr(plan["x"]), network.code, st), "area_resize_crop")
+        _lib.check(lib.fn_area_resize_crop(ptr(frame), H, W, ptr(win), n, size, size, 0, ptr(plan["x"]), network.code, st), "area_resize_crop")
         out = network.run(plan, n, st)
         return out[:n].reshape(n, -1).cpu().numpy()
 

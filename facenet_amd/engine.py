@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, keras_names, params as _params
+from ._call import ptr as _ptr          # (train.py, heads.py, optimizers.py, grouping.py, triplet.py and models/ import it from here)
 from ._lib import ConvDesc
 from .params import Layer, _pad8
 from .schedule import Op, Region, emit, region, stats_region
@@ -131,10 +132,6 @@ class Rec:
     x: Optional[Slice] = None
     y: Optional[Slice] = None
     extra: dict = field(default_factory=dict)
-
-
-def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
-    return t.data_ptr() + elem_off * t.element_size()
 
 
 def weight_region(pack: torch.Tensor, L: Layer) -> Region:

@@ -18,37 +18,17 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import as_table, ptr, stream
 
 MODE_DISTANCE, MODE_NORMALIZED = 0, 1
 TILE = 64                 # rows per tile side of fn_f2f_pair_loss_fwd_bwd (include/facenet_hip.h)
 ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON = 0.9, 0.999, 0.1
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _as_table(x, device) -> torch.Tensor:
-    """fp32 [n, E] contiguous on `device`, rows 16-byte aligned (E % 4 == 0 is required by the kernels)."""
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-    if t.dim() != 2:
-        raise ValueError(f"embeddings must be a 2-D [n, E] array, got shape {tuple(t.shape)}")
-    if t.shape[1] % 4:
-        raise ValueError(f"embedding length {t.shape[1]} must be a multiple of 4")
-    t = t.to(device=device, dtype=torch.float32).contiguous()
-    if t.data_ptr() % 16:
-        t = t.clone()
-    return t
-
-
 def row_norms(table: torch.Tensor) -> torch.Tensor:
     """|x_r| of every row (fn_f2f_row_norms)."""
     out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
-    _lib.check(_lib.load().fn_f2f_row_norms(_ptr(table), table.shape[0], table.shape[1], _ptr(out), _stream(table.device)),
+    _lib.check(_lib.load().fn_f2f_row_norms(ptr(table), table.shape[0], table.shape[1], ptr(out), stream(table.device)),
                "f2f_row_norms")
     return out
 
@@ -81,8 +61,8 @@ class _FaceToFaceClassifier:
 
     def _matrix(self, x, y, logits):
         numpy_in = not torch.is_tensor(x)
-        xt = _as_table(x, self.device)
-        yt = xt if y is None else _as_table(y, self.device)
+        xt = as_table(x, self.device)
+        yt = xt if y is None else as_table(y, self.device)
         if yt.shape[1] != xt.shape[1]:
             raise ValueError(f"embedding lengths differ: {xt.shape[1]} and {yt.shape[1]}")
         nx = ny = None
@@ -90,8 +70,8 @@ class _FaceToFaceClassifier:
             nx = row_norms(xt)
             ny = nx if y is None else row_norms(yt)
         out = torch.empty(xt.shape[0], yt.shape[0], dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().fn_f2f_distance(_ptr(xt), _ptr(nx), xt.shape[0], _ptr(yt), _ptr(ny), yt.shape[0], xt.shape[1], self.mode,
-                                               _ptr(self.params), int(logits), _ptr(out), _stream(self.device)), "f2f_distance")
+        _lib.check(_lib.load().fn_f2f_distance(ptr(xt), ptr(nx), xt.shape[0], ptr(yt), ptr(ny), yt.shape[0], xt.shape[1], self.mode,
+                                               ptr(self.params), int(logits), ptr(out), stream(self.device)), "f2f_distance")
         return out.cpu().numpy() if numpy_in else out
 
     def __call__(self, x, y=None):
@@ -161,7 +141,7 @@ class ClassifierTrainer:
         self.model, self.P, self.K, self.B = model, P, K, P * K
         dev = self.device = model.device
         arrays = list(embeddings) if isinstance(embeddings, (list, tuple)) else [embeddings]
-        self.table = _as_table(np.concatenate([np.asarray(e, dtype=np.float32) for e in arrays]) if not torch.is_tensor(arrays[0])
+        self.table = as_table(np.concatenate([np.asarray(e, dtype=np.float32) for e in arrays]) if not torch.is_tensor(arrays[0])
                                else torch.cat(arrays), dev)
         self.n_rows, self.E = self.table.shape
         self.norms = row_norms(self.table) if model.mode == MODE_DISTANCE else None
@@ -178,12 +158,12 @@ class ClassifierTrainer:
         self._graph = None
 
     def _launch(self):
-        lib, st = _lib.load(), _stream(self.device)
-        _lib.check(lib.fn_f2f_pair_loss_fwd_bwd(_ptr(self.table), _ptr(self.norms), self.n_rows, _ptr(self.rows), self.P, self.K, self.E,
-                                                self.model.mode, self.q, _ptr(self.model.params), _ptr(self.loss), _ptr(self.grad),
-                                                _ptr(self.ws), self.ws.numel(), st), "f2f_pair_loss_fwd_bwd")
-        _lib.check(lib.fn_adam_tick(_ptr(self.hyper), ADAM_BETA1, ADAM_BETA2, st), "adam_tick")
-        _lib.check(lib.fn_adam_keras(_ptr(self.model.params), _ptr(self.grad), _ptr(self.M), _ptr(self.V), None, 0, 4, 0, _ptr(self.hyper),
+        lib, st = _lib.load(), stream(self.device)
+        _lib.check(lib.fn_f2f_pair_loss_fwd_bwd(ptr(self.table), ptr(self.norms), self.n_rows, ptr(self.rows), self.P, self.K, self.E,
+                                                self.model.mode, self.q, ptr(self.model.params), ptr(self.loss), ptr(self.grad),
+                                                ptr(self.ws), self.ws.numel(), st), "f2f_pair_loss_fwd_bwd")
+        _lib.check(lib.fn_adam_tick(ptr(self.hyper), ADAM_BETA1, ADAM_BETA2, st), "adam_tick")
+        _lib.check(lib.fn_adam_keras(ptr(self.model.params), ptr(self.grad), ptr(self.M), ptr(self.V), None, 0, 4, 0, ptr(self.hyper),
                                      ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, 0.0, _lib.FN_BF16, st), "adam_keras")
 
     def set_rows(self, rows):

@@ -19,21 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .faceclass import _ptr, _stream
-from .recognize import MAX_K, Gallery
-from .statistics import check_unit_range
-
-
-def check_nlist(nlist, G):
-    if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= nlist <= G:
-        raise ValueError(f"nlist must be an integer in [1, {G}] (the gallery's rows), got {nlist!r}")
-    return int(nlist)
-
-
-def check_nprobe(nprobe):
-    if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or nprobe < 1:
-        raise ValueError(f"nprobe must be an integer of at least 1, got {nprobe!r}")
-    return int(nprobe)
+from ._call import check_int, host_array, ptr, stream
+from .gallery import MAX_K, Gallery, check_k, like_queries, shape_of
 
 
 def initial_rows(G, nlist, seed):
@@ -46,29 +33,24 @@ def kmeans(gallery, nlist, iters=10, seed=0):
     the ones returned.  ``info``: ``iterations`` (centroid updates run), ``moved`` (rows whose list changed at each assignment
     step; the first counts every row), ``empty`` (lists without a row in ``assign``) and ``converged``."""
     G = gallery.nrof_images
-    nlist = check_nlist(nlist, G)
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
-        raise ValueError(f"iters must be a non-negative integer, got {iters!r}")
+    nlist = check_int("nlist", nlist, 1, G, note=" (the gallery's rows)")
+    iters = check_int("iters", iters, 0)
     dev, E = gallery.device, gallery.length
     if dev.type != "cuda":
         raise _lib.FacenetHipError("Gallery.kmeans runs fn_kmeans_update on the GPU; facenet_amd has no CPU fallback")
-    lib, rows, st = _lib.load(), gallery.embeddings, _stream(dev)
+    lib, rows, st = _lib.load(), gallery.embeddings, stream(dev)
     centroids = rows[torch.from_numpy(initial_rows(G, nlist, seed)).to(dev)].contiguous()
-    ws = gallery._workspace(lib.fn_gallery_search_workspace, "gallery_search_workspace", G, nlist, 1, 0)
-    dist = torch.empty((G, 1), dtype=torch.float32, device=dev)
     kept = torch.empty(nlist, dtype=torch.int32, device=dev)
 
-    def assign_step():
-        near = torch.empty((G, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.fn_gallery_search(_ptr(rows), G, _ptr(centroids), nlist, E, 1, 0, None, None, 0, _ptr(ws), _ptr(dist), _ptr(near), None,
-                                         None, st), "gallery_search")
-        return near.view(G)
+    def assign_step(assign):
+        """Every row's nearest centroid: the rows as the queries of a search over the centroids (metric 0, no range check)."""
+        new = Gallery(centroids, device=dev)._search(rows, 1, atol=None)[1].view(G)
+        moved.append(G if assign is None else int((new != assign).sum().item()))
+        return new
 
     assign, moved, updates, converged = None, [], 0, False
     for _ in range(iters):
-        new = assign_step()
-        moved.append(G if assign is None else int((new != assign).sum().item()))
-        assign = new
+        assign = assign_step(assign)
         if moved[-1] == 0:
             converged = True
             break
@@ -76,19 +58,14 @@ def kmeans(gallery, nlist, iters=10, seed=0):
         list_start = torch.zeros(nlist + 1, dtype=torch.int32, device=dev)
         list_start[1:] = torch.cumsum(torch.bincount(assign, minlength=nlist), 0)
         updated = torch.empty_like(centroids)
-        _lib.check(lib.fn_kmeans_update(_ptr(rows), G, E, _ptr(order), _ptr(list_start), nlist, _ptr(centroids), _ptr(updated), _ptr(kept), st),
+        _lib.check(lib.fn_kmeans_update(ptr(rows), G, E, ptr(order), ptr(list_start), nlist, ptr(centroids), ptr(updated), ptr(kept), st),
                    "kmeans_update")
         centroids, updates = updated, updates + 1
     if not converged:                                                        # the rows' lists under the centroids returned
-        new = assign_step()
-        moved.append(G if assign is None else int((new != assign).sum().item()))
-        assign, converged = new, moved[-1] == 0
+        assign = assign_step(assign)
+        converged = moved[-1] == 0
     empty = int((torch.bincount(assign, minlength=nlist) == 0).sum().item())
     return centroids, assign, {"iterations": updates, "moved": moved, "empty": empty, "converged": converged}
-
-
-def _host(x):
-    return np.asarray(x.cpu() if torch.is_tensor(x) else x)
 
 
 class IVFGallery(Gallery):
@@ -101,7 +78,7 @@ class IVFGallery(Gallery):
     def __init__(self, lists, ids, list_start, centroids, labels=None, names=None, files=None, metric=0, device="cuda", nprobe=8):
         super().__init__(lists, labels=labels, names=names, files=files, metric=metric, device=device)
         G = self.nrof_images
-        ids, list_start = _host(ids), _host(list_start)
+        ids, list_start = host_array(ids), host_array(list_start)
         if ids.shape != (G,) or ids.dtype.kind not in "iu" or not np.array_equal(np.sort(ids), np.arange(G)):
             raise ValueError(f"ids must be a permutation of the {G} gallery rows")
         if list_start.ndim != 1 or len(list_start) < 2 or list_start.dtype.kind not in "iu" or list_start[0] != 0 or list_start[-1] != G \
@@ -116,7 +93,7 @@ class IVFGallery(Gallery):
             centroids = Gallery(centroids, metric=metric, device=device)
         if centroids.nrof_images != self.nlist or centroids.length != self.length:
             raise ValueError(f"centroids must be [{self.nlist}, {self.length}], got [{centroids.nrof_images}, {centroids.length}]")
-        self.centroids, self.nprobe = centroids, check_nprobe(nprobe)
+        self.centroids, self.nprobe = centroids, check_int("nprobe", nprobe, 1)
         self._ids_dev = self._list_start_dev = None
 
     @property
@@ -132,10 +109,10 @@ class IVFGallery(Gallery):
         """The index of ``gallery`` under any assignment of its rows to lists: ``centroids`` [nlist, E], ``assign`` [G] integers
         in [0, nlist).  Rows keep their order within a list."""
         G, E = gallery.nrof_images, gallery.length
-        shape = tuple(centroids.shape) if hasattr(centroids, "shape") else np.shape(centroids)
+        shape = shape_of(centroids)
         if len(shape) != 2 or shape[0] < 1 or shape[1] != E:
             raise ValueError(f"centroids must be a non-empty 2-D [nlist, {E}] array, got shape {shape}")
-        assign = _host(assign)
+        assign = host_array(assign)
         if assign.shape != (G,) or assign.dtype.kind not in "iu":
             raise ValueError(f"assign must be {G} integers (the list of every row), got shape {assign.shape} of {assign.dtype}")
         if G and (assign.min() < 0 or assign.max() >= shape[0]):
@@ -178,52 +155,36 @@ class IVFGallery(Gallery):
             self._list_start_dev = torch.from_numpy(self.list_start).to(self.device)
         return self._ids_dev, self._list_start_dev
 
-    def _search(self, queries, k, skip, slab_rows, atol, nprobe=None):
-        """-> device (dist [Q, k], rows [Q, k]) after every check of `search`."""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        nprobe = min(check_nprobe(self.nprobe if nprobe is None else nprobe), self.nlist)
+    def _search(self, queries, k, skip=None, slab_rows=0, atol=1.e-5, *, nprobe=None):
+        """-> device (dist [Q, k], rows [Q, k]) after every check of `search`.  ``slab_rows`` has no meaning here."""
+        k = check_k(k)
+        nprobe = min(check_int("nprobe", self.nprobe if nprobe is None else nprobe, 1), self.nlist)
         if nprobe > MAX_K:
             raise ValueError(f"nprobe must be at most {MAX_K} (the centroid search keeps k <= {MAX_K}), got {nprobe}")
-        Q, q, skip_dev = self._queries(queries, skip, "IVFGallery.search runs fn_ivf_search")
-        dev, G, L = self.device, self.nrof_images, self.nlist
-        dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
-        if Q == 0:
-            return dist, rows
-        lib = _lib.load()
-        probes = self.centroids._search(q, nprobe, None, 0, None)[1]
-        ids, list_start = self._index()
-        ws = self._workspace(lib.fn_ivf_search_workspace, "ivf_search_workspace", Q, L, nprobe, self.length, k)
-        rng = None if atol is None else torch.zeros(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.fn_ivf_search(_ptr(q), Q, _ptr(self.embeddings), _ptr(ids), G, _ptr(list_start), L, self.length, _ptr(probes), nprobe, k,
-                                     self.metric, _ptr(skip_dev), _ptr(ws), _ptr(dist), _ptr(rows), _ptr(rng), _stream(dev)), "ivf_search")
-        if rng is not None:
-            check_unit_range(rng, atol)         # waits for the search
-        return dist, rows
+        G, L = self.nrof_images, self.nlist
+
+        def launch(c, dist, rows):
+            probes = self.centroids._search(c.queries, nprobe, atol=None)[1]
+            ids, list_start = self._index()
+            _lib.check(c.lib.fn_ivf_search(ptr(c.queries), c.Q, ptr(self.embeddings), ptr(ids), G, ptr(list_start), L, self.length, ptr(probes),
+                                           nprobe, k, self.metric, ptr(c.skip), ptr(c.workspace), ptr(dist), ptr(rows), ptr(c.range), c.stream),
+                       "ivf_search")
+
+        return self._run("IVFGallery.search runs fn_ivf_search", queries, skip, atol, lambda Q: self._nearest(Q, k), "ivf_search_workspace",
+                         lambda Q: (Q, L, nprobe, self.length, k), launch)
 
     def search(self, queries, k=1, nprobe=None, skip=None, atol=1.e-5):
         """`Gallery.search` over the ``nprobe`` lists nearest to each query (None: the index's default; clamped to nlist):
         the same return types, the same errors, rows and ``skip`` in the parent gallery's row numbers.  A query whose lists hold
         fewer than k admissible rows gets row -1 at distance +inf in the tail.  The normalisation check covers the pairs
         evaluated."""
-        dist, rows = self._search(queries, k, skip, 0, atol, nprobe)
-        if torch.is_tensor(queries):
-            return dist, rows
-        return dist.cpu().numpy(), rows.cpu().numpy()
+        return like_queries(queries, self._search(queries, k, skip, atol=atol, nprobe=nprobe))
 
     def leave_one_out(self, k=1, nprobe=None):
         """Every gallery row's k nearest OTHER rows among its probed lists, device tensors indexed by ORIGINAL row."""
         dist, rows = self.search(self.embeddings, k, nprobe=nprobe, skip=self.ids)
         ids = self._index()[0].long()
         return torch.empty_like(dist).index_copy_(0, ids, dist), torch.empty_like(rows).index_copy_(0, ids, rows)
-
-    def identify(self, queries, threshold=None, classifier=None, k=1, nprobe=None):
-        """`Gallery.identify` through the probed lists."""
-        thr = self.threshold_of(threshold, classifier)
-        dist, rows = self._search(queries, k, None, 0, 1.e-5, nprobe)
-        return [self.who(d, r, thr) for d, r in zip(dist[:, 0].cpu().numpy(), rows[:, 0].cpu().numpy())]
 
     def _not_indexed(self, *args, **kwargs):
         raise NotImplementedError("an IVFGallery answers search, leave_one_out and identify; run this on the Gallery it was built from")

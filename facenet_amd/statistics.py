@@ -6,22 +6,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr
-
-
-def _decode_ord(i: int) -> float:
-    i = int(i)
-    bits = i if i >= 0 else (i ^ 0x7FFFFFFF)
-    return float(np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0])
-
-
-def check_unit_range(rng_words, atol):
-    """The two `range` words of a kernel (a device tensor; reading them waits for the kernel) -> the reference's ValueError when
-    some dot product left +-(1 + atol) (statistics.py:40-42).  A kernel that evaluated no pair leaves words that decode to
-    lo = +3.4e38 > hi = -3.4e38, which neither comparison takes for a violation: the empty case needs no rule of its own."""
-    lo, hi = (_decode_ord(v) for v in rng_words.cpu().tolist())
-    if lo < -(1 + atol) or hi > 1 + atol:
-        raise ValueError("\nembeddings must be normalized to 1, range {} {}".format(lo, hi))
+from ._call import _decode_ord, check_int, check_unit_range, host_array, ptr, stream      # noqa: F401  (the tests read _decode_ord here)
+from .gallery import Gallery
 
 
 def pairwise_similarities(xa, xb=None, metric: int = 0, atol: float = 1.e-5, device: str = "cuda"):
@@ -37,8 +23,7 @@ def pairwise_similarities(xa, xb=None, metric: int = 0, atol: float = 1.e-5, dev
         return np.zeros((0,) if xb is None else (n, m), dtype=np.float32)
     out = torch.empty(n, m, dtype=torch.float32, device=a.device)
     rng = torch.zeros(2, dtype=torch.int32, device=a.device)
-    st = torch.cuda.current_stream(a.device).cuda_stream
-    _lib.check(lib.fn_pairwise_sqdist(_ptr(a), _ptr(b), _ptr(out), _ptr(rng), n, m, E, metric, st), "pairwise_sqdist")
+    _lib.check(lib.fn_pairwise_sqdist(ptr(a), ptr(b), ptr(out), ptr(rng), n, m, E, metric, stream(a.device)), "pairwise_sqdist")
     if xb is None:
         iu = torch.triu_indices(n, n, offset=1, device=a.device)
         sims = out[iu[0], iu[1]]
@@ -162,9 +147,8 @@ class ConfidenceMatrix:
         out = torch.zeros(4 * thr.size, dtype=torch.float64, device=dev)
         rng = torch.zeros(2, dtype=torch.int32, device=dev)
         n, E = calculator.emb.shape
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.fn_confidence_counts(_ptr(calculator.emb), _ptr(calculator._cls), calculator.nrof_classes, E, _ptr(t_dev), thr.size,
-                                            calculator.metric, _ptr(out), _ptr(rng), st), "confidence_counts")
+        _lib.check(lib.fn_confidence_counts(ptr(calculator.emb), ptr(calculator._cls), calculator.nrof_classes, E, ptr(t_dev), thr.size,
+                                            calculator.metric, ptr(out), ptr(rng), stream(dev)), "confidence_counts")
         self.counts = out.cpu().numpy().reshape(4, thr.size)
         check_unit_range(rng, atol)
 
@@ -326,9 +310,8 @@ def confidence_counts_folds(calculator: SimilarityCalculator, fold_sorted, train
     rows_dev, classes_dev = as_dev(train_rows, np.int32), as_dev(train_classes, np.int32)
     out = torch.zeros(F * 4 * thr.size, dtype=torch.float64, device=dev)
     rng = torch.zeros(2, dtype=torch.int32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.fn_confidence_counts_folds(_ptr(calculator.emb), _ptr(calculator._cls), _ptr(fold_dev), _ptr(rows_dev), _ptr(classes_dev),
-                                              calculator.nrof_classes, E, F, _ptr(t_dev), thr.size, calculator.metric, _ptr(out), _ptr(rng), st),
+    _lib.check(lib.fn_confidence_counts_folds(ptr(calculator.emb), ptr(calculator._cls), ptr(fold_dev), ptr(rows_dev), ptr(classes_dev),
+                                              calculator.nrof_classes, E, F, ptr(t_dev), thr.size, calculator.metric, ptr(out), ptr(rng), stream(dev)),
                "confidence_counts_folds")
     counts = out.cpu().numpy().reshape(F, 4, thr.size)
     check_unit_range(rng, atol)
@@ -555,9 +538,8 @@ class VerificationCurve:
             self._buffer = torch.empty(KEY_WINDOWS * 2 * (KEY_BINS + 2) + 1, dtype=torch.int64, device=dev)
         buf = self._buffer[:words + 1]
         buf.zero_()
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.fn_pair_key_histogram(_ptr(self._emb), _ptr(self._cls), self._classes, self._emb.shape[1], self.metric,
-                                             (ctypes.c_uint32 * R)(*lo), (ctypes.c_int32 * R)(*shift), R, _ptr(buf), _ptr(buf, words), st),
+        _lib.check(lib.fn_pair_key_histogram(ptr(self._emb), ptr(self._cls), self._classes, self._emb.shape[1], self.metric,
+                                             (ctypes.c_uint32 * R)(*lo), (ctypes.c_int32 * R)(*shift), R, ptr(buf), ptr(buf, words), stream(dev)),
                    "pair_key_histogram")
         host = buf.cpu()
         check_unit_range(host[words:].view(torch.int32), self._atol)
@@ -716,11 +698,10 @@ class IdentificationCurve:
     def __init__(self, embeddings, labels, metric=0, device: str = "cuda", atol: float = 1.e-5):
         if metric not in KEY_TOP:
             raise ValueError('Undefined similarity metric {}'.format(metric))
-        labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+        labels = host_array(labels)
         _, inverse, sizes = np.unique(labels, return_inverse=True, return_counts=True)
         n = len(labels)
         self._check(int(np.count_nonzero(sizes[inverse.reshape(-1)] > 1)) if n else 0, n if len(sizes) > 1 else 0)      # no launch
-        from .recognize import Gallery
         gallery = Gallery(embeddings, labels=inverse.reshape(-1).astype(np.int64), metric=metric, device=device)
         found = gallery.mates(gallery.embeddings, gallery.labels, skip=np.arange(n, dtype=np.int32), ranks=True, atol=atol)
         self._init(*(t.cpu().numpy() for t in found), metric)
@@ -758,12 +739,6 @@ class IdentificationCurve:
         self.nrof_nonmated = len(self._sorted)
         self._asked = {}
 
-    @staticmethod
-    def _rank(rank):
-        if isinstance(rank, bool) or not isinstance(rank, (int, np.integer)) or rank < 1:
-            raise ValueError("rank must be an integer of at least 1, got {!r}".format(rank))
-        return int(rank)
-
     def _counts(self, threshold, rank):
         t = np.float32(threshold)
         false_positives = int(np.searchsorted(self._sorted, t, side="left"))                  # #{d < t}
@@ -779,7 +754,7 @@ class IdentificationCurve:
         the mated searches with the mate within ``rank`` and nearer than the threshold; ``fpir``, ``dir`` (the detection and
         identification rate) and ``fnir`` = 1 - dir their shares."""
         from fractions import Fraction
-        rank = self._rank(rank)
+        rank = check_int("rank", rank, 1)
         fpirs = [float(f) for f in np.atleast_1d(np.asarray(fpirs, dtype=np.float64))]
         if any(not 0.0 <= f <= 1.0 for f in fpirs):
             raise ValueError("false-positive identification rates must lie in [0, 1], got {}".format(fpirs))
@@ -797,7 +772,7 @@ class IdentificationCurve:
 
     def dir_at(self, threshold, rank=1):
         """The counts of `fnir_at_fpir` at a threshold of the caller's: a classifier's, or `VerificationCurve.threshold_at_far`."""
-        rank = self._rank(rank)
+        rank = check_int("rank", rank, 1)
         if np.isnan(np.float32(threshold)):
             raise ValueError("threshold must be a number, got NaN")
         return self._counts(threshold, rank)
@@ -805,8 +780,7 @@ class IdentificationCurve:
     def cmc(self, k):
         """-> (curve float64 [k], left_out): curve[r] is the share of mated probes whose first mate has rank <= r, at any depth;
         for k <= 64 it is `statistics.cmc` of the leave-one-out search."""
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
-            raise ValueError("k must be an integer of at least 1, got {!r}".format(k))
+        k = check_int("k", k, 1)
         mated = self.ranks[self.ranks >= 0]
         found = np.cumsum(np.bincount(np.minimum(mated, k), minlength=k + 1)[:k])
         return found / np.float64(self.nrof_mated), self.nrof_probes - self.nrof_mated
@@ -845,7 +819,7 @@ def identification_curve(embeddings, labels, config, device: str = "cuda"):
     if fpirs is None or isinstance(fpirs, Config):        # a Config reads a missing key as an empty Config
         return None
     rank = getattr(config, "fpir_rank", None)
-    rank = 1 if rank is None or isinstance(rank, Config) else IdentificationCurve._rank(rank)
+    rank = 1 if rank is None or isinstance(rank, Config) else check_int("rank", rank, 1)
     fpirs = sorted(float(f) for f in np.atleast_1d(fpirs))
     if any(not 0.0 <= f <= 1.0 for f in fpirs):           # before any launch
         raise ValueError("false-positive identification rates must lie in [0, 1], got {}".format(fpirs))

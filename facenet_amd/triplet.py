@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr
+from ._call import ptr as _ptr, stream
 
 
 def squared_distances(emb: torch.Tensor) -> torch.Tensor:
@@ -14,7 +14,7 @@ def squared_distances(emb: torch.Tensor) -> torch.Tensor:
     e = emb.to(dtype=torch.float32).contiguous()
     n, E = e.shape
     out = torch.empty(n, n, dtype=torch.float32, device=e.device)
-    _lib.check(lib.fn_pairwise_sqdist(_ptr(e), _ptr(e), _ptr(out), None, n, n, E, 2, torch.cuda.current_stream(e.device).cuda_stream),
+    _lib.check(lib.fn_pairwise_sqdist(_ptr(e), _ptr(e), _ptr(out), None, n, n, E, 2, stream(e.device)),
                "pairwise_sqdist")
     return out
 
@@ -34,7 +34,7 @@ def select_triplets(dist: torch.Tensor, labels, alpha: float, nrof_triplets: int
     trip = torch.zeros(nrof_triplets, 3, dtype=torch.int32, device=dist.device)
     info = torch.zeros(8 + 5 * (n * (n - 1) // 2), dtype=torch.int32, device=dist.device)
     _lib.check(lib.fn_select_triplets(_ptr(dist.contiguous()), _ptr(lab), n, float(alpha), nrof_triplets, int(seed) & 0xFFFFFFFF,
-                                      1 if semi_hard else 0, _ptr(trip), _ptr(info), torch.cuda.current_stream(dist.device).cuda_stream),
+                                      1 if semi_hard else 0, _ptr(trip), _ptr(info), stream(dist.device)),
                "select_triplets")
     q, valid, short = info[:3].cpu().tolist()
     if short:
@@ -49,6 +49,6 @@ def triplet_loss(emb: torch.Tensor, alpha: float, with_grad: bool = False):
     T, E = e.shape[0] // 3, e.shape[1]
     loss = torch.zeros(4, dtype=torch.float32, device=e.device)      # word 0 = the loss, words 1-3 = the launch's accumulator
     grad = torch.empty_like(e) if with_grad else None
-    _lib.check(lib.fn_triplet_loss_fwd_bwd(_ptr(e), _ptr(grad) if with_grad else None, _ptr(loss), T, E, float(alpha),
-                                           torch.cuda.current_stream(e.device).cuda_stream), "triplet_loss")
+    _lib.check(lib.fn_triplet_loss_fwd_bwd(_ptr(e), _ptr(grad), _ptr(loss), T, E, float(alpha),
+                                           stream(e.device)), "triplet_loss")
     return (loss[0], grad) if with_grad else loss[0]

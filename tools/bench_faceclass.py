@@ -17,7 +17,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from facenet_amd.apps.train_classifier import ConfusionMatrix, pair_counts  # noqa: E402
 from facenet_amd.config import Config  # noqa: E402
-from facenet_amd.faceclass import ClassifierTrainer, FaceToFaceDistanceClassifier, _as_table, row_norms  # noqa: E402
+from facenet_amd._call import as_table  # noqa: E402
+from facenet_amd.faceclass import ClassifierTrainer, FaceToFaceDistanceClassifier, row_norms  # noqa: E402
 from facenet_amd.facenet import equal_batches_input_pipeline  # noqa: E402
 
 
@@ -74,7 +75,7 @@ def main():
     out["train_step_captured_us"] = round(timed(tr.step, args.steps), 2)
     out["train_step_gflop"] = round(P * K * (P * K - 1) / 2 * 2 * E / 1e9, 3)
 
-    table = _as_table(np.concatenate(embs), model.device)
+    table = as_table(np.concatenate(embs), model.device)
     norms = row_norms(table)
     pair_counts(embs, model, table, norms)
     torch.cuda.synchronize()

@@ -84,9 +84,9 @@ results = []
 for Q in (16, 4096):
     queries = members(centres, Q)
     out = {}
-    paths = {"exhaustive": lambda: out.__setitem__("exhaustive", gallery._search(queries, K, None, 0, None))}
+    paths = {"exhaustive": lambda: out.__setitem__("exhaustive", gallery.search(queries, K, atol=None))}
     for nprobe in NPROBES:
-        paths[f"ivf_nprobe{nprobe}"] = lambda nprobe=nprobe: out.__setitem__(nprobe, index._search(queries, K, None, 0, None, nprobe))
+        paths[f"ivf_nprobe{nprobe}"] = lambda nprobe=nprobe: out.__setitem__(nprobe, index.search(queries, K, nprobe=nprobe, atol=None))
     t, inner = bench(paths, args.reps)
     full = out["exhaustive"][1]
     te = float(np.median(t["exhaustive"]))
