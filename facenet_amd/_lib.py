@@ -144,6 +144,9 @@ _SIGNATURES = {
     "fn_kmeans_update": [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p],
     "fn_ivf_search_workspace": [_i, _i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_ivf_search": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "fn_quantize_rows": [_p, _i, _i, _p, _p, _p, _p, _p],
+    "fn_qgallery_search_workspace": [_i, _i, _i, _i, _i, C.POINTER(C.c_longlong)],
+    "fn_qgallery_search": [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p],
     "fn_mate_search_workspace": [_i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_mate_search": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p],
     "fn_radius_workspace": [_i, _i, _i, C.POINTER(C.c_longlong)],

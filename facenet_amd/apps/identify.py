@@ -7,7 +7,10 @@ and gallery.path (required: the .npz of apps/embeddings.py with the known faces)
 kept per face, 1..64) and at most one of identify.threshold (a number) and identify.classifier (an .npz written by a
 FaceToFaceNormalizedEmbeddingsClassifier's ``save``); with neither every face gets its nearest gallery row's label.
 identify.nlist (``--nlist``; unset: off) searches through an inverted-file index of that many k-means lists (at most one per
-gallery row), built once from the gallery (Gallery.ivf), of which every face probes identify.nprobe (``--nprobe``, default 8).  Every image
+gallery row), built once from the gallery (Gallery.ivf), of which every face probes identify.nprobe (``--nprobe``, default 8).
+identify.quantized (``--quantized``; default off) searches through int8 codes of the gallery (Gallery.quantize, DESIGN.md section
+27) with a shortlist of identify.shortlist rows (``--shortlist``, k..64, default 64); the answers are the exhaustive search's bit
+for bit.  It cannot be combined with identify.nlist.  Every image
 of the data set is read and its faces go to ``file``, one .npz with a row per face: ``files``, ``face``, ``boxes`` int64 [N, 4],
 ``confidence`` float64 [N] as photo_embeddings writes them, ``labels`` int64 [N] (-1: nobody nearer than the threshold),
 ``names`` [N] ('' for -1 or a gallery without names), ``distances`` float32 [N, k] and ``rows`` int32 [N, k] (gallery rows by
@@ -24,7 +27,8 @@ from facenet_amd.apps import photo_embeddings
 from facenet_amd.config import Config, _merge
 
 DEFAULTS = dict(photo_embeddings.DEFAULTS, gallery={"path": None, "metric": 0},
-                identify={"threshold": None, "classifier": None, "k": 1, "nlist": None, "nprobe": None})
+                identify={"threshold": None, "classifier": None, "k": 1, "nlist": None, "nprobe": None, "quantized": False,
+                          "shortlist": None})
 
 
 def load_options(path=None, overrides: dict = None) -> Config:
@@ -56,6 +60,16 @@ def load_options(path=None, overrides: dict = None) -> Config:
             raise ValueError(f"identify.{key} must be an integer of at least 1, got {value!r}")
     if c.identify.nprobe is not None and c.identify.nlist is None:
         raise ValueError("identify.nprobe needs identify.nlist")
+    if not isinstance(c.identify.quantized, bool):
+        raise ValueError(f"identify.quantized must be true or false, got {c.identify.quantized!r}")
+    if c.identify.quantized and c.identify.nlist is not None:
+        raise ValueError("identify.quantized cannot be combined with identify.nlist: quantised inverted-file lists are not built")
+    shortlist = c.identify.shortlist
+    if shortlist is not None:
+        if not c.identify.quantized:
+            raise ValueError("identify.shortlist needs identify.quantized")
+        if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not c.identify.k <= shortlist <= 64:
+            raise ValueError(f"identify.shortlist must be an integer in [identify.k, 64], got {shortlist!r}")
     if c.file:
         c.file = Path(c.file).expanduser()
     else:
@@ -79,6 +93,8 @@ def load_gallery(options):
         gallery = gallery.ivf(min(options.identify.nlist, gallery.nrof_images))
         if options.identify.nprobe is not None:
             gallery.nprobe = options.identify.nprobe
+    if options.identify.quantized:
+        gallery = gallery.quantize(64 if options.identify.shortlist is None else options.identify.shortlist)
     return gallery, threshold
 
 
@@ -132,8 +148,10 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
 @click.option("--config", default=None, type=Path, help="Path to yaml config file with used options for the application.")
 @click.option("--nlist", default=None, type=int, help="Search through an inverted-file index of this many lists (identify.nlist).")
 @click.option("--nprobe", default=None, type=int, help="Lists every face probes (identify.nprobe); needs --nlist or identify.nlist.")
+@click.option("--quantized", is_flag=True, default=None, help="Search through int8 codes of the gallery (identify.quantized).")
+@click.option("--shortlist", default=None, type=int, help="Rows the int8 stage keeps per face (identify.shortlist); needs --quantized.")
 def main(**options):
-    given = {key: options[key] for key in ("nlist", "nprobe") if options[key] is not None}
+    given = {key: options[key] for key in ("nlist", "nprobe", "quantized", "shortlist") if options[key] is not None}
     write_identified(load_options(options["config"], {"identify": given} if given else None))
 
 

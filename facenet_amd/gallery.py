@@ -233,6 +233,13 @@ class Gallery:
         from .ivf import ivf
         return ivf(self, nlist, iters, seed)
 
+    def quantize(self, shortlist=64):
+        """This gallery with int8 codes of its rows -> `quantized.QuantizedGallery`, whose searches take a
+        shortlist of ``shortlist`` rows on the int8 MFMA, rank it exactly and fall back to `search` where that is not provably
+        the exhaustive answer."""
+        from .quantized import quantize
+        return quantize(self, shortlist)
+
     def _label_codes(self):
         """(the gallery's sorted unique labels int64 [C], device int32 [G] dense codes 0 .. C - 1), built once: fn_mate_search
         compares int32 codes, whatever non-negative int64 the labels are."""

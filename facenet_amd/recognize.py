@@ -26,6 +26,9 @@ turns them into FNIR at FPIR.
 ``Gallery.kmeans`` and ``Gallery.ivf`` (`ivf.py`): spherical k-means on the device and the inverted-file
 index it trains; an `ivf.IVFGallery` searches only the lists a query probes, with `search`'s bits.
 
+``Gallery.quantize`` (`quantized.py`): int8 codes of the rows; a `QuantizedGallery` takes a shortlist on the
+int8 MFMA, ranks it with `search`'s bits and runs the queries it cannot certify through `search` itself.
+
 `FacePipeline` is defined here; `Gallery`, its result types and its limits live in `gallery.py`."""
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ import torch
 
 from .detectors.face_detector import image_processing_aligned_batch, image_processing_batch
 from .gallery import DBSCAN_ROUNDS, MAX_EDGES, MAX_K, MAX_LENGTH, Clustering, Gallery, MateSearch, check_edges      # noqa: F401
+from .quantized import QuantizedGallery      # noqa: F401
 
 BATCH_SIZES = (1, 4, 16, 64, 256)
 

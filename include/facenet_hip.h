@@ -421,6 +421,37 @@ int fn_ivf_search(const float* queries, int Q, const float* lists, const int32_t
                   const int32_t* probes, int nprobe, int k, int metric, const int32_t* skip, void* workspace, float* dist,
                   int32_t* rows, int32_t* range, void* stream);
 
+/* ---- the quantised gallery: an int8 shortlist, the exact re-rank of it and a certificate ---------------------
+ * fn_quantize_rows: rows fp32 [N, E] (E a multiple of 4 in [4, 512]) -> codes int8 [N, Ep], Ep = E rounded up to a multiple of 64,
+ * the padding zero; scale, rho, norm fp32 [N].  Per row x: m = max |x_e|; codes[e] = rint((double) x_e * 127.0 / (double) m) in
+ * fp64, half to even (|code| <= 127); scale = (float)((double) m / 127.0); m = 0 gives codes and scale 0.  rho = ||x - scale c||:
+ * the sequential fp64 sum from 0.0 over ascending e of t * t, t = (double) x_e - (double) scale * c_e, every product rounded
+ * before it is used (no fused multiply-add), the IEEE square root, stored as the smallest float not below it; norm = ||x|| the
+ * same way.  rows and codes 16-byte aligned.
+ *
+ * fn_qgallery_search: the k nearest of G gallery rows through a shortlist of R = shortlist rows, k <= R <= 64.  queries, gallery,
+ * E, metric, skip, slab_rows and the alignment rule: as fn_gallery_search; qcodes / qscale / qrho / qnorm and gcodes / gscale: what
+ * fn_quantize_rows gave for the two tables (code tables 16-byte aligned); rho_max, norm_max: the maxima of the gallery's rho and
+ * norm.  Stage one (v_mfma_i32_16x16x64_i8): idot = the int32 dot product of two code rows, s^ = (qscale gscale) (float) idot
+ * (two fp32 products in that association), key = bits(2 (1 - clip(s^))) << 32 | row; the shortlist is the R smallest keys,
+ * ascending, skip[q] left out; shortlist_keys uint64 [Q, R] or NULL receives it, all ones behind its length.  Stage two: the
+ * rows of the shortlist are ranked by fn_gallery_search's own key (the fp32 chain on queries and gallery) and cut to k: dist fp32
+ * [Q, k], rows int32 [Q, k], row -1 and dist +inf in the tail.  certified int32 [Q]: 1 when the shortlist is not full, or when,
+ * in fp64 and in this order, with u = 2^-24, g = E u / (1 - E u), B = qrho norm_max + (qnorm + qrho) rho_max + g qnorm norm_max
+ * + 4 u:  (qnorm + qrho) (norm_max + rho_max) <= 1.05  and  d0_k < d~_R - 2 B - 8 u  (d0_k the k-th distance of stage two for
+ * metric 0, d~_R the R-th of stage one).  A certified query's dist and rows are fn_gallery_search's bit for bit; any other query's
+ * are the best k of its shortlist.  range (2 words or NULL): ordered-int min/max of the chain values s of the pairs re-ranked,
+ * NOT of all Q x G pairs.  workspace: at least the bytes fn_qgallery_search_workspace reports for the same Q, G, k, shortlist and
+ * slab_rows.  The result depends neither on slab_rows nor on scheduling.  The caller owns every buffer; no call here allocates or
+ * synchronises. */
+int fn_quantize_rows(const float* rows, int N, int E, int8_t* codes, float* scale, float* rho, float* norm, void* stream);
+int fn_qgallery_search_workspace(int Q, int G, int k, int shortlist, int slab_rows, long long* bytes);
+int fn_qgallery_search(const float* queries, int Q, const float* gallery, int G, const int8_t* qcodes, const float* qscale,
+                       const int8_t* gcodes, const float* gscale, const float* qrho, const float* qnorm, double rho_max,
+                       double norm_max, int E, int k, int shortlist, int metric, const int32_t* skip, int slab_rows, void* workspace,
+                       float* dist, int32_t* rows, int32_t* certified, unsigned long long* shortlist_keys, int32_t* range,
+                       void* stream);
+
 /* ---- open-set 1:N evaluation: per probe its nearest mate, its nearest impostor and the rank of that mate;
  * the [Q, G] matrix never reaches memory.  s, sc, d0 = 2 (1 - sc) and the key bits(d0) << 32 | row are those of fn_gallery_search,
  * fn_radius_*, fn_confidence_counts* and fn_pair_key_histogram bit for bit.  queries, gallery, E, metric, skip, slab_rows and the
