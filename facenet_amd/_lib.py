@@ -139,6 +139,7 @@ _SIGNATURES = {
     "fn_confidence_counts": [_p, _p, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_confidence_counts_folds": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_pair_key_histogram": [_p, _p, _i, _i, _i, C.POINTER(_u), C.POINTER(C.c_int32), _i, _p, _p, _p],
+    "fn_false_pairs": [_p, _p, _i, _i, _i, _f, _i, _i, _p, C.c_longlong, _p, _p, _p],
     "fn_gallery_search_workspace": [_i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_gallery_search": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
     "fn_kmeans_update": [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p],

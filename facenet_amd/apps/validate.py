@@ -25,7 +25,10 @@ DEFAULTS = {   # apps/configs/validate.yaml of the reference
     "model": {"path": None},
     # validate.far_targets (not set here: absent means None): a list of false-accept rates; the exact VerificationCurve at these
     # rates is appended to the report.  validate.fpir_targets (likewise absent): a list of false-positive
-    # identification rates, and validate.fpir_rank (default 1); the open-set IdentificationCurve at these rates follows (section 24)
+    # identification rates, and validate.fpir_rank (default 1); the open-set IdentificationCurve at these rates follows (section 24).
+    # validate.false_examples (likewise absent): {threshold: null, max_fneg: 10, max_fpos: 2, fpos_dir: null, fneg_dir: null}; the
+    # worst pairs at the threshold (null: the mean of the folds' max-accuracy thresholds) are listed in the report and written as
+    # pictures into the directories (null: false_positives and false_negatives next to the report) (section 28)
     "validate": {"nrof_folds": 10, "metric": 0, "far_target": 0.001},
     "file": None,
 }
@@ -56,12 +59,12 @@ def load_options(path=None, overrides: dict = None) -> Config:
 def validate(options, log=print):
     """Returns the FaceToFaceValidation; ``options`` as ``load_options`` builds them.  ``report.curve`` is the VerificationCurve
     that ``validate.far_targets`` asks for and ``report.identification`` the IdentificationCurve that ``validate.fpir_targets`` asks
-    for, each None without its key."""
+    for, each None without its key; ``report.false_examples`` likewise the FalseExamples of ``validate.false_examples``."""
     from facenet_amd import dataset
     from facenet_amd.api import FaceNet
     from facenet_amd.apps.train_classifier import write_text_log
     from facenet_amd.facenet import evaluate_embeddings
-    from facenet_amd.statistics import FaceToFaceValidation, identification_curve, verification_curve
+    from facenet_amd.statistics import FaceToFaceValidation, false_examples, identification_curve, verification_curve
 
     start = time.monotonic()
     options.file.parent.mkdir(parents=True, exist_ok=True)
@@ -90,6 +93,15 @@ def validate(options, log=print):
     if report.identification is not None:
         write_text_log(options.file, report.identification)
         log(report.identification)
+    # rows are in the database's order, so row i is dbase.files[i]
+    threshold = float(np.mean([m.threshold for m in report.reports[0].conf_matrix_test]))
+    report.false_examples = false_examples(embeddings, labels, dbase.files, options.validate, threshold)
+    if report.false_examples is not None:
+        write_text_log(options.file, report.false_examples)
+        log(report.false_examples)
+        asked = options.validate.false_examples
+        report.false_examples.write_false_pairs(asked.fpos_dir or options.file.parent / "false_positives",
+                                                asked.fneg_dir or options.file.parent / "false_negatives")
 
     with options.file.open("at") as f:
         f.write("elapsed time: {:.3f}\n".format(time.monotonic() - start))

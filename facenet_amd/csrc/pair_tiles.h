@@ -11,8 +11,8 @@
 // evaluated, and keeps its initial words (which decode to hi < lo) when it evaluated none.
 //
 // Which pairs are evaluated is defined here too: the gallery walk (identify.hip, ivf.hip, opensearch.hip, cluster.hip) and the class-pair
-// walk (validation.hip's confidence_folds_kernel, verification.hip's pair_key_histogram_kernel; confidence_kernel keeps its own
-// scalar walk: it is the independent reference of the exactness tests).
+// walk (validation.hip's confidence_folds_kernel, verification.hip's pair_key_histogram_kernel, false_pairs.hip's
+// false_pairs_kernel; confidence_kernel keeps its own scalar walk: it is the independent reference of the exactness tests).
 //
 // A new consumer of the gallery walk supplies a prologue (its per-row state) and on_tile(c0, acc), the epilogue of one super-tile.
 // A new consumer of the class-pair walk supplies what it does with a valid pair's dot product, inside the loops that section shows.

@@ -826,3 +826,7 @@ def identification_curve(embeddings, labels, config, device: str = "cuda"):
     curve = IdentificationCurve(embeddings, labels, metric=config.metric, device=device)
     curve.fnir_at_fpir(fpirs, rank=rank)
     return curve
+
+
+# Which pairs a threshold gets wrong: a module of its own, on SimilarityCalculator
+from .false_examples import FalseExamples, false_examples      # noqa: E402, F401

@@ -378,6 +378,22 @@ int fn_confidence_counts_folds(const float* emb, const int32_t* cls_start, const
 int fn_pair_key_histogram(const float* emb, const int32_t* cls_start, int C, int E, int metric, const uint32_t* lo,
                           const int32_t* shift, int R, unsigned long long* out, int32_t* range, void* stream);
 
+/* ---- false examples: the worst pairs at a threshold, picked greedily as facenet/statistics.py:334-421 does.
+ * emb, cls_start, C, E, metric and range: as fn_pair_key_histogram; d is the same distance, bit for bit; no class may have more
+ * than 65536 rows (the tie-break position is two 16-bit row numbers; the caller checks it).  False negatives, per class: the pair
+ * (i < k) of not yet excluded rows with the largest d, ties to the smallest i, then k; emitted when d > threshold (strict fp32),
+ * and both rows are excluded from the class's further picks; at most max_fneg picks.  False positives, per pair of classes a < b:
+ * the pair (i in a, k in b) with row i and column k not yet excluded and the smallest d, ties to the smallest i, then k; emitted
+ * when d < threshold, and row i and column k are excluded; at most max_fpos picks.  0 <= max_fneg, max_fpos <= 64.
+ * count uint64 [2], zeroed by the caller: [0] the false negatives, [1] the false positives found, whatever the capacity.
+ * records int32 [capacity][4], 16-byte aligned (NULL with capacity 0): {row1, row2, bits of d, pick index within its class (pair)},
+ * rows of the sorted table, row1 < row2 (the lower class's row first).  False negative number s (in arrival order, which is not
+ * deterministic) is records[s], false positive number s is records[capacity - 1 - s]; one beyond the capacity is counted and not
+ * written, so the records are complete exactly when count[0] + count[1] <= capacity.  The call allocates nothing and does not
+ * synchronise. */
+int fn_false_pairs(const float* emb, const int32_t* cls_start, int C, int E, int metric, float threshold, int max_fneg, int max_fpos,
+                   int32_t* records, long long capacity, unsigned long long* count, int32_t* range, void* stream);
+
 /* ---- 1:N identification: for each of Q query rows the k nearest of G gallery rows; the [Q, G] distance
  * matrix never reaches memory.  s(q, g) is the same fp32 fmaf chain as fn_confidence_counts (exact fp32 MFMA), sc = s clipped to
  * [-1, 1]; rows are ranked by ascending (2 (1 - sc), gallery row) for both metrics, equal distances going to the lower row; dist
