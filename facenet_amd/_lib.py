@@ -142,6 +142,8 @@ _SIGNATURES = {
     "fn_false_pairs": [_p, _p, _i, _i, _i, _f, _i, _i, _p, C.c_longlong, _p, _p, _p],
     "fn_gallery_search_workspace": [_i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_gallery_search": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    "fn_gallery_candidates_workspace": [_i, _i, _i, _i, C.POINTER(C.c_longlong)],
+    "fn_gallery_candidates": [_p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p],
     "fn_kmeans_update": [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p],
     "fn_ivf_search_workspace": [_i, _i, _i, _i, _i, C.POINTER(C.c_longlong)],
     "fn_ivf_search": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p],

@@ -10,7 +10,13 @@ identify.nlist (``--nlist``; unset: off) searches through an inverted-file index
 gallery row), built once from the gallery (Gallery.ivf), of which every face probes identify.nprobe (``--nprobe``, default 8).
 identify.quantized (``--quantized``; default off) searches through int8 codes of the gallery (Gallery.quantize, DESIGN.md section
 27) with a shortlist of identify.shortlist rows (``--shortlist``, k..64, default 64); the answers are the exhaustive search's bit
-for bit.  It cannot be combined with identify.nlist.  Every image
+for bit.  It cannot be combined with identify.nlist.  identify.templates (``--templates``; default off) searches one template
+per identity, the normalised mean of its gallery rows (Gallery.templates), instead of the rows: ``rows`` are
+then rows of the template gallery, one per label in ascending label order.  It cannot be combined with identify.nlist or
+identify.quantized.  identify.candidates (``--candidates``, 1..64; unset: off) adds every face's candidate list of that many
+distinct identities (Gallery.candidates): ``candidate_labels`` int64 [N, c], ``candidate_distances`` float32 [N, c] and
+``candidate_rows`` int32 [N, c] (each identity's nearest gallery row; -1 / inf / -1 where the gallery has fewer identities), which
+needs the exhaustive search and so cannot be combined with identify.nlist either.  Every image
 of the data set is read and its faces go to ``file``, one .npz with a row per face: ``files``, ``face``, ``boxes`` int64 [N, 4],
 ``confidence`` float64 [N] as photo_embeddings writes them, ``labels`` int64 [N] (-1: nobody nearer than the threshold),
 ``names`` [N] ('' for -1 or a gallery without names), ``distances`` float32 [N, k] and ``rows`` int32 [N, k] (gallery rows by
@@ -28,7 +34,7 @@ from facenet_amd.config import Config, _merge
 
 DEFAULTS = dict(photo_embeddings.DEFAULTS, gallery={"path": None, "metric": 0},
                 identify={"threshold": None, "classifier": None, "k": 1, "nlist": None, "nprobe": None, "quantized": False,
-                          "shortlist": None})
+                          "shortlist": None, "candidates": None, "templates": False})
 
 
 def load_options(path=None, overrides: dict = None) -> Config:
@@ -70,6 +76,16 @@ def load_options(path=None, overrides: dict = None) -> Config:
             raise ValueError("identify.shortlist needs identify.quantized")
         if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not c.identify.k <= shortlist <= 64:
             raise ValueError(f"identify.shortlist must be an integer in [identify.k, 64], got {shortlist!r}")
+    candidates = c.identify.candidates
+    if candidates is not None and (isinstance(candidates, bool) or not isinstance(candidates, int) or not 1 <= candidates <= 64):
+        raise ValueError(f"identify.candidates must be an integer in [1, 64], got {candidates!r}")
+    if candidates is not None and c.identify.nlist is not None:
+        raise ValueError("identify.candidates cannot be combined with identify.nlist: candidate lists need the exhaustive search")
+    if not isinstance(c.identify.templates, bool):
+        raise ValueError(f"identify.templates must be true or false, got {c.identify.templates!r}")
+    if c.identify.templates and (c.identify.nlist is not None or c.identify.quantized):
+        raise ValueError("identify.templates cannot be combined with identify.nlist or identify.quantized: "
+                         "the templates are searched exhaustively in fp32")
     if c.file:
         c.file = Path(c.file).expanduser()
     else:
@@ -89,6 +105,8 @@ def load_gallery(options):
     if options.identify.classifier is not None:
         classifier = FaceToFaceNormalizedEmbeddingsClassifier().load(options.identify.classifier)
     threshold = gallery.threshold_of(options.identify.threshold, classifier)
+    if options.identify.templates:
+        gallery = gallery.templates()
     if options.identify.nlist is not None:
         gallery = gallery.ivf(min(options.identify.nlist, gallery.nrof_images))
         if options.identify.nprobe is not None:
@@ -108,7 +126,8 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
     if gallery is None:
         gallery, threshold = load_gallery(options)
     log(gallery)
-    k = options.identify.k
+    k, nc = options.identify.k, options.identify.candidates
+    candidates = {"candidate_labels": [], "candidate_distances": [], "candidate_rows": []}
     files, face, boxes, confidence, labels, names, distances, rows, unread = [], [], [], [], [], [], [], [], 0
     for path in dbase.files:
         try:
@@ -121,6 +140,11 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
             continue
         emb = pipeline.embed_device(crops)
         dist, near = (t.cpu().numpy() for t in gallery.search(emb, k=k))
+        if nc is not None:
+            cdist, crows, clabels = (t.cpu().numpy() for t in gallery.candidates(emb, k=nc))
+            candidates["candidate_labels"].append(clabels)
+            candidates["candidate_distances"].append(cdist)
+            candidates["candidate_rows"].append(crows)
         for n, box in enumerate(found):
             label, name, _, _ = gallery.who(dist[n, 0], near[n, 0], threshold)
             name = "" if name is None else str(name)
@@ -133,11 +157,15 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
             distances.append(dist[n])
             rows.append(near[n])
             log(f"{path} face {n}: {name or label} distance {dist[n, 0]:.6f} gallery row {near[n, 0]}")
+    extra = {}
+    if nc is not None:
+        for (name, parts), dtype in zip(candidates.items(), (np.int64, np.float32, np.int32)):
+            extra[name] = np.concatenate(parts + [np.empty((0, nc), dtype=dtype)]).astype(dtype)
     options.file.parent.mkdir(parents=True, exist_ok=True)
     np.savez(options.file, files=np.asarray(files, dtype=str), face=np.asarray(face, dtype=np.int64),
              boxes=np.asarray(boxes, dtype=np.int64).reshape(-1, 4), confidence=np.asarray(confidence, dtype=np.float64),
              labels=np.asarray(labels, dtype=np.int64), names=np.asarray(names, dtype=str),
-             distances=np.asarray(distances, dtype=np.float32).reshape(-1, k), rows=np.asarray(rows, dtype=np.int32).reshape(-1, k))
+             distances=np.asarray(distances, dtype=np.float32).reshape(-1, k), rows=np.asarray(rows, dtype=np.int32).reshape(-1, k), **extra)
     log('Number of files that cannot be read', unread)
     log(f"output file: {options.file}")
     log(f"number of faces: {len(files)} in {dbase.nrof_images} images")
@@ -150,8 +178,10 @@ def write_identified(options, pipeline=None, gallery=None, threshold=None, log=p
 @click.option("--nprobe", default=None, type=int, help="Lists every face probes (identify.nprobe); needs --nlist or identify.nlist.")
 @click.option("--quantized", is_flag=True, default=None, help="Search through int8 codes of the gallery (identify.quantized).")
 @click.option("--shortlist", default=None, type=int, help="Rows the int8 stage keeps per face (identify.shortlist); needs --quantized.")
+@click.option("--candidates", default=None, type=int, help="Distinct identities listed per face (identify.candidates), 1..64.")
+@click.option("--templates", is_flag=True, default=None, help="Search one mean template per identity (identify.templates).")
 def main(**options):
-    given = {key: options[key] for key in ("nlist", "nprobe", "quantized", "shortlist") if options[key] is not None}
+    given = {key: options[key] for key in ("nlist", "nprobe", "quantized", "shortlist", "candidates", "templates") if options[key] is not None}
     write_identified(load_options(options["config"], {"identify": given} if given else None))
 
 

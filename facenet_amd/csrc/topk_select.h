@@ -90,18 +90,27 @@ __device__ __forceinline__ void id_select_tile(int c0, f32x4 (&acc)[4], int g1, 
     }
 }
 
+// What cuts a list in id_emit and id_merge: cut(list, n, k, thr, lane) -> the new length, id_prune's contract.  IdCutSmallest,
+// their default, is id_prune itself; candidates.hip passes the cut that keeps one key per label.
+struct IdCutSmallest {
+    __device__ __forceinline__ int operator()(u64* __restrict__ list, int n, int k, u64* __restrict__ thr, int lane) const {
+        return id_prune(list, n, k, thr, lane);
+    }
+};
+
 // After the walk (and a workgroup barrier): list `row`, cut to its k smallest, goes out ascending as out[0 .. k), all ones
 // behind its length.  Called by the whole wave that owns the row.
+template <typename Cut = IdCutSmallest>
 __device__ __forceinline__ void id_emit(u64* __restrict__ sList, u64* __restrict__ sThr, const int* __restrict__ sCnt, int row, int cap, int k, int lane,
-                                        u64* __restrict__ out) {
-    const int n = id_prune(sList + row * cap, sCnt[row], k, &sThr[row], lane);
+                                        u64* __restrict__ out, Cut cut = Cut()) {
+    const int n = cut(sList + row * cap, sCnt[row], k, &sThr[row], lane);
     if (lane < k) out[lane] = lane < n ? sList[row * cap + lane] : INONE;
 }
 
 // One wave cuts `total` keys, key_at(0 .. total) (all ones: none), to the k smallest: ascending in sList [IMERGE_CAP] (LDS),
 // sThr one LDS word.  Returns their number.
-template <typename KeyAt>
-__device__ __forceinline__ int id_merge(u64* __restrict__ sList, u64* __restrict__ sThr, long total, int k, int lane, KeyAt key_at) {
+template <typename KeyAt, typename Cut = IdCutSmallest>
+__device__ __forceinline__ int id_merge(u64* __restrict__ sList, u64* __restrict__ sThr, long total, int k, int lane, KeyAt key_at, Cut cut = Cut()) {
     if (lane == 0) *sThr = INONE;
     __builtin_amdgcn_wave_barrier();
     int n = 0;
@@ -114,9 +123,9 @@ __device__ __forceinline__ int id_merge(u64* __restrict__ sList, u64* __restrict
         if (keep) sList[n + __popcll(m & ((1ull << lane) - 1ull))] = key;
         n += __popcll(m);
         __builtin_amdgcn_wave_barrier();
-        if (n > IMERGE_CAP - 64) n = id_prune(sList, n, k, sThr, lane);
+        if (n > IMERGE_CAP - 64) n = cut(sList, n, k, sThr, lane);
     }
-    return id_prune(sList, n, k, sThr, lane);
+    return cut(sList, n, k, sThr, lane);
 }
 
 }  // namespace fn

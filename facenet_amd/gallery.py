@@ -1,6 +1,6 @@
 """The known faces on the device and every search over them (the map of the stack: `recognize.py`).  `Gallery._run` is the one
-path from a set of queries to a launched fn_* search; ``search``, ``mates`` and ``within`` are argument
-checks, one call of it and the shaping of its result, and `ivf.IVFGallery` overrides the launch of ``search`` alone."""
+path from a set of queries to a launched fn_* search; ``search``, ``candidates``, ``mates`` and ``within``
+are argument checks, one call of it and the shaping of its result, and `ivf.IVFGallery` overrides the launch of ``search`` alone."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -220,6 +220,77 @@ class Gallery:
     def leave_one_out(self, k=1):
         """Every gallery row's k nearest OTHER rows, device tensors: ``search(gallery, k, skip=arange(G))``."""
         return self.search(self.embeddings, k, skip=np.arange(self.nrof_images, dtype=np.int32))
+
+    def _candidates(self, queries, k, skip=None, slab_rows=0, atol=1.e-5):
+        """-> device (dist [Q, k], rows [Q, k]) after every check of `candidates`: the launch of fn_gallery_candidates."""
+        k, G, slab_rows = check_k(k), self.nrof_images, int(slab_rows)
+
+        def launch(c, dist, rows):
+            _lib.check(c.lib.fn_gallery_candidates(ptr(c.queries), c.Q, ptr(self.embeddings), G, ptr(self._label_codes()[1]), self.length, k,
+                                                   self.metric, ptr(c.skip), slab_rows, ptr(c.workspace), ptr(dist), ptr(rows), ptr(c.range),
+                                                   c.stream), "gallery_candidates")
+
+        return self._run("Gallery.candidates runs fn_gallery_candidates", queries, skip, atol, lambda Q: self._nearest(Q, k),
+                         "gallery_candidates_workspace", lambda Q: (Q, G, k, slab_rows), launch)
+
+    def candidates(self, queries, k=1, skip=None, slab_rows=0, atol=1.e-5):
+        """The candidate list of every query row: its k nearest IDENTITIES (distinct labels), each through its nearest gallery row
+        (DESIGN.md section 29) -> (dist float32 [Q, k], rows int32 [Q, k], labels int64 [Q, k]), ascending by (distance, row);
+        NumPy in gives NumPy out, a device tensor in gives device tensors out.  ``rows[q, j]`` is the nearest row of the j-th
+        identity (equal distances go to the lower row), ``dist`` its distance, `search`'s bit for bit, and ``labels`` its label,
+        looked up on the host from the rows.  Column 0 is `search`'s.  A query with fewer than k admissible identities gets row
+        -1, distance +inf and label -1 in the tail.  ``k`` in [1, 64] counts identities however many rows each has, which
+        `search` cannot promise at any k.  ``skip``, ``slab_rows``, ``atol`` and the ValueError for unnormalised embeddings: as
+        `search`.  ``statistics.cmc(labels, rows)`` of these rows is the identity-level cumulative match curve: a mate at column
+        j has j impostor identities in front of it, not j impostor rows."""
+        dist, rows = self._candidates(queries, k, skip, slab_rows, atol)
+        found = rows.cpu().numpy()
+        labels = np.where(found >= 0, self.labels[np.maximum(found, 0)], -1).astype(np.int64)
+        if torch.is_tensor(queries):
+            return dist, rows, torch.from_numpy(labels).to(rows.device)
+        return dist.cpu().numpy(), found, labels
+
+    def leave_one_out_candidates(self, k=1):
+        """Every gallery row's k nearest identities among all OTHER rows, device tensors: ``candidates(gallery, k,
+        skip=arange(G))``.  A probe's own identity is a candidate whenever it has another row, so ``statistics.cmc(labels,
+        rows)`` of the rows returned is the identity-level cumulative match curve of the gallery."""
+        return self.candidates(self.embeddings, k, skip=np.arange(self.nrof_images, dtype=np.int32))
+
+    def identify_candidates(self, queries, k, threshold=None, classifier=None):
+        """-> for every query row the list of (label, name, distance, row) of its candidates (`candidates`, `who`), nearest first:
+        at most k distinct identities.  Open set (``threshold`` or ``classifier``, as `identify`): the list stops at the first
+        candidate that fails ``distance < threshold`` (strict, fp32), so it may be empty.  Closed set: every identity found."""
+        thr = self.threshold_of(threshold, classifier)
+        dist, rows = (t.cpu().numpy() for t in self._candidates(queries, k))
+        out = []
+        for d, r in zip(dist, rows):
+            n = int((r >= 0).sum())                            # (the tail is behind every candidate)
+            if thr is not None:
+                n = min(n, int(np.argmin(np.append(d[:n] < thr, False))))
+            out.append([self.who(d[j], r[j], thr) for j in range(n)])
+        return out
+
+    def templates(self):
+        """One template per identity -> a new `Gallery` with one row per label, in ascending label order: the L2-normalised mean
+        of that label's rows, from one launch of fn_kmeans_update (sequential fp64 sums in ascending row order, one rounding to
+        fp32: reproducible bit for bit).  Its labels are the sorted unique labels, so its searches answer in identities; names
+        and the metric carry over, ``files`` is None.  Raises a ValueError naming the label when a label's rows sum to zero: such
+        an identity has no direction."""
+        dev, E = self.device, self.length
+        if dev.type != "cuda":
+            raise _lib.FacenetHipError("Gallery.templates runs fn_kmeans_update on the GPU; facenet_amd has no CPU fallback")
+        uniq = self._label_codes()[0]
+        codes = np.searchsorted(uniq, self.labels)
+        order = torch.from_numpy(np.argsort(codes, kind="stable").astype(np.int32)).to(dev)          # by (label, row)
+        list_start = torch.from_numpy(np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=len(uniq)))]).astype(np.int32)).to(dev)
+        prev = torch.zeros((len(uniq), E), dtype=torch.float32, device=dev)
+        means = torch.empty_like(prev)
+        kept = torch.empty(len(uniq), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().fn_kmeans_update(ptr(self.embeddings), self.nrof_images, E, ptr(order), ptr(list_start), len(uniq), ptr(prev), ptr(means), ptr(kept), stream(dev)), "kmeans_update")
+        flat = np.nonzero(kept.cpu().numpy())[0]
+        if len(flat):
+            raise ValueError(f"the rows of label {int(uniq[flat[0]])} sum to zero: that identity has no template")
+        return Gallery(means, labels=uniq, names=self.names, metric=self.metric, device=dev)
 
     def kmeans(self, nlist, iters=10, seed=0):
         """Spherical k-means of the gallery's rows into ``nlist`` groups on the device -> (centroids fp32

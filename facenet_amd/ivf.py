@@ -190,6 +190,7 @@ class IVFGallery(Gallery):
         raise NotImplementedError("an IVFGallery answers search, leave_one_out and identify; run this on the Gallery it was built from")
 
     mates = leave_one_out_mates = within = neighbours = cluster = kmeans = ivf = _not_indexed
+    candidates = leave_one_out_candidates = identify_candidates = templates = _not_indexed      # (they walk the rows in gallery order)
 
 
 def ivf(gallery, nlist, iters=10, seed=0, nprobe=8):

@@ -116,6 +116,14 @@ class FacePipeline:
             return []
         return list(zip(boxes, gallery.identify(self.embed_device(crops), **kw)))
 
+    def identify_candidates(self, image, gallery, **kw):
+        """-> list of (BoundingBox, [(label, name, distance, row), ...]) through `gallery.identify_candidates(embeddings, **kw)`:
+        every face's candidate list of identities.  [] without a network or search launch when nothing was detected."""
+        boxes, crops = self.crops(image)
+        if len(boxes) == 0:
+            return []
+        return list(zip(boxes, gallery.identify_candidates(self.embed_device(crops), **kw)))
+
     def cluster(self, images, metric=0, **kw):
         """Detect, crop and embed the faces of a list of photographs, then `Gallery.cluster(**kw)` them; the embeddings never
         visit the host.  -> (Clustering, faces): faces[row] = (image index, face index within the image, BoundingBox).  Without a

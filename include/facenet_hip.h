@@ -487,6 +487,24 @@ int fn_mate_search(const float* queries, int Q, const int32_t* query_labels, con
                    const int32_t* gallery_labels, int E, int metric, const int32_t* skip, int slab_rows, void* workspace,
                    float* dist, int32_t* rows, int32_t* rank, int32_t* range, void* stream);
 
+/* ---- candidate lists of identities: per query the k nearest DISTINCT labels, each through its nearest row;
+ * the [Q, G] matrix never reaches memory.  s, sc, d0 = 2 (1 - sc) and the key bits(d0) << 32 | row are those of fn_gallery_search
+ * bit for bit.  queries, gallery, E, metric, skip, slab_rows and the alignment rule: as fn_gallery_search.  gallery_labels int32
+ * [G] (>= 0) must be given; the caller guarantees the range.  Gallery row g is admissible for query q when g != skip[q].  For a
+ * label c, best(q, c) is the smallest key over the admissible rows with gallery_labels[g] == c.  The result for q is the k labels
+ * with the smallest best, ascending by best: rows int32 [Q, k] holds the row in that key (the identity's nearest row, equal
+ * distances going to the lower row), dist fp32 [Q, k] that row's distance in the gallery's metric (2 (1 - sc) for metric 0,
+ * acosf(sc) of the recomputed chain for metric 1).  A query with fewer than k admissible identities gets row -1 and dist +inf in
+ * the tail.  1 <= k <= 64.  range (2 words or NULL): ordered-int min/max of s over all Q x G pairs, skipped pairs included.
+ * workspace: at least the bytes fn_gallery_candidates_workspace reports for the same Q, G, k and slab_rows: slabs x lists x Q x k
+ * 8-byte keys, slabs = ceil(G / slab_rows rounded up to a multiple of 64), lists = 4 for Q <= 16 and 1 otherwise.  The result
+ * depends neither on slab_rows nor on scheduling.  The caller owns every buffer; the call allocates nothing and does not
+ * synchronise. */
+int fn_gallery_candidates_workspace(int Q, int G, int k, int slab_rows, long long* bytes);
+int fn_gallery_candidates(const float* queries, int Q, const float* gallery, int G, const int32_t* gallery_labels, int E, int k,
+                          int metric, const int32_t* skip, int slab_rows, void* workspace, float* dist, int32_t* rows, int32_t* range,
+                          void* stream);
+
 /* ---- face clustering ------------------------------------------------------------------------------------
  * Radius search: every (query, gallery row) pair with d < eps as a CSR; the [Q, G] matrix never reaches memory.  s, sc and d
  * (2 (1 - sc) for metric 0, acosf(sc) for metric 1) are those of fn_gallery_search and fn_confidence_counts bit for bit, and the
