@@ -158,6 +158,9 @@ _SIGNATURES = {
     "fn_dbscan_init": [_i, _p, _i, _p, _p, _p, _p],
     "fn_dbscan_rounds": [_i, _p, _p, _p, _p, _p, _i, _p],
     "fn_dbscan_finish": [_i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p],
+    "fn_mst_workspace": [_i, _i, C.POINTER(C.c_longlong)],
+    "fn_mst_init": [_i, _p, _p, _p],
+    "fn_mst_rounds": [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p],
     "fn_softmax_xent_fwd_bwd": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _f, _i, _p],
     "fn_margin_weight_rnorm": [_p, _i, _i, _f, _p, _p],
     "fn_margin_softmax_fwd_bwd": [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _f, _f, _f, _f, _i, _p],

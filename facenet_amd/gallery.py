@@ -13,6 +13,7 @@ import torch
 from . import _lib
 from ._call import as_table, check_int, check_unit_range, host_array, ptr, stream, workspace
 from .faceclass import FaceToFaceNormalizedEmbeddingsClassifier
+from .hierarchy import MAX_MIN_SAMPLES, SpanningTree
 
 MAX_K = 64                # fn_gallery_search: 1 <= k <= 64
 MAX_LENGTH = 512          # ... and embedding length a multiple of 4 up to 512
@@ -463,3 +464,46 @@ class Gallery:
         _, rounds, clusters, noise = info.cpu().tolist()[:4]
         return Clustering(labels.cpu().numpy().astype(np.int64), core.cpu().numpy().astype(bool), clusters, noise, rounds, float(eps),
                           min_samples, offsets, rows, dist)
+
+    def spanning_tree(self, min_samples=1, slab_rows=0):
+        """The minimum spanning tree of the gallery's rows under the mutual-reachability distance w(i, j) = max(d(i, j), core[i],
+        core[j]) -> `hierarchy.SpanningTree`, built on the device by Boruvka's algorithm (fn_mst_*): at
+        most ceil(log2 N) walks of all pairs, and the [N, N] matrix never reaches memory.  ``core[i]`` is the distance to the
+        (min_samples - 1)-th nearest OTHER row (`leave_one_out`, the same bits), 0 for ``min_samples=1``, which makes the tree
+        single linkage's.  The tree is the unique one under the edge order (bits(w), lo, hi): it depends neither on ``slab_rows``
+        (fn_mst_rounds', 0: chosen by the library) nor on scheduling.  Metric 0 only."""
+        N = self.nrof_images
+        min_samples = check_int("min_samples", min_samples, 1, min(MAX_MIN_SAMPLES, N), note=" (at most the number of rows)")
+        if self.metric != 0:
+            raise ValueError("a spanning tree needs metric 0, whose distances are pinned bit for bit; this gallery reports metric {}".format(self.metric))
+        dev, slab_rows = self.device, int(slab_rows)
+        if dev.type != "cuda":
+            raise _lib.FacenetHipError("Gallery.spanning_tree runs fn_mst_rounds on the GPU; facenet_amd has no CPU fallback")
+        core = None
+        if min_samples > 1:
+            core = self.leave_one_out(min_samples - 1)[0][:, min_samples - 2].contiguous()
+        lib, st = _lib.load(), stream(dev)
+        work = workspace(dev, lib.fn_mst_workspace, "mst_workspace", N, slab_rows)
+        comp = torch.empty(N, dtype=torch.int32, device=dev)
+        edges = torch.empty((max(N - 1, 1), 2), dtype=torch.int32, device=dev)
+        weights = torch.empty(max(N - 1, 1), dtype=torch.float32, device=dev)
+        info = torch.zeros(8, dtype=torch.int32, device=dev)
+        _lib.check(lib.fn_mst_init(N, ptr(comp), ptr(info), st), "mst_init")
+        rounds = max(1, int(N - 1).bit_length())               # ceil(log2 N): Boruvka's bound
+        _lib.check(lib.fn_mst_rounds(ptr(self.embeddings), N, self.length, ptr(core), slab_rows, ptr(work), ptr(comp), ptr(edges), ptr(weights),
+                                     ptr(info), rounds, st), "mst_rounds")
+        done, ran, components, written = info.cpu().tolist()[:4]
+        if not done or written != N - 1:
+            raise _lib.FacenetHipError(f"fn_mst_rounds left {components} components after {ran} rounds: are the embeddings numbers?")
+        host_core = np.zeros(N, dtype=np.float32) if core is None else core.cpu().numpy()
+        return SpanningTree.from_edges(edges[:N - 1].cpu().numpy(), weights[:N - 1].cpu().numpy(), host_core, rounds=ran, min_samples=min_samples)
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, method="eom", allow_single_cluster=False, slab_rows=0):
+        """HDBSCAN over the gallery's rows, no threshold at all -> `hierarchy.HierarchicalClustering`:
+        ``spanning_tree(min_samples).hdbscan(min_cluster_size, method, allow_single_cluster)``.  ``min_samples=None`` means
+        ``min_cluster_size``, as scikit-learn does."""
+        check_int("min_cluster_size", min_cluster_size, 2)
+        if method not in ("eom", "leaf"):
+            raise ValueError(f"method must be 'eom' or 'leaf', got {method!r}")
+        tree = self.spanning_tree(min_cluster_size if min_samples is None else min_samples, slab_rows=slab_rows)
+        return tree.hdbscan(min_cluster_size, method=method, allow_single_cluster=allow_single_cluster)

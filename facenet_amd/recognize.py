@@ -19,6 +19,10 @@ fn_radius_fill, with the same distances and the same strict fp32 < as validation
 DBSCAN on the self-join (fn_dbscan_*) and returns a `Clustering`; ``FacePipeline.cluster`` does so for the faces of a list of
 photographs without their embeddings leaving the device.
 
+``Gallery.spanning_tree`` and ``Gallery.hdbscan`` (`hierarchy.py`): the minimum spanning tree of the rows under
+the mutual-reachability distance, built on the device (fn_mst_*), and what is read from it on the host: the cut at any threshold,
+the linkage matrix and HDBSCAN, which needs no threshold.
+
 ``Gallery.mates`` is the search of the open-set evaluation: every probe's nearest mate, nearest impostor and
 the rank of that mate at any depth, from fn_mate_search on the same walk and the same bits; ``statistics.IdentificationCurve``
 turns them into FNIR at FPIR.
@@ -37,6 +41,7 @@ import torch
 
 from .detectors.face_detector import image_processing_aligned_batch, image_processing_batch
 from .gallery import DBSCAN_ROUNDS, MAX_EDGES, MAX_K, MAX_LENGTH, Clustering, Gallery, MateSearch, check_edges      # noqa: F401
+from .hierarchy import HierarchicalClustering, SpanningTree      # noqa: F401
 from .quantized import QuantizedGallery      # noqa: F401
 
 BATCH_SIZES = (1, 4, 16, 64, 256)
@@ -124,10 +129,13 @@ class FacePipeline:
             return []
         return list(zip(boxes, gallery.identify_candidates(self.embed_device(crops), **kw)))
 
-    def cluster(self, images, metric=0, **kw):
-        """Detect, crop and embed the faces of a list of photographs, then `Gallery.cluster(**kw)` them; the embeddings never
-        visit the host.  -> (Clustering, faces): faces[row] = (image index, face index within the image, BoundingBox).  Without a
-        single face: (None, [])."""
+    def cluster(self, images, metric=0, method="dbscan", **kw):
+        """Detect, crop and embed the faces of a list of photographs, then `Gallery.cluster(**kw)` them (``method='dbscan'``) or
+        `Gallery.hdbscan(**kw)` them (``'hdbscan'``: no threshold); the embeddings never visit the host.
+        -> (Clustering or HierarchicalClustering, faces): faces[row] = (image index, face index within the image, BoundingBox).
+        Without a single face: (None, [])."""
+        if method not in ("dbscan", "hdbscan"):
+            raise ValueError(f"method must be 'dbscan' or 'hdbscan', got {method!r}")
         faces, embeddings = [], []
         for index, image in enumerate(images):
             boxes, crops = self.crops(image)
@@ -137,4 +145,5 @@ class FacePipeline:
             faces.extend((index, n, box) for n, box in enumerate(boxes))
         if not faces:
             return None, []
-        return Gallery(torch.cat(embeddings), metric=metric, device=self.device).cluster(**kw), faces
+        gallery = Gallery(torch.cat(embeddings), metric=metric, device=self.device)
+        return (gallery.cluster(**kw) if method == "dbscan" else gallery.hdbscan(**kw)), faces

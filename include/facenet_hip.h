@@ -539,6 +539,26 @@ int fn_dbscan_rounds(int N, const int64_t* offsets, const int32_t* cols, const i
 int fn_dbscan_finish(int N, const int64_t* offsets, const int32_t* cols, const float* dist, int metric, const float* emb, int E,
                      const int32_t* core, int32_t* labels, int32_t* ids, int32_t* info, void* stream);
 
+/* ---- hierarchical clustering: the minimum spanning tree of N rows under the mutual-reachability distance,
+ * by Boruvka's algorithm on the device; the [N, N] matrix never reaches memory.  s and d = 2 (1 - sc) are those of fn_gallery_search,
+ * fn_radius_* and fn_mate_search bit for bit (metric 0 only: acosf is not pinned bit for bit, and the tree is).  The weight of the
+ * pair (i, j) is w = max(d(i, j), core[i], core[j]) in fp32; core fp32 [N] or NULL (zeros).  Edges are ordered by (bits(w), lo, hi),
+ * lo = min(i, j), hi = max(i, j); the result is THE minimum spanning tree under that strict total order (Kruskal's on the edges
+ * sorted that way), so it depends neither on slab_rows nor on scheduling.  rows fp32 [N, E], E, slab_rows and the alignment rule:
+ * as fn_mate_search's gallery.
+ * fn_mst_init: comp int32 [N] = 0 .. N - 1 (a row's component: the smallest row of it), info int32 [8] = {done, rounds run,
+ *   components, edges written, 4 words of the library's}.  N = 1 is done at once.
+ * fn_mst_rounds: enqueues `rounds` (1 .. 64) rounds: one walk of all pairs that finds every row's nearest row of another
+ *   component, then the contraction.  A round at least halves the components, so ceil(log2 N) rounds finish; a round does nothing
+ *   once info[0] is set, so the caller may enqueue them all and read info once.  edges int32 [N - 1][2] (lo < hi) and weights fp32
+ *   [N - 1] receive the tree; the SET of edges is the contract, their order in the buffer is not.  workspace: at least the bytes
+ *   fn_mst_workspace reports for the same N and slab_rows, the same buffer for every call of one tree.
+ * No call allocates or synchronises. */
+int fn_mst_workspace(int N, int slab_rows, long long* bytes);
+int fn_mst_init(int N, int32_t* comp, int32_t* info, void* stream);
+int fn_mst_rounds(const float* rows, int N, int E, const float* core, int slab_rows, void* workspace, int32_t* comp, int32_t* edges,
+                  float* weights, int32_t* info, int rounds, void* stream);
+
 /* ---- softmax classifier loss: apps/train_softmax.py:91 (SparseCategoricalCrossentropy(from_logits)); loss: fp32[4] as above;
  * dbias (optional): fixed point, FN_ACC_GRAD_BITS, += column sums of dlogits */
 int fn_softmax_xent_fwd_bwd(const float* logits, int ld, const int32_t* labels, float* loss, void* dlogits_lp, int ld_d, fn_acc_t* dbias, int N,
