@@ -263,7 +263,7 @@ static int launch_adam_keras(float* w, const float* g, float* m, float* v, void*
 extern "C" int fn_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper, float beta1,
                              float beta2, float eps, float l2, int dtype, void* stream) {
     FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
-    FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp % 4 == 0 && n_lp <= n,
+    FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp >= 0 && n_lp % 4 == 0 && n_lp <= n,
                "adam_keras: bad arguments (n %% 4 == 0)");
     return launch_adam_keras<false>(w, g, m, v, w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, nullptr, 0.f, dtype, stream);
 }
@@ -271,7 +271,7 @@ extern "C" int fn_adam_keras(float* w, const float* g, float* m, float* v, void*
 extern "C" int fn_adam_keras_ema(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper,
                                  float beta1, float beta2, float eps, float l2, int dtype, float* shadow, float decay, void* stream) {
     FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
-    FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp % 4 == 0 && n_lp <= n,
+    FN_REQUIRE(w && g && m && v && hyper && n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n && n_lp >= 0 && n_lp % 4 == 0 && n_lp <= n,
                "adam_keras_ema: bad arguments (n %% 4 == 0)");
     FN_REQUIRE(shadow && decay > 0.f && decay < 1.f, "adam_keras_ema: null shadow or decay %g outside (0, 1)", (double)decay);
     return launch_adam_keras<true>(w, g, m, v, w_lp, n_lp, n, n_decay, hyper, beta1, beta2, eps, l2, shadow, decay, dtype, stream);
@@ -348,7 +348,8 @@ extern "C" int fn_pack_transpose(const void* w_lp, void* wt_lp, const int32_t* t
 extern "C" int fn_fold_bn(const float* w, void* wf_lp, float* fold_bias, const float* beta, const float* moving_mean, const float* moving_var,
                           const int32_t* table, int n_layers, int max_layer_elems, float eps, int dtype, void* stream) {
     FN_REQUIRE(dtype == FN_BF16 || dtype == FN_F16, "dtype %d unsupported", dtype);
-    FN_REQUIRE(w && wf_lp && fold_bias && beta && moving_mean && moving_var && table && n_layers > 0, "fold_bn: bad arguments");
+    FN_REQUIRE(w && wf_lp && fold_bias && beta && moving_mean && moving_var && table && n_layers > 0 && max_layer_elems > 0,
+               "fold_bn: bad arguments");
     int gx = cdiv(max_layer_elems, 256 * 8);
     if (gx > 256) gx = 256;
     if (dtype == FN_BF16)

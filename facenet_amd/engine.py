@@ -227,6 +227,17 @@ class Network:
         self.bias_lo = self.n_decay + self.CB          # [bias_lo, n_params): the biases
         self.max_layer_elems = max(L.numel for L in self.layers.values())
 
+    def layer_table(self) -> np.ndarray:
+        """The int32 table fn_pack_transpose and fn_fold_bn walk, one row per layer: {w_off, cout, ktot, taps, cin, bn_off,
+        fold_bias_off, 0} (-1: no BatchNorm).  Their 16-byte paths need w_off and cin to be multiples of 8 and ktot == taps * cin,
+        and every layer here has cout % 8 == 0 as well; the C entries cannot check that in device memory
+        (tests/test_optim_refs_host.py does, on this)."""
+        tab = np.zeros((len(self.layers), 8), dtype=np.int32)
+        for i, L in enumerate(self.layers.values()):
+            tab[i] = [L.w_off, L.cout, L.ktot, L.kh * L.kw, L.cin, L.bn_off if L.has_bn else -1,
+                      L.bn_off if L.has_bn else -1, 0]
+        return tab
+
     def _alloc_params(self, seed: int):
         dev = self.device
         self.P = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
@@ -236,11 +247,7 @@ class Network:
         self.Wt_train = torch.zeros(self.n_kernel, dtype=self.train_dtype, device=dev)
         self.W_infer = torch.zeros(self.n_kernel, dtype=self.infer_dtype, device=dev)
         self.fold_bias = torch.zeros(self.CB, dtype=torch.float32, device=dev)
-        tab = np.zeros((len(self.layers), 8), dtype=np.int32)
-        for i, L in enumerate(self.layers.values()):
-            tab[i] = [L.w_off, L.cout, L.ktot, L.kh * L.kw, L.cin, L.bn_off if L.has_bn else -1,
-                      L.bn_off if L.has_bn else -1, 0]
-        self.table = torch.from_numpy(tab).to(dev)
+        self.table = torch.from_numpy(self.layer_table()).to(dev)
         self.G = None  # gradient / optimiser state are created by the Trainer
         self.load_keras_params(self.init_keras_params(seed))
 

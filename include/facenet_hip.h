@@ -628,7 +628,8 @@ int fn_f2f_distance(const float* x, const float* nx, int N, const float* y, cons
 /* ---- optimiser: tf.keras.optimizers.Adam(epsilon=0.1) apps/train_softmax.py:92 + Keras L2(5e-4) (:65) ----
  * hyper = device word[8] {lr, beta1^t, beta2^t, grad_scale, t (int32: Keras' `iterations`), 3 spare}; fn_adam_tick advances t and
  * re-derives the beta powers from it on the device (graph replay safe; t survives past the fp32 underflow of beta1^t).
- * Elements [0, n_decay) get the coupled L2 term g += 2*l2*w.  w_lp receives the low-precision copy of w[0, n_lp). */
+ * Elements [0, n_decay) get the coupled L2 term g += 2*l2*w.  w_lp receives the low-precision copy of w[0, n_lp).
+ * n > 0, n % 4 == 0, 0 <= n_decay <= n, 0 <= n_lp <= n, n_lp % 4 == 0, else FN_EINVAL. */
 int fn_adam_keras(float* w, const float* g, float* m, float* v, void* w_lp, long n_lp, long n, long n_decay, float* hyper, float beta1,
                   float beta2, float eps, float l2, int dtype, void* stream);
 /* fn_adam_keras_ema: fn_adam_keras (w, m, v, w_lp bit-identical) fused with the moving average of the new weights over [0, n):
@@ -657,7 +658,10 @@ int fn_opt_keras_ema(int rule, float* w, const float* g, float* s1, float* s2, v
 /* ---- weight packs ----------------------------------------------------------------------------------
  * table = device int32 [n_layers][8] {w_off, cout, ktot, taps, cin, bn_off(-1 none), fold_bias_off, 0}.
  * fn_pack_transpose: wt[cin][tap][cout] = w[cout][tap][cin] (dgrad operand) for every layer.
- * fn_fold_bn: wf = lp(w * rsqrt(var+eps)[cout]), bias = beta - mean*rsqrt(var+eps)   (facenet/tfutils.py:244-250) */
+ * fn_fold_bn: wf = lp(w * rsqrt(var+eps)[cout]), bias = beta - mean*rsqrt(var+eps)   (facenet/tfutils.py:244-250)
+ * Every row: w_off and cin multiples of 8, ktot == taps * cin (the 16-byte paths; not checkable here: the table is device
+ * memory); fn_pack_transpose moves a layer whose cout is no multiple of 8 element by element.  n_layers > 0 and
+ * max_layer_elems > 0 (it sizes the grid), else FN_EINVAL. */
 int fn_pack_transpose(const void* w_lp, void* wt_lp, const int32_t* table, int n_layers, int max_layer_elems, int dtype, void* stream);
 int fn_fold_bn(const float* w, void* wf_lp, float* fold_bias, const float* beta, const float* moving_mean, const float* moving_var,
                const int32_t* table, int n_layers, int max_layer_elems, float eps, int dtype, void* stream);

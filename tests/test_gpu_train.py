@@ -194,12 +194,15 @@ def test_checkpoint_round_trip_in_keras_naming(tmp_path):
     assert tr2.iterations == 1102 and torch.equal(tr.hyper.view(torch.int32)[:5], tr2.hyper.view(torch.int32)[:5])
 
 
-def test_bn_folded_export_matches_tfutils_formula():
+@pytest.mark.parametrize("infer_dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+def test_bn_folded_export_matches_tfutils_formula(infer_dtype):
     """facenet/tfutils.py:244-250: weights * 1/sqrt(variance + epsilon), biases = -mean * scale + beta, applied to the
-    un-folded Keras variables, must give what the inference kernels read (fn_fold_bn), to f16 rounding."""
+    un-folded Keras variables, must give what the inference kernels read (fn_fold_bn), to the rounding of the storage type:
+    2u of the layer's largest weight, u = 2^-11 (f16) or 2^-8 (bf16).  (Element by element against fp64: test_gpu_optim_edges.py.)"""
     params, _, _ = fo.build_params(128, seed=0)
     fo.perturb_bn_stats(params, seed=1)
-    net = Network(embedding_size=128, device="cuda:0", infer_dtype=torch.float16)
+    bar = 2.0 ** -10 if infer_dtype == torch.float16 else 2.0 ** -7
+    net = Network(embedding_size=128, device="cuda:0", infer_dtype=infer_dtype)
     net.load_keras_params(params)
     folded = net.export_folded_params()
     n_bn = 0
@@ -215,8 +218,8 @@ def test_bn_folded_export_matches_tfutils_formula():
             want_w, want_b = w, params[L.name + "/bias"]
         got_w, got_b = folded[L.name + "/weights"], folded[L.name + "/biases"]
         assert got_w.shape == want_w.shape
-        assert torch.allclose(got_w, want_w.half().float(), rtol=0, atol=0) or \
-            (got_w - want_w).abs().max() <= 2 ** -10 * want_w.abs().max(), L.name      # one f16 rounding of the product
+        assert torch.allclose(got_w, want_w.to(infer_dtype).float(), rtol=0, atol=0) or \
+            (got_w - want_w).abs().max() <= bar * want_w.abs().max(), L.name           # one storage rounding of the product
         assert torch.allclose(got_b, want_b, rtol=1e-6, atol=1e-6), L.name
     assert n_bn == 112
 
