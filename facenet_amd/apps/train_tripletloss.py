@@ -6,7 +6,11 @@ Per step: embed a P x K pool with the inference path -> [PK,PK] squared distance
 train on the selected (a,p,n) rows: forward(training=True) -> l2_normalize -> triplet loss -> backward -> the Keras optimizer
 train.optimizer names (Adam by default).
 Pools come from ``pools`` (an iterable of (uint8 images [P*K,160,160,3])) with labels repeat(arange(P), K) or, by
-default, from a seeded synthetic generator."""
+default, from a seeded synthetic generator.
+
+``loss.triplet_strategy: batch_hard | batch_all`` (with ``loss.soft_margin``) trains on the whole P x K batch instead and mines
+inside it (arXiv 1703.07737 sec. 2): no pool forward, no selection, no gather; per step set_images(images,
+labels) -> step.  ``pools`` may then yield ``images`` or ``(images, labels)``.  Absent or ``mined``: the behaviour above."""
 from __future__ import annotations
 
 import time
@@ -19,8 +23,69 @@ import torch
 from facenet_amd import config as config_mod
 from facenet_amd.engine_v2 import build_network
 from facenet_amd.facenet import LearningRateScheduler
+from facenet_amd.heads import TRIPLET_STRATEGIES
 from facenet_amd.train import GraphRunner, Trainer, TripletMiner, moving_average_decay, optimizer_name
 from facenet_amd.schedule import make_events
+
+
+def triplet_settings(cfg):
+    """(loss.triplet_strategy, loss.soft_margin): absent keys mean the mined step and the hinge."""
+    strategy = cfg.loss.triplet_strategy if cfg.loss.triplet_strategy else "mined"
+    if strategy not in TRIPLET_STRATEGIES:
+        raise ValueError(f"loss.triplet_strategy must be one of {', '.join(TRIPLET_STRATEGIES)}, got {strategy!r}")
+    return strategy, bool(cfg.loss.soft_margin)
+
+
+def end_of_epoch(cfg, trainer, validation, epoch):
+    if trainer.shadow is not None and cfg.model.path:            # the averaged model, loadable by FaceNet(config.path=...)
+        path = Path(cfg.model.path).expanduser()
+        if trainer.rank == 0:
+            (path / "averaged").mkdir(parents=True, exist_ok=True)
+        trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
+    if validation is not None:
+        validation.on_epoch_end(epoch)
+
+
+def train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_batch, images_per_person, pools, use_graph, world_size,
+                        process_group, log, validation):
+    """The batch-mined run: the trainer's batch is the whole P x K batch and every embedded image receives a gradient."""
+    n = people_per_batch * images_per_person
+    scheduler = LearningRateScheduler(cfg.train.learning_rate)
+    trainer = Trainer(net, batch=n, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size, process_group=process_group,
+                      moving_average_decay=moving_average_decay(cfg), optimizer=optimizer, triplet_strategy=strategy, soft_margin=soft)
+    if trainer.rank == 0:
+        log(f"triplet strategy: {strategy}" + (", soft margin" if soft else "") + (f", optimizer: {optimizer}" if optimizer != "ADAM" else ""))
+    if validation is not None and validation.model is None:
+        validation.attach(trainer, path=cfg.model.path if cfg.model.path else None, rank=trainer.rank, world=world_size,
+                          process_group=process_group)
+    default_labels = np.repeat(np.arange(people_per_batch), images_per_person)
+    if pools is None:
+        g = torch.Generator().manual_seed(cfg.seed)
+        pools = (torch.randint(0, 256, (n, cfg.image.size, cfg.image.size, 3), dtype=torch.uint8, generator=g) for _ in iter(int, 1))
+    pools = iter(pools)
+
+    def feed():
+        item = next(pools)
+        images, labels = item if isinstance(item, (tuple, list)) else (item, default_labels)
+        trainer.set_images(images, labels)
+
+    if use_graph:
+        trainer.set_images(torch.zeros_like(trainer.plan.images), default_labels)      # the warm-up step of capture() needs a live batch
+        trainer.capture()                                         # side-effect free (state restored after its warm-up step)
+    for epoch in range(cfg.train.epoch.nrof_epochs):
+        trainer.set_learning_rate(scheduler(epoch))
+        t0 = time.perf_counter()
+        for _ in range(cfg.train.epoch.size):
+            feed()
+            trainer.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        stats = trainer.triplet_stats()
+        log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  triplet loss {trainer.loss_value():.4f}  "
+            f"active {stats['active_fraction']:.3f} ({stats['active']}/{stats['terms']})  "
+            f"{n * cfg.train.epoch.size * world_size / dt:.1f} img/s")
+        end_of_epoch(cfg, trainer, validation, epoch)
+    return net, trainer
 
 
 def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 4, nrof_triplets: int = 30, embedding_size: int = 128,
@@ -32,6 +97,12 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
     # model.module picks the family (Inception-ResNet-v1 by default, v2 for facenet[_amd].models.inception_resnet_v2)
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         device=device, seed=cfg.seed)
+    strategy, soft = triplet_settings(cfg)
+    if strategy != "mined":
+        return train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_batch, images_per_person, pools, use_graph,
+                                   world_size, process_group, log, validation)
+    if soft:
+        raise ValueError("loss.soft_margin needs loss.triplet_strategy batch_hard or batch_all")
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=3 * nrof_triplets, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size,
                       process_group=process_group, moving_average_decay=moving_average_decay(cfg), optimizer=optimizer)
@@ -65,13 +136,7 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
         dt = time.perf_counter() - t0
         log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  triplet loss {trainer.loss_value():.4f}  "
             f"{3 * nrof_triplets * cfg.train.epoch.size * world_size / dt:.1f} img/s")
-        if trainer.shadow is not None and cfg.model.path:        # the averaged model, loadable by FaceNet(config.path=...)
-            path = Path(cfg.model.path).expanduser()
-            if trainer.rank == 0:
-                (path / "averaged").mkdir(parents=True, exist_ok=True)
-            trainer.save_averaged_weights(path / "averaged" / f"{path.stem}.npz")
-        if validation is not None:
-            validation.on_epoch_end(epoch)
+        end_of_epoch(cfg, trainer, validation, epoch)
     return net, trainer
 
 
@@ -96,8 +161,9 @@ def main(**options):
     validation = callbacks.from_config(cfg)                      # None unless validate.dataset.path is set
     if cfg.dataset.path:
         pipe = dataset_pools(cfg)
+        batch_mined = triplet_settings(cfg)[0] != "mined"         # the batch strategies mine by the sampler's own labels
         train_tripletloss(cfg, people_per_batch=cfg.nrof_classes_per_batch, images_per_person=cfg.nrof_examples_per_class,
-                          pools=(images for images, _ in pipe), validation=validation)
+                          pools=pipe if batch_mined else (images for images, _ in pipe), validation=validation)
     else:
         train_tripletloss(cfg, validation=validation)
 

@@ -2,6 +2,8 @@
 gradient ``demb``.
 
 * ``triplet_head``: l2_normalize -> triplet loss over rows (a0,p0,n0,a1,...) (arXiv 1503.03832).
+* ``batch_triplet_head``: l2_normalize -> squared distances -> batch-hard / batch-all triplet loss mined inside the labelled batch
+  (arXiv 1703.07737 sec. 2).
 * ``softmax_head``: the classifier Dense(C) + softmax cross-entropy (apps/train_softmax.py:49-104), or with ``margin`` the
   large-margin cosine softmax (NormFace / CosFace / ArcFace) through the same classifier launches.
 * ``add_regularizers``: center loss and prelogits norm on a softmax head (facenet/facenet.py:204-217).
@@ -22,15 +24,30 @@ from .engine import Network, _ptr, bias_region, weight_region
 from .schedule import Op, emit, region, torch_op
 
 
+TRIPLET_STRATEGIES = ("mined", "batch_hard", "batch_all")      # "mined": TripletMiner fills the (a,p,n) rows; the others: fn_batch_triplet_fwd_bwd
+
+
 def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: float, center_alfa: float, prelogits_norm_factor: float,
-                         prelogits_norm_p: float, margin_scale: float = 0.0, margin_arc: float = 0.0, margin_cos: float = 0.0):
+                         prelogits_norm_p: float, margin_scale: float = 0.0, margin_arc: float = 0.0, margin_cos: float = 0.0,
+                         triplet_strategy: str = "mined", soft_margin: bool = False):
     """What the Trainer refuses: an unknown loss, a batch or network that does not fit it, regulariser settings out of range
     (loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p, train_softmax.yaml:73-78), margin settings out of
-    range or without a scale (loss.margin_scale / margin_arc / margin_cos)."""
+    range or without a scale (loss.margin_scale / margin_arc / margin_cos), an unknown triplet strategy or
+    one that does not fit the loss or the batch (loss.triplet_strategy / soft_margin)."""
     if loss not in ("triplet", "softmax"):
         raise ValueError(f"unknown loss {loss!r}")
-    if loss == "triplet" and batch % 3:
+    if triplet_strategy not in TRIPLET_STRATEGIES:
+        raise ValueError(f"unknown triplet_strategy {triplet_strategy!r}: expected one of {', '.join(TRIPLET_STRATEGIES)}")
+    if loss == "softmax" and (triplet_strategy != "mined" or soft_margin):
+        raise ValueError("triplet_strategy and soft_margin belong to triplet training")
+    if soft_margin and triplet_strategy == "mined":
+        raise ValueError("soft_margin needs triplet_strategy 'batch_hard' or 'batch_all': the mined triplet loss has the hinge only")
+    if batch < 2:
+        raise ValueError(f"batch must be >= 2, got {batch}")
+    if loss == "triplet" and triplet_strategy == "mined" and batch % 3:
         raise ValueError("triplet batches are laid out (a,p,n,...): batch must be a multiple of 3")
+    if loss == "triplet" and triplet_strategy != "mined" and batch > 1024:
+        raise ValueError(f"the batch-mined triplet losses take at most 1024 rows, got batch {batch}")
     if loss == "softmax" and net.nrof_classes is None:
         raise ValueError("softmax training needs Network(nrof_classes=...)")
     if not (center_factor >= 0 and prelogits_norm_factor >= 0):
@@ -74,6 +91,30 @@ def triplet_head(net: Network, emb: torch.Tensor, demb: torch.Tensor, loss: torc
     emit(ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(dembn), _ptr(demb), batch, E, 1e-10,
          r=[region(emb), region(dembn)], w=[region(demb)])
     return Head(ops, dict(embn=embn, dembn=dembn))
+
+
+def batch_triplet_head(net: Network, emb: torch.Tensor, demb: torch.Tensor, loss: torch.Tensor, alpha: float, strategy: str,
+                       soft: bool) -> Head:
+    """l2_normalize -> [batch,batch] squared distances -> batch-hard / batch-all loss mined inside the labelled batch -> gradient wrt
+    the un-normalised embedding.  ``labels`` (int32 [batch], on the device) name the identities; the head
+    carries nothing from step to step."""
+    lib, dev, (batch, E) = net.lib, net.device, emb.shape
+    embn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
+    dembn = torch.zeros(batch, E, dtype=torch.float32, device=dev)
+    dist = torch.zeros(batch, batch, dtype=torch.float32, device=dev)
+    coef = torch.zeros(batch, batch, dtype=torch.float32, device=dev)
+    labels = torch.zeros(batch, dtype=torch.int32, device=dev)
+    mine_info = torch.zeros(8, dtype=torch.int32, device=dev)
+    ops: List[Op] = []
+    emit(ops, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(emb), _ptr(embn), batch, E, 1e-10, r=[region(emb)], w=[region(embn)])
+    emit(ops, "pairwise_sqdist", lib.fn_pairwise_sqdist, _ptr(embn), _ptr(embn), _ptr(dist), None, batch, batch, E, 2,
+         r=[region(embn)], w=[region(dist)])
+    emit(ops, "batch_triplet", lib.fn_batch_triplet_fwd_bwd, _ptr(embn), _ptr(dist), _ptr(labels), _ptr(dembn), _ptr(loss), _ptr(coef),
+         _ptr(mine_info), batch, E, alpha, TRIPLET_STRATEGIES.index(strategy) - 1, 1 if soft else 0,
+         r=[region(embn), region(dist), region(labels)], w=[region(dembn), region(loss), region(coef), region(mine_info)])
+    emit(ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(dembn), _ptr(demb), batch, E, 1e-10,
+         r=[region(emb), region(dembn)], w=[region(demb)])
+    return Head(ops, dict(embn=embn, dembn=dembn, dist=dist, coef=coef, labels=labels, mine_info=mine_info))
 
 
 def _cls_desc(batch: int, L, dt: int):

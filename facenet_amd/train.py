@@ -6,6 +6,8 @@
 * ``Trainer(loss='triplet')`` is the north-star path the reference lacks (build-defined
   from arXiv 1503.03832): forward(training=True) -> l2_normalize -> triplet loss over rows laid out
   (a0,p0,n0,a1,...).  ``TripletMiner`` does the online selection in a PxK pool on device.
+* ``Trainer(loss='triplet', triplet_strategy='batch_hard' | 'batch_all', soft_margin=...)`` trains on the whole labelled P x K batch
+  and mines inside it (arXiv 1703.07737 sec. 2): ``set_images(images, labels)``, no miner, no gather.
 * ``Trainer(loss='softmax', center_factor=..., prelogits_norm_factor=...)`` adds the reference's embedding regularisers
   (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
 * ``Trainer(loss='softmax', margin_scale=64, margin_arc=0.5)`` replaces the plain softmax head by the large-margin cosine softmax
@@ -75,7 +77,7 @@ class Trainer:
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
                  center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0,
                  moving_average_decay: Optional[float] = None, optimizer: str = "ADAM", margin_scale: float = 0.0,
-                 margin_arc: float = 0.0, margin_cos: float = 0.0):
+                 margin_arc: float = 0.0, margin_cos: float = 0.0, triplet_strategy: str = "mined", soft_margin: bool = False):
         self.group_wgrad = group_wgrad
         self.optimizer = check_optimizer(optimizer)        # beta1, beta2 and epsilon are Adam's; the other rules' constants: OPTIMIZERS
         self.rule = OPTIMIZERS[self.optimizer]
@@ -88,7 +90,10 @@ class Trainer:
         self.exchange = world_size > 1 or process_group is not None
         self.segmented = self.exchange or force_segments
         check_loss_arguments(net, batch, loss, center_factor, center_alfa, prelogits_norm_factor, prelogits_norm_p, margin_scale,
-                             margin_arc, margin_cos)
+                             margin_arc, margin_cos, triplet_strategy, soft_margin)
+        # "mined": rows (a,p,n,...) filled by a TripletMiner; "batch_hard" / "batch_all": mined inside the labelled batch (section 31)
+        self.triplet_strategy, self.soft_margin = triplet_strategy, bool(soft_margin)
+        self.batch_mined = loss == "triplet" and triplet_strategy != "mined"
         # NormFace / CosFace / ArcFace: settings, not state; margin_scale == 0 is the plain softmax head
         self.margin_scale, self.margin_arc, self.margin_cos = float(margin_scale), float(margin_arc), float(margin_cos)
         self.margin = margin_scale > 0
@@ -124,7 +129,9 @@ class Trainer:
         self.plan: Lowering = net.plan(batch, training=True, step_word=self.hyper.view(torch.int32)[4:5], rank=rank)
         self.demb = torch.zeros(batch, E, dtype=torch.float32, device=dev)
         self.emb = self.plan.embedding.buf.act.view(batch, E)
-        if loss == "triplet":
+        if self.batch_mined:
+            head = heads.batch_triplet_head(net, self.emb, self.demb, self.loss, alpha, triplet_strategy, self.soft_margin)
+        elif loss == "triplet":
             head = heads.triplet_head(net, self.emb, self.demb, self.loss, alpha)
         else:
             head = heads.softmax_head(net, self.emb, self.demb, self.loss, self.G, self.dt,
@@ -132,8 +139,8 @@ class Trainer:
             if self.regularized:
                 heads.add_regularizers(head, net, self.emb, self.demb, self.center_factor, float(center_alfa), self.prelogits_norm_factor,
                                        float(prelogits_norm_p), world_size, rank)
-        # the head's tensors are the trainer's attributes, bound here once: embn, dembn (triplet, margin); labels, emb_lp, logits,
-        # dlogits (softmax); rnorm, margin_t (margin); reg_terms, centers, center_rows (regularisers).  `head` itself stays: it
+        # the head's tensors are the trainer's attributes, bound here once: embn, dembn (triplet, margin); dist, coef, labels, mine_info
+        # (batch-mined triplet); labels, emb_lp, logits, dlogits (softmax); rnorm, margin_t (margin); reg_terms, centers, center_rows (regularisers).  `head` itself stays: it
         # keeps what its launches point at alive
         self.head, self.centers = head, None
         for name, t in head.tensors.items():
@@ -348,7 +355,20 @@ class Trainer:
     # ---- host conveniences -----------------------------------------------------------------------
     def set_images(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None):
         self.plan.images.copy_(images.to(self.net.device, non_blocking=True))
-        if labels is not None:
+        if labels is not None and self.batch_mined:
+            # identity ids, any values: checked on the host, where it is cheap -- a batch in which no row has both a positive and
+            # a negative would train on nothing without a word
+            lab = np.asarray(torch.as_tensor(labels).cpu()).reshape(-1).astype(np.int64)
+            if lab.size != self.N:
+                raise ValueError(f"labels must hold one identity per batch row ({self.N}), got {lab.size}")
+            if lab.min() < -2 ** 31 or lab.max() >= 2 ** 31:
+                raise ValueError("labels must fit int32")
+            _, inverse, counts = np.unique(lab, return_inverse=True, return_counts=True)
+            if len(counts) < 2 or not bool((counts[inverse] >= 2).any()):
+                raise ValueError("no row of the batch has both a positive and a negative: the labels need at least two identities, one "
+                                 "of them with two rows")
+            self.labels.copy_(torch.from_numpy(lab.astype(np.int32)).to(self.net.device))
+        elif labels is not None:
             if self.loss_kind != "softmax":
                 raise ValueError("labels are only used by the softmax loss")
             labels = torch.as_tensor(labels)
@@ -506,6 +526,14 @@ class Trainer:
     def loss_value(self) -> float:
         """The cross-entropy (softmax) or triplet loss of the last step, without the regularisers (see loss_terms)."""
         return float(self.loss[0].item())
+
+    def triplet_stats(self) -> Dict[str, float]:
+        """The last step's mining counts of a batch-mined triplet trainer (one small copy from the device): ``anchors`` (rows with a
+        positive and a negative), ``terms``, ``active`` (hinge: terms > 0; soft margin: all of them) and ``active_fraction``."""
+        if not self.batch_mined:
+            raise RuntimeError("triplet_stats() belongs to triplet_strategy 'batch_hard' / 'batch_all'")
+        anchors, terms, active = self.mine_info[:3].cpu().tolist()
+        return {"anchors": anchors, "terms": terms, "active": active, "active_fraction": active / terms if terms else 0.0}
 
     def loss_terms(self) -> Dict[str, Optional[float]]:
         """The last step's terms under the names the reference logged: ``xent``, ``center_loss``, ``prelogits_norm`` and their

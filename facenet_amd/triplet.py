@@ -1,5 +1,6 @@
 """Triplet selection and loss (build-defined: the reference has none; arXiv 1503.03832 sec. 3).
-Thin host wrappers over fn_pairwise_sqdist / fn_select_triplets / fn_triplet_loss_fwd_bwd for use outside a plan."""
+Thin host wrappers over fn_pairwise_sqdist / fn_select_triplets / fn_triplet_loss_fwd_bwd / fn_batch_triplet_fwd_bwd (the
+batch-mined losses of arXiv 1703.07737 sec. 2) for use outside a plan."""
 from __future__ import annotations
 
 import numpy as np
@@ -52,3 +53,33 @@ def triplet_loss(emb: torch.Tensor, alpha: float, with_grad: bool = False):
     _lib.check(lib.fn_triplet_loss_fwd_bwd(_ptr(e), _ptr(grad), _ptr(loss), T, E, float(alpha),
                                            stream(e.device)), "triplet_loss")
     return (loss[0], grad) if with_grad else loss[0]
+
+
+BATCH_STRATEGIES = {"batch_hard": 0, "batch_all": 1}
+
+
+def batch_triplet_loss(emb: torch.Tensor, labels, alpha: float = 0.2, strategy: str = "batch_hard", soft: bool = False,
+                       with_grad: bool = False):
+    """emb fp32 [N,E] (normalised or not), labels [N] identity ids.  Batch-hard or batch-all triplet loss mined inside the batch, with
+    the hinge (``alpha``) or the soft margin.  Returns (loss 0-d tensor, info) or (loss, d loss / d emb, info); info = {"anchors",
+    "terms", "active", "active_fraction"}.  A non-finite distance makes the loss NaN."""
+    if strategy not in BATCH_STRATEGIES:
+        raise ValueError(f"unknown strategy {strategy!r}: expected 'batch_hard' or 'batch_all'")
+    lib = _lib.load()
+    e = emb.to(dtype=torch.float32).contiguous()
+    n, E = e.shape
+    lab = torch.as_tensor(np.asarray(torch.as_tensor(labels).cpu()).reshape(-1).astype(np.int32)).to(e.device)
+    if lab.numel() != n:
+        raise ValueError(f"labels must have one entry per row of emb ({n}), got {lab.numel()}")
+    if not 2 <= n <= 1024:
+        raise ValueError(f"batch_triplet_loss takes 2 to 1024 rows, got {n}")
+    dist = squared_distances(e)
+    loss = torch.zeros(4, dtype=torch.float32, device=e.device)      # word 0 = the loss, words 1-3 = the launch's
+    coef = torch.empty(n, n, dtype=torch.float32, device=e.device)
+    info = torch.zeros(8, dtype=torch.int32, device=e.device)
+    grad = torch.empty_like(e) if with_grad else None
+    _lib.check(lib.fn_batch_triplet_fwd_bwd(_ptr(e), _ptr(dist), _ptr(lab), _ptr(grad), _ptr(loss), _ptr(coef), _ptr(info), n, E,
+                                            float(alpha), BATCH_STRATEGIES[strategy], 1 if soft else 0, stream(e.device)), "batch_triplet")
+    anchors, terms, active = info[:3].cpu().tolist()
+    stats = {"anchors": anchors, "terms": terms, "active": active, "active_fraction": active / terms if terms else 0.0}
+    return (loss[0], grad, stats) if with_grad else (loss[0], stats)

@@ -349,6 +349,19 @@ int fn_select_triplets(const float* dist, const int32_t* labels, int n, float al
                        int semi_hard, int32_t* triplets, int32_t* info, void* stream);
 /* loss: fp32[4] -- word 0 receives the loss; words 2-3 are the launch's own fixed-point accumulator (FN_ACC_GRAD_BITS) */
 int fn_triplet_loss_fwd_bwd(const float* emb, float* demb, float* loss, int T, int E, float alpha, void* stream);
+/* Batch-mined triplet losses on a whole batch (arXiv 1703.07737 sec. 2).
+ * emb fp32 [N,E] (unit norm is not assumed); dist fp32 [N,N] = fn_pairwise_sqdist(emb, emb, metric 2), bitwise symmetric; labels
+ * int32 [N], any values; 2 <= N <= 1024, 1 <= E <= 512.  strategy 0 = batch hard (per anchor the farthest positive and the nearest
+ * negative, the lowest index on ties), 1 = batch all (every valid triplet).  soft 0 = hinge max(d_ap - d_an + alpha, 0), active
+ * iff strictly > 0 (alpha finite, >= 0); soft 1 = softplus(d_ap - d_an), alpha ignored.
+ * info int32 [8]: [0] anchors with a positive and a negative, [1] terms, [2] active terms (soft: = [1]), [3] 1 if a distance of
+ * such an anchor to one of its positives or negatives was not finite (loss[0] is then NaN), [4..7] zero.
+ * Z = info[0] (batch hard), info[2] (batch all, hinge), info[1] (batch all, soft); Z = 0 gives loss 0 and a zero gradient.
+ * coef fp32 [N,N], written in full: coef[a][j] = d (Z loss) / d dist[a][j] with a as the anchor (> 0 for a positive j, < 0 for a
+ * negative j, else 0).  demb fp32 [N,E] or NULL: demb[r] = (2/Z) sum_j (coef[r][j] + coef[j][r]) (emb[r] - emb[j]), j ascending;
+ * every row is written.  loss: fp32[4], 8-byte aligned, word 0 receives the loss.  No float atomics: bitwise reproducible. */
+int fn_batch_triplet_fwd_bwd(const float* emb, const float* dist, const int32_t* labels, float* demb, float* loss, float* coef,
+                             int32_t* info, int N, int E, float alpha, int strategy, int soft, void* stream);
 
 /* ---- face-to-face validation statistics: facenet/statistics.py:111-138 (ConfidenceMatrix) with the class-balanced
  * weights of SimilarityCalculator.evaluate (:92-103).  emb fp32 [n,E], unit-norm rows grouped by class (class c = rows
