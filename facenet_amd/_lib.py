@@ -137,6 +137,8 @@ _SIGNATURES = {
     "fn_select_triplets": [_p, _p, _i, _f, _i, _u, _i, _p, _p, _p],
     "fn_triplet_loss_fwd_bwd": [_p, _p, _p, _i, _i, _f, _p],
     "fn_batch_triplet_fwd_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _i, _p],
+    "fn_xbm_triplet_fwd_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
+    "fn_xbm_enqueue": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "fn_confidence_counts": [_p, _p, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_confidence_counts_folds": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p],
     "fn_pair_key_histogram": [_p, _p, _i, _i, _i, C.POINTER(_u), C.POINTER(C.c_int32), _i, _p, _p, _p],

@@ -10,7 +10,11 @@ default, from a seeded synthetic generator.
 
 ``loss.triplet_strategy: batch_hard | batch_all`` (with ``loss.soft_margin``) trains on the whole P x K batch instead and mines
 inside it (arXiv 1703.07737 sec. 2): no pool forward, no selection, no gather; per step set_images(images,
-labels) -> step.  ``pools`` may then yield ``images`` or ``(images, labels)``.  Absent or ``mined``: the behaviour above."""
+labels) -> step.  ``pools`` may then yield ``images`` or ``(images, labels)``.  Absent or ``mined``: the behaviour above.
+
+``loss.memory_size: M`` (with ``loss.memory_start``: the steps to let pass before rows are stored) adds a cross-batch memory of the last M
+embedded rows to ``batch_hard`` (Wang et al., CVPR 2020).  Its labels must mean the same identity in every
+step, so ``pools`` must then yield ``(images, labels)`` with dataset-wide identity ids."""
 from __future__ import annotations
 
 import time
@@ -36,6 +40,19 @@ def triplet_settings(cfg):
     return strategy, bool(cfg.loss.soft_margin)
 
 
+def memory_settings(cfg):
+    """(loss.memory_size, loss.memory_start): absent keys mean no cross-batch memory.  Whole numbers only; their ranges are the
+    Trainer's to refuse (heads.check_loss_arguments)."""
+    out = []
+    for key in ("memory_size", "memory_start"):
+        v = getattr(cfg.loss, key)
+        v = 0 if v is None or isinstance(v, config_mod.Config) and not v else v      # (an absent key reads as an empty Config)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"loss.{key} must be a non-negative integer, got {v!r}")
+        out.append(int(v))
+    return tuple(out)
+
+
 def end_of_epoch(cfg, trainer, validation, epoch):
     if trainer.shadow is not None and cfg.model.path:            # the averaged model, loadable by FaceNet(config.path=...)
         path = Path(cfg.model.path).expanduser()
@@ -47,14 +64,16 @@ def end_of_epoch(cfg, trainer, validation, epoch):
 
 
 def train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_batch, images_per_person, pools, use_graph, world_size,
-                        process_group, log, validation):
+                        process_group, log, validation, memory_size=0, memory_start=0):
     """The batch-mined run: the trainer's batch is the whole P x K batch and every embedded image receives a gradient."""
     n = people_per_batch * images_per_person
     scheduler = LearningRateScheduler(cfg.train.learning_rate)
     trainer = Trainer(net, batch=n, loss="triplet", alpha=alpha, lr=scheduler(0), world_size=world_size, process_group=process_group,
-                      moving_average_decay=moving_average_decay(cfg), optimizer=optimizer, triplet_strategy=strategy, soft_margin=soft)
+                      moving_average_decay=moving_average_decay(cfg), optimizer=optimizer, triplet_strategy=strategy, soft_margin=soft,
+                      **(dict(memory_size=memory_size, memory_start=memory_start) if memory_size else {}))
     if trainer.rank == 0:
-        log(f"triplet strategy: {strategy}" + (", soft margin" if soft else "") + (f", optimizer: {optimizer}" if optimizer != "ADAM" else ""))
+        log(f"triplet strategy: {strategy}" + (", soft margin" if soft else "") + (f", optimizer: {optimizer}" if optimizer != "ADAM" else "")
+            + (f", cross-batch memory: {memory_size} rows from step {memory_start}" if memory_size else ""))
     if validation is not None and validation.model is None:
         validation.attach(trainer, path=cfg.model.path if cfg.model.path else None, rank=trainer.rank, world=world_size,
                           process_group=process_group)
@@ -66,6 +85,9 @@ def train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_b
 
     def feed():
         item = next(pools)
+        if memory_size and not isinstance(item, (tuple, list)):
+            # repeat(arange(P), K) restarts at 0 in every batch: in the memory, rows of different people would share an id
+            raise ValueError("with loss.memory_size the pools must yield (images, labels) with dataset-wide identity ids")
         images, labels = item if isinstance(item, (tuple, list)) else (item, default_labels)
         trainer.set_images(images, labels)
 
@@ -83,6 +105,7 @@ def train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_b
         stats = trainer.triplet_stats()
         log(f"epoch {epoch + 1}/{cfg.train.epoch.nrof_epochs}  triplet loss {trainer.loss_value():.4f}  "
             f"active {stats['active_fraction']:.3f} ({stats['active']}/{stats['terms']})  "
+            + (f"memory negatives {stats['memory_negatives'] / max(stats['anchors'], 1):.3f} ({stats['memory_valid']} rows)  " if memory_size else "") +
             f"{n * cfg.train.epoch.size * world_size / dt:.1f} img/s")
         end_of_epoch(cfg, trainer, validation, epoch)
     return net, trainer
@@ -98,9 +121,12 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
     net = build_network(cfg.model, embedding_size, image_size=cfg.image.size, normalization=cfg.image.normalization,
                         device=device, seed=cfg.seed)
     strategy, soft = triplet_settings(cfg)
+    memory_size, memory_start = memory_settings(cfg)
+    if memory_size and strategy != "batch_hard":
+        raise ValueError("loss.memory_size needs loss.triplet_strategy batch_hard")
     if strategy != "mined":
         return train_batch_triplet(cfg, net, strategy, soft, alpha, optimizer, people_per_batch, images_per_person, pools, use_graph,
-                                   world_size, process_group, log, validation)
+                                   world_size, process_group, log, validation, memory_size, memory_start)
     if soft:
         raise ValueError("loss.soft_margin needs loss.triplet_strategy batch_hard or batch_all")
     scheduler = LearningRateScheduler(cfg.train.learning_rate)

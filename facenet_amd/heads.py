@@ -4,6 +4,8 @@ gradient ``demb``.
 * ``triplet_head``: l2_normalize -> triplet loss over rows (a0,p0,n0,a1,...) (arXiv 1503.03832).
 * ``batch_triplet_head``: l2_normalize -> squared distances -> batch-hard / batch-all triplet loss mined inside the labelled batch
   (arXiv 1703.07737 sec. 2).
+* ``xbm_triplet_head``: batch hard mined over the batch and a cross-batch memory of earlier steps' rows (Wang et al., CVPR 2020;
+  DESIGN.md section 32).
 * ``softmax_head``: the classifier Dense(C) + softmax cross-entropy (apps/train_softmax.py:49-104), or with ``margin`` the
   large-margin cosine softmax (NormFace / CosFace / ArcFace) through the same classifier launches.
 * ``add_regularizers``: center loss and prelogits norm on a softmax head (facenet/facenet.py:204-217).
@@ -24,16 +26,18 @@ from .engine import Network, _ptr, bias_region, weight_region
 from .schedule import Op, emit, region, torch_op
 
 
+XBM_MAX_ROWS = 65536                                          # the rows fn_xbm_triplet_fwd_bwd takes as a memory
 TRIPLET_STRATEGIES = ("mined", "batch_hard", "batch_all")      # "mined": TripletMiner fills the (a,p,n) rows; the others: fn_batch_triplet_fwd_bwd
 
 
 def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: float, center_alfa: float, prelogits_norm_factor: float,
                          prelogits_norm_p: float, margin_scale: float = 0.0, margin_arc: float = 0.0, margin_cos: float = 0.0,
-                         triplet_strategy: str = "mined", soft_margin: bool = False):
+                         triplet_strategy: str = "mined", soft_margin: bool = False, memory_size: int = 0, memory_start: int = 0):
     """What the Trainer refuses: an unknown loss, a batch or network that does not fit it, regulariser settings out of range
     (loss.center_factor / center_alfa / prelogits_norm_factor / prelogits_norm_p, train_softmax.yaml:73-78), margin settings out of
     range or without a scale (loss.margin_scale / margin_arc / margin_cos), an unknown triplet strategy or
-    one that does not fit the loss or the batch (loss.triplet_strategy / soft_margin)."""
+    one that does not fit the loss or the batch (loss.triplet_strategy / soft_margin), a cross-batch memory
+    without batch hard, smaller than the batch or larger than 65 536 rows (loss.memory_size / memory_start)."""
     if loss not in ("triplet", "softmax"):
         raise ValueError(f"unknown loss {loss!r}")
     if triplet_strategy not in TRIPLET_STRATEGIES:
@@ -48,6 +52,14 @@ def check_loss_arguments(net: Network, batch: int, loss: str, center_factor: flo
         raise ValueError("triplet batches are laid out (a,p,n,...): batch must be a multiple of 3")
     if loss == "triplet" and triplet_strategy != "mined" and batch > 1024:
         raise ValueError(f"the batch-mined triplet losses take at most 1024 rows, got batch {batch}")
+    if isinstance(memory_size, bool) or not isinstance(memory_size, (int, np.integer)) or memory_size < 0:
+        raise ValueError(f"memory_size must be a non-negative integer, got {memory_size!r}")
+    if isinstance(memory_start, bool) or not isinstance(memory_start, (int, np.integer)) or memory_start < 0:
+        raise ValueError(f"memory_start must be a non-negative integer, got {memory_start!r}")
+    if memory_size and (loss != "triplet" or triplet_strategy != "batch_hard"):
+        raise ValueError("the cross-batch memory needs loss 'triplet' with triplet_strategy 'batch_hard'")
+    if memory_size and not batch <= memory_size <= XBM_MAX_ROWS:
+        raise ValueError(f"memory_size must be in [batch, {XBM_MAX_ROWS}] = [{batch}, {XBM_MAX_ROWS}], got {memory_size}")
     if loss == "softmax" and net.nrof_classes is None:
         raise ValueError("softmax training needs Network(nrof_classes=...)")
     if not (center_factor >= 0 and prelogits_norm_factor >= 0):
@@ -115,6 +127,39 @@ def batch_triplet_head(net: Network, emb: torch.Tensor, demb: torch.Tensor, loss
     emit(ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(dembn), _ptr(demb), batch, E, 1e-10,
          r=[region(emb), region(dembn)], w=[region(demb)])
     return Head(ops, dict(embn=embn, dembn=dembn, dist=dist, coef=coef, labels=labels, mine_info=mine_info))
+
+
+def xbm_triplet_head(net: Network, emb: torch.Tensor, demb: torch.Tensor, loss: torch.Tensor, alpha: float, soft: bool,
+                     memory_size: int, memory_start: int) -> Head:
+    """batch_triplet_head's batch hard with a cross-batch memory: the anchors are mined over the batch and a ring
+    of the last ``memory_size`` normalised rows of earlier steps.  The enqueue comes last, so a step never mines against its own rows;
+    the ring (mem_emb, mem_labels, mem_state) is the head's state.  ``labels`` must name the same identity in every step."""
+    lib, dev, (batch, E), M = net.lib, net.device, emb.shape, memory_size
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    embn, dembn = torch.zeros(batch, E, **f32), torch.zeros(batch, E, **f32)
+    dist, coef = torch.zeros(batch, batch, **f32), torch.zeros(batch, batch, **f32)
+    labels, mine_info = torch.zeros(batch, **i32), torch.zeros(8, **i32)
+    mem_emb, mem_labels, mem_state = torch.zeros(M, E, **f32), torch.zeros(M, **i32), torch.zeros(4, **i32)
+    mem_dist, mpick, mcoef = torch.zeros(batch, M, **f32), torch.zeros(batch, 2, **i32), torch.zeros(batch, 2, **f32)
+    ring = [region(mem_emb), region(mem_labels), region(mem_state)]
+    ops: List[Op] = []
+    emit(ops, "l2norm_fwd", lib.fn_l2norm_fwd, _ptr(emb), _ptr(embn), batch, E, 1e-10, r=[region(emb)], w=[region(embn)])
+    emit(ops, "pairwise_sqdist", lib.fn_pairwise_sqdist, _ptr(embn), _ptr(embn), _ptr(dist), None, batch, batch, E, 2,
+         r=[region(embn)], w=[region(dist)])
+    emit(ops, "pairwise_sqdist", lib.fn_pairwise_sqdist, _ptr(embn), _ptr(mem_emb), _ptr(mem_dist), None, batch, M, E, 2,
+         r=[region(embn), region(mem_emb)], w=[region(mem_dist)])
+    emit(ops, "xbm_triplet", lib.fn_xbm_triplet_fwd_bwd, _ptr(embn), _ptr(dist), _ptr(labels), _ptr(mem_emb), _ptr(mem_dist), _ptr(mem_labels),
+         _ptr(mem_state), _ptr(dembn), _ptr(loss), _ptr(coef), _ptr(mpick), _ptr(mcoef), _ptr(mine_info), batch, M, E, alpha, 1 if soft else 0,
+         r=[region(embn), region(dist), region(labels), region(mem_dist)] + ring,
+         w=[region(dembn), region(loss), region(coef), region(mpick), region(mcoef), region(mine_info)])
+    emit(ops, "l2norm_bwd", lib.fn_l2norm_bwd, _ptr(emb), _ptr(dembn), _ptr(demb), batch, E, 1e-10,
+         r=[region(emb), region(dembn)], w=[region(demb)])
+    emit(ops, "xbm_enqueue", lib.fn_xbm_enqueue, _ptr(embn), _ptr(labels), _ptr(mem_emb), _ptr(mem_labels), _ptr(mem_state), batch, M, E,
+         memory_start, r=[region(embn), region(labels), region(mem_state)], w=ring)
+    return Head(ops, dict(embn=embn, dembn=dembn, dist=dist, coef=coef, labels=labels, mine_info=mine_info, mem_emb=mem_emb,
+                          mem_labels=mem_labels, mem_state=mem_state, mem_dist=mem_dist, mpick=mpick, mcoef=mcoef),
+                state=("mem_emb", "mem_labels", "mem_state"))
 
 
 def _cls_desc(batch: int, L, dt: int):

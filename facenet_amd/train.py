@@ -8,6 +8,8 @@
   (a0,p0,n0,a1,...).  ``TripletMiner`` does the online selection in a PxK pool on device.
 * ``Trainer(loss='triplet', triplet_strategy='batch_hard' | 'batch_all', soft_margin=...)`` trains on the whole labelled P x K batch
   and mines inside it (arXiv 1703.07737 sec. 2): ``set_images(images, labels)``, no miner, no gather.
+* ``Trainer(..., triplet_strategy='batch_hard', memory_size=M, memory_start=s)`` also mines over a cross-batch memory of the last M
+  normalised rows of earlier steps (Wang et al., CVPR 2020); the labels are then dataset-wide identity ids.
 * ``Trainer(loss='softmax', center_factor=..., prelogits_norm_factor=...)`` adds the reference's embedding regularisers
   (facenet/facenet.py:204-217 center loss, apps/configs/train_softmax.yaml:73-78 prelogits norm).
 * ``Trainer(loss='softmax', margin_scale=64, margin_arc=0.5)`` replaces the plain softmax head by the large-margin cosine softmax
@@ -29,6 +31,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import warnings
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -77,7 +80,8 @@ class Trainer:
                  n_buckets: int = 6, n_streams: int = 1, group_wgrad: bool = True, force_segments: bool = False,
                  center_factor: float = 0.0, center_alfa: float = 0.95, prelogits_norm_factor: float = 0.0, prelogits_norm_p: float = 1.0,
                  moving_average_decay: Optional[float] = None, optimizer: str = "ADAM", margin_scale: float = 0.0,
-                 margin_arc: float = 0.0, margin_cos: float = 0.0, triplet_strategy: str = "mined", soft_margin: bool = False):
+                 margin_arc: float = 0.0, margin_cos: float = 0.0, triplet_strategy: str = "mined", soft_margin: bool = False,
+                 memory_size: int = 0, memory_start: int = 0):
         self.group_wgrad = group_wgrad
         self.optimizer = check_optimizer(optimizer)        # beta1, beta2 and epsilon are Adam's; the other rules' constants: OPTIMIZERS
         self.rule = OPTIMIZERS[self.optimizer]
@@ -90,10 +94,12 @@ class Trainer:
         self.exchange = world_size > 1 or process_group is not None
         self.segmented = self.exchange or force_segments
         check_loss_arguments(net, batch, loss, center_factor, center_alfa, prelogits_norm_factor, prelogits_norm_p, margin_scale,
-                             margin_arc, margin_cos, triplet_strategy, soft_margin)
+                             margin_arc, margin_cos, triplet_strategy, soft_margin, memory_size, memory_start)
         # "mined": rows (a,p,n,...) filled by a TripletMiner; "batch_hard" / "batch_all": mined inside the labelled batch (section 31)
         self.triplet_strategy, self.soft_margin = triplet_strategy, bool(soft_margin)
         self.batch_mined = loss == "triplet" and triplet_strategy != "mined"
+        # a cross-batch memory of the last memory_size normalised rows, filled from step memory_start on (section 32); 0: none
+        self.memory_size, self.memory_start = int(memory_size), int(memory_start)
         # NormFace / CosFace / ArcFace: settings, not state; margin_scale == 0 is the plain softmax head
         self.margin_scale, self.margin_arc, self.margin_cos = float(margin_scale), float(margin_arc), float(margin_cos)
         self.margin = margin_scale > 0
@@ -129,7 +135,9 @@ class Trainer:
         self.plan: Lowering = net.plan(batch, training=True, step_word=self.hyper.view(torch.int32)[4:5], rank=rank)
         self.demb = torch.zeros(batch, E, dtype=torch.float32, device=dev)
         self.emb = self.plan.embedding.buf.act.view(batch, E)
-        if self.batch_mined:
+        if self.memory_size:
+            head = heads.xbm_triplet_head(net, self.emb, self.demb, self.loss, alpha, self.soft_margin, self.memory_size, self.memory_start)
+        elif self.batch_mined:
             head = heads.batch_triplet_head(net, self.emb, self.demb, self.loss, alpha, triplet_strategy, self.soft_margin)
         elif loss == "triplet":
             head = heads.triplet_head(net, self.emb, self.demb, self.loss, alpha)
@@ -140,7 +148,8 @@ class Trainer:
                 heads.add_regularizers(head, net, self.emb, self.demb, self.center_factor, float(center_alfa), self.prelogits_norm_factor,
                                        float(prelogits_norm_p), world_size, rank)
         # the head's tensors are the trainer's attributes, bound here once: embn, dembn (triplet, margin); dist, coef, labels, mine_info
-        # (batch-mined triplet); labels, emb_lp, logits, dlogits (softmax); rnorm, margin_t (margin); reg_terms, centers, center_rows (regularisers).  `head` itself stays: it
+        # (batch-mined triplet); mem_emb, mem_labels, mem_state, mem_dist, mpick, mcoef (its cross-batch memory); labels, emb_lp, logits,
+        # dlogits (softmax); rnorm, margin_t (margin); reg_terms, centers, center_rows (regularisers).  `head` itself stays: it
         # keeps what its launches point at alive
         self.head, self.centers = head, None
         for name, t in head.tensors.items():
@@ -364,7 +373,8 @@ class Trainer:
             if lab.min() < -2 ** 31 or lab.max() >= 2 ** 31:
                 raise ValueError("labels must fit int32")
             _, inverse, counts = np.unique(lab, return_inverse=True, return_counts=True)
-            if len(counts) < 2 or not bool((counts[inverse] >= 2).any()):
+            # (with a cross-batch memory a row may find both in the memory: what the step had is in triplet_stats()["anchors"])
+            if not self.memory_size and (len(counts) < 2 or not bool((counts[inverse] >= 2).any())):
                 raise ValueError("no row of the batch has both a positive and a negative: the labels need at least two identities, one "
                                  "of them with two rows")
             self.labels.copy_(torch.from_numpy(lab.astype(np.int32)).to(self.net.device))
@@ -401,6 +411,10 @@ class Trainer:
         if self.centers is not None:
             out["centers:0"] = self.centers.cpu().numpy()      # the TF1 variable of facenet.py:208 (identical on every replica)
         out.update(self.opt.average_state_dict())
+        if self.memory_size:                                   # this replica's ring: a resumed run mines against the same rows
+            out["xbm/embeddings:0"] = self.mem_emb.cpu().numpy()
+            out["xbm/labels:0"] = self.mem_labels.cpu().numpy()
+            out["xbm/state:0"] = self.mem_state.cpu().numpy()
         return out
 
     def save_checkpoint(self, path, epoch: int = 0):
@@ -416,7 +430,7 @@ class Trainer:
         with np.load(path, allow_pickle=False) as z:
             sd = {k: z[k] for k in z.files}
         optimizer_keys = tuple(r.keras + "/" for r in OPTIMIZERS.values())
-        net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith(optimizer_keys) and k != "epoch"})
+        net.load_keras_params({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if not k.startswith(optimizer_keys + ("xbm/",)) and k != "epoch"})
         if self.centers is not None:
             if "centers:0" in sd:
                 c = np.asarray(sd["centers:0"], dtype=np.float32)
@@ -426,7 +440,31 @@ class Trainer:
             else:
                 self.centers.zero_()                            # a checkpoint from a run without center loss
         self.opt.load_state_dict(sd, path)
+        if self.memory_size:
+            self._load_memory(sd, path)
         return int(sd.get("epoch", 0))
+
+    # ---- the cross-batch memory ---------------------------------------------------------------------
+    def _require_memory(self):
+        if not self.memory_size:
+            raise RuntimeError("this Trainer keeps no cross-batch memory: build it with memory_size > 0")
+
+    def reset_memory(self):
+        """Empty the cross-batch memory; memory_start counts again from here."""
+        self._require_memory()
+        self.mem_state.zero_()
+
+    def _load_memory(self, sd, path):
+        keys = ("xbm/embeddings:0", "xbm/labels:0", "xbm/state:0")
+        found = [np.asarray(sd[k]) for k in keys if k in sd]
+        if len(found) == 3 and found[0].shape == tuple(self.mem_emb.shape) and found[1].shape == tuple(self.mem_labels.shape) \
+                and found[2].shape == (4,):
+            for t, a in zip((self.mem_emb, self.mem_labels, self.mem_state), found):
+                t.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(dtype=t.dtype))
+            return
+        why = "holds no cross-batch memory" if len(found) < 3 else f"holds a memory of {found[0].shape[0]} x {found[0].shape[-1]}"
+        warnings.warn(f"checkpoint {path} {why}; this trainer's is {self.memory_size} x {self.net.E}: it starts empty")
+        self.mem_state.zero_()
 
     # ---- the moving average of the weights (DESIGN.md section 14) ---------------------------------------------------------
     def _require_average(self):
@@ -529,11 +567,17 @@ class Trainer:
 
     def triplet_stats(self) -> Dict[str, float]:
         """The last step's mining counts of a batch-mined triplet trainer (one small copy from the device): ``anchors`` (rows with a
-        positive and a negative), ``terms``, ``active`` (hinge: terms > 0; soft margin: all of them) and ``active_fraction``."""
+        positive and a negative), ``terms``, ``active`` (hinge: terms > 0; soft margin: all of them) and ``active_fraction``.  With a cross-batch memory also
+        ``memory_valid`` (the rows it held when the step mined) and ``memory_positives`` / ``memory_negatives`` (the anchors whose
+        farthest positive / nearest negative was one of them)."""
         if not self.batch_mined:
             raise RuntimeError("triplet_stats() belongs to triplet_strategy 'batch_hard' / 'batch_all'")
-        anchors, terms, active = self.mine_info[:3].cpu().tolist()
-        return {"anchors": anchors, "terms": terms, "active": active, "active_fraction": active / terms if terms else 0.0}
+        info = self.mine_info.cpu().tolist()
+        anchors, terms, active = info[:3]
+        out = {"anchors": anchors, "terms": terms, "active": active, "active_fraction": active / terms if terms else 0.0}
+        if self.memory_size:      # the rows the memory held when the step mined, and the anchors whose pick came out of it
+            out.update(memory_valid=info[6], memory_positives=info[4], memory_negatives=info[5])
+        return out
 
     def loss_terms(self) -> Dict[str, Optional[float]]:
         """The last step's terms under the names the reference logged: ``xent``, ``center_loss``, ``prelogits_norm`` and their

@@ -362,6 +362,27 @@ int fn_triplet_loss_fwd_bwd(const float* emb, float* demb, float* loss, int T, i
  * every row is written.  loss: fp32[4], 8-byte aligned, word 0 receives the loss.  No float atomics: bitwise reproducible. */
 int fn_batch_triplet_fwd_bwd(const float* emb, const float* dist, const int32_t* labels, float* demb, float* loss, float* coef,
                              int32_t* info, int N, int E, float alpha, int strategy, int soft, void* stream);
+/* Batch hard over the batch and a cross-batch memory (Wang et al., CVPR 2020).  emb, dist, labels, demb, loss,
+ * coef, alpha, soft: as fn_batch_triplet_fwd_bwd with strategy 0; labels must name the same identity in every step.
+ * mem_emb fp32 [M,E], mem_labels int32 [M], mem_state int32 [4] = cursor | valid rows | enqueue calls seen | 0: the ring that
+ * fn_xbm_enqueue fills; mem_dist fp32 [N,M] = fn_pairwise_sqdist(emb, mem_emb, metric 2).  N <= M <= 65536.
+ * The candidates of anchor a are the batch columns j != a (union index j) and the slots s < mem_state[1], read on the device (union
+ * index N + s); slots at or beyond it are never looked at.  A row with a positive and a negative in the union is an anchor and gives
+ * one term from its farthest positive and nearest negative, compared as fp32, the lowest union index on ties.
+ * coef [N,N]: the picks that are batch columns.  mpick int32 [N,2]: the memory slot of the positive and of the negative pick, -1
+ * where the pick is a batch column or the row is no anchor.  mcoef fp32 [N,2]: +c and -c for those slots (c = 1, sigma(l), or 0
+ * for an inactive hinge).  info int32 [8]: [0..3] as fn_batch_triplet_fwd_bwd ([3] also covers the valid slots), [4] anchors whose
+ * positive is a memory slot, [5] whose negative is, [6] the valid rows seen, [7] zero.  loss = sum / info[0].
+ * demb [N,E] or NULL: (2/Z) times the chain of fn_batch_triplet_fwd_bwd followed by mcoef[r][0] (emb[r] - mem_emb[mpick[r][0]]) and
+ * mcoef[r][1] (emb[r] - mem_emb[mpick[r][1]]).  The memory receives no gradient.  No float atomics: bitwise reproducible. */
+int fn_xbm_triplet_fwd_bwd(const float* emb, const float* dist, const int32_t* labels, const float* mem_emb, const float* mem_dist,
+                           const int32_t* mem_labels, const int32_t* mem_state, float* demb, float* loss, float* coef, int32_t* mpick,
+                           float* mcoef, int32_t* info, int N, int M, int E, float alpha, int soft, void* stream);
+/* One step of the ring, entirely on the device (a replayed graph advances it): while mem_state[2] < start the call is only counted;
+ * afterwards row i of emb [N,E] and labels [N] goes to slot (cursor + i) mod M, then cursor <- (cursor + N) mod M, valid <-
+ * min(valid + N, M).  mem_state[2] counts every call and saturates.  1 <= N <= min(M, 1024), M <= 65536, 1 <= E <= 512, start >= 0. */
+int fn_xbm_enqueue(const float* emb, const int32_t* labels, float* mem_emb, int32_t* mem_labels, int32_t* mem_state, int N, int M,
+                   int E, int start, void* stream);
 
 /* ---- face-to-face validation statistics: facenet/statistics.py:111-138 (ConfidenceMatrix) with the class-balanced
  * weights of SimilarityCalculator.evaluate (:92-103).  emb fp32 [n,E], unit-norm rows grouped by class (class c = rows
