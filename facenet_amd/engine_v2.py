@@ -81,6 +81,39 @@ def map_sizes(image_size: int) -> Tuple[int, int, int]:
     return s5, s6, (s6 - 3) // 2 + 1
 
 
+# the stages after the stem, in the model's order: repeated residual stage -> (scope of block k, counted from 1; scale of `up`)
+V2_REPEATED = {"block35": ("Repeat/block35_{}", 0.17), "block17": ("Repeat_1/block17_{}", 0.10), "block8": ("Repeat_2/block8_{}", 0.20)}
+V2_TAIL = ("block8_last", "conv_7b", "head")        # Block8 (scale 1, no activation), Conv2d_7b_1x1, pool + dropout + Bottleneck
+V2_STAGES = ("mixed_5a", "mixed_6a", "mixed_7a") + tuple(V2_REPEATED) + V2_TAIL
+
+
+def lower_stages(g: Lowering, cfg, x, stages, E: int, keep: float):
+    """The stages of Inception-ResNet-v2 below the stem (inception_resnet_v2.py:150-256), lowered in the given order onto the
+    feature map ``x``: the whole model (NetworkV2._topology) and a lone stage or chain (BlockNetworkV2) go through these calls.
+    The k-th occurrence of a repeated stage is block k of its ``tf_slim.repeat`` scope."""
+    seen = {k: 0 for k in V2_REPEATED}
+    for stage in stages:
+        if stage == "mixed_5a":
+            x = g.mixed("Mixed_5a", x, mixed_5a_towers(cfg["mixed_5a"]["branch"]))
+        elif stage == "mixed_6a":
+            x = g.reduction("Mixed_6a", x, mixed_6a_towers(cfg["mixed_6a"]["branch"]), branch="Branch_{}")
+        elif stage == "mixed_7a":
+            x = g.reduction("Mixed_7a", x, mixed_7a_towers(cfg["mixed_7a"]["branch"]), branch="Branch_{}")
+        elif stage in V2_REPEATED:
+            scope, scale = V2_REPEATED[stage]
+            seen[stage] += 1
+            x = g.block(scope.format(seen[stage]), x, V2_BLOCKS[stage], x.C, scale, True, branch="Branch_{}", up_name="Conv2d_1x1")
+        elif stage == "block8_last":
+            x = g.block("Block8", x, V2_BLOCKS["block8"], x.C, 1.0, False, branch="Branch_{}", up_name="Conv2d_1x1")
+        elif stage == "conv_7b":
+            x = g.cbr("Conv2d_7b_1x1", x, 1536, (1, 1), 1, "same")
+        elif stage == "head":
+            x = g.head(x, E, dense="Bottleneck", pool="Logits/AvgPool_1a", out="Bottleneck/bn", whole_map=True, keep=keep)
+        else:
+            raise ValueError(f"unknown Inception-ResNet-v2 stage {stage!r}: expected one of {V2_STAGES}")
+    return x
+
+
 class NetworkV2(Network):
     """Parameters + topology of Inception-ResNet-v2.  ``config``: the yaml's keys (``mixed_5a`` / ``mixed_6a`` / ``mixed_7a``
     ``.branch``, ``repeat``, ``embedding_size``, ``keep_probability``, ``weight_decay``); ``embedding_size`` given as an argument
@@ -114,20 +147,9 @@ class NetworkV2(Network):
         x = g.cbr("Conv2d_3b_1x1", x, 80, (1, 1), 1, "valid")
         x = g.cbr("Conv2d_4a_3x3", x, 192, (3, 3), 1, "valid")
         x = g.maxpool("MaxPool_5a_3x3", x)
-        x = g.mixed("Mixed_5a", x, mixed_5a_towers(cfg["mixed_5a"]["branch"]))
         r35, r17, r8 = (int(v) for v in cfg["repeat"])
-        for i in range(r35):
-            x = g.block(f"Repeat/block35_{i + 1}", x, V2_BLOCKS["block35"], x.C, 0.17, True, branch="Branch_{}", up_name="Conv2d_1x1")
-        x = g.reduction("Mixed_6a", x, mixed_6a_towers(cfg["mixed_6a"]["branch"]), branch="Branch_{}")
-        for i in range(r17):
-            x = g.block(f"Repeat_1/block17_{i + 1}", x, V2_BLOCKS["block17"], x.C, 0.10, True, branch="Branch_{}", up_name="Conv2d_1x1")
-        x = g.reduction("Mixed_7a", x, mixed_7a_towers(cfg["mixed_7a"]["branch"]), branch="Branch_{}")
-        for i in range(r8):
-            x = g.block(f"Repeat_2/block8_{i + 1}", x, V2_BLOCKS["block8"], x.C, 0.20, True, branch="Branch_{}", up_name="Conv2d_1x1")
-        x = g.block("Block8", x, V2_BLOCKS["block8"], x.C, 1.0, False, branch="Branch_{}", up_name="Conv2d_1x1")
-        x = g.cbr("Conv2d_7b_1x1", x, 1536, (1, 1), 1, "same")
-        return g.head(x, self.E, dense="Bottleneck", pool="Logits/AvgPool_1a", out="Bottleneck/bn", whole_map=True,
-                      keep=self.keep_probability)
+        stages = ["mixed_5a"] + ["block35"] * r35 + ["mixed_6a"] + ["block17"] * r17 + ["mixed_7a"] + ["block8"] * r8 + list(V2_TAIL)
+        return lower_stages(g, cfg, x, stages, self.E, self.keep_probability)
 
     # ---- slim variable names ------------------------------------------------------------------
     def variable_table(self) -> List[Tuple[str, str]]:
@@ -164,6 +186,28 @@ class NetworkV2(Network):
         """Every variable under its slim name (``variable_table`` order)."""
         p = self.export_keras_params(moving_stats, params)
         return OrderedDict((k, p[i]) for k, i in self.variable_table())
+
+
+class BlockNetworkV2(NetworkV2):
+    """A stage of Inception-ResNet-v2, or a chain of them (``stages``: names of V2_STAGES in the order they run; a chain may
+    cross a reduction), on a [N,H,W,C] low-precision feature map: ``lower_stages`` on ``Lowering.feature_input``, so the lowering,
+    the kernels and the fusions are those of the full network.  As with engine.BlockNetwork, ``plan.bufs['trunk']`` is the input
+    (``.act`` in, ``.grad`` out) and ``plan.embedding`` the output of the last stage (``.act`` out, ``.grad`` in; after ``head``:
+    the fp32 embedding, whose gradient ``build_backward`` takes)."""
+
+    def __init__(self, stages, H: int, W: int, C: int, embedding_size: int = 128, config=None, **kw):
+        self._stages = tuple([stages] if isinstance(stages, str) else stages)
+        unknown = [s for s in self._stages if s not in V2_STAGES]
+        if unknown or not self._stages:
+            raise ValueError(f"unknown Inception-ResNet-v2 stages {unknown}: expected names of {V2_STAGES}")
+        self._map = (int(H), int(W), int(C))
+        super().__init__(embedding_size=embedding_size, config=config, **kw)
+
+    def _topology(self, g: Lowering):
+        return lower_stages(g, self.cfg, g.feature_input(*self._map), self._stages, self.E, self.keep_probability)
+
+    def _engine_keys(self, params):
+        return params          # a lone stage has no place in a checkpoint's variable naming: engine keys only
 
 
 V1_MODULES = ("facenet.models.inception_resnet_v1", "facenet_amd.models.inception_resnet_v1")

@@ -16,7 +16,7 @@ import sys
 import torch
 
 from facenet_amd import _lib
-from tests.plan_signature import OPTION_VARS, _environ, _stub_network
+from tests.plan_signature import OPTION_VARS, V2_BLOCK_PLANS, _environ, _stub_network
 from tests.util import conv_desc
 
 POINTER_FIELDS = [f for f, t in _lib.ConvDesc._fields_ if t is C.c_void_p]
@@ -105,6 +105,13 @@ def _block(kind, HW, Cc, N, training, **kw):
     return lambda: _lower(BlockNetwork(kind, HW, HW, Cc, allocate=False, device="cpu", **kw), N, training)
 
 
+def _block_v2(stages, HW, Cc, N, keep=1.0):
+    from facenet_amd.engine_v2 import BlockNetworkV2
+    from tests.irv2_oracle import BLOCK_E, BLOCK_SEED
+    return lambda: _lower(BlockNetworkV2(stages, HW, HW, Cc, embedding_size=BLOCK_E, config={"keep_probability": keep}, seed=BLOCK_SEED,
+                                         allocate=False, device="cpu"), N, True)
+
+
 PLANS = {
     "v1_train_90": ({}, _v1(90, True)),
     "v1_infer_180_no_fuse_blocks": ({"FACENET_FUSE_BLOCKS": "0"}, _v1(180, False)),
@@ -118,6 +125,8 @@ PLANS = {
     "reduction_b_train_6": ({}, _block("reduction_b", 8, 896, 6, True)),
     "block35_infer_32_no_fuse_blocks": ({"FACENET_FUSE_BLOCKS": "0"}, _block("block35", 17, 256, 32, False, repeat=2)),      # (fused: no convolution launch)
     "block17_infer_32_no_fuse_blocks": ({"FACENET_FUSE_BLOCKS": "0"}, _block("block17", 8, 896, 32, False, scale=0.1, repeat=2)),
+    # the lone stages and chains of Inception-ResNet-v2 of tests/plan_signature.V2_BLOCK_PLANS
+    **{key: ({}, _block_v2(*spec)) for key, spec in V2_BLOCK_PLANS.items()},
     "v1_train_6_norm_on_load": ({"FACENET_NORM_ON_LOAD": "1"}, _v1(6, True)),
     "v1_train_6_lazy_bn_17": ({"FACENET_LAZY_BN_MAXHW": "17"}, _v1(6, True)),
     "v1_train_6_no_merge_siblings": ({"FACENET_MERGE_SIBLINGS": "0"}, _v1(6, True)),

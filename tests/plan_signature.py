@@ -182,6 +182,34 @@ def _block(kind, H, W, Cc, N, training, **kw):
     return lambda: signature(BlockNetwork(kind, H, W, Cc, allocate=False, device="cpu", **kw), N, training, regions=True)
 
 
+def _block_v2(stages, HW, Cc, N, keep=1.0):
+    from facenet_amd.engine_v2 import BlockNetworkV2
+    from tests.irv2_oracle import BLOCK_E, BLOCK_SEED
+    return lambda: signature(BlockNetworkV2(stages, HW, HW, Cc, embedding_size=BLOCK_E, config={"keep_probability": keep}, seed=BLOCK_SEED,
+                                            allocate=False, device="cpu"), N, True, regions=True)
+
+
+# the lone stages and chains of Inception-ResNet-v2: key -> case of tests/irv2_oracle.BLOCK_CASES, the table tests/test_gpu_irv2_blocks.py
+# runs (stages, input map, channels, N, keep), so the recorded plan is the plan that test lowers
+V2_BLOCK_KEYS = {
+    "v2_mixed_5a_train_4": "mixed_5a", "v2_block35_x2_train_4": "block35_x2", "v2_mixed_6a_train_8": "mixed_6a",
+    "v2_block17_x2_train_8": "block17_x2", "v2_mixed_7a_train_48": "mixed_7a", "v2_block8_x2_train_48": "block8_x2",
+    "v2_block8_last_train_48": "block8_last", "v2_chain_35_6a_17_train_8": "chain_35_6a_17", "v2_chain_17_7a_8_train_48": "chain_17_7a_8",
+    "v2_tail_train_48_dropout": "tail_keep_half", "v2_tail_train_48_keep_all": "tail_keep_1", "v2_block35_299_train_2": "g299_block35",
+    "v2_tail_299_train_48_dropout": "g299_tail_keep_half",
+}
+
+
+def _v2_block_plans():
+    from tests.irv2_oracle import BLOCK_CASES
+    plans = {key: BLOCK_CASES[case] for key, case in V2_BLOCK_KEYS.items()}
+    assert all(key.endswith((f"_train_{spec[3]}", f"_train_{spec[3]}_dropout", f"_train_{spec[3]}_keep_all")) for key, spec in plans.items())
+    return plans
+
+
+V2_BLOCK_PLANS = _v2_block_plans()
+
+
 def _trainer(loss="triplet", **kw):
     from facenet_amd.engine import Network
     classes = 10 if loss == "softmax" else None
@@ -216,6 +244,7 @@ CASES = {
     "reduction_b_train_6": ({}, _block("reduction_b", 8, 8, 896, 6, True)),
     "block35_infer_32": ({}, _block("block35", 17, 17, 256, 32, False, repeat=2)),
     "block17_infer_32": ({}, _block("block17", 8, 8, 896, 32, False, scale=0.1, repeat=2)),
+    **{key: ({}, _block_v2(*spec)) for key, spec in V2_BLOCK_PLANS.items()},
     "trainer_triplet": ({}, _trainer()),
     "trainer_softmax": ({}, _trainer("softmax")),
     "trainer_triplet_force_segments": ({}, _trainer(force_segments=True)),

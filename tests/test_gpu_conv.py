@@ -1,6 +1,7 @@
 """Implicit-GEMM convolution kernels (fwd / dgrad / wgrad) against an fp32 CPU convolution on the same
 rounded operands.  Shapes cover every kernel size / stride / padding of Inception-ResNet-v1, ragged M,
-odd channel counts (80, 10575-like), channel slices (ld > C) and the fused epilogues."""
+odd channel counts (80, 10575-like), channel slices (ld > C) and the fused epilogues; CASES also holds the layer shapes of
+Inception-ResNet-v2 (Mixed_5a .. Bottleneck)."""
 import ctypes as C
 
 import numpy as np
@@ -33,8 +34,28 @@ CASES = [
     (2, 40, 33, 32, 64, 3, 3, 1, 1, 1),    # 'same' padding: zero fill on all four sides
     (1, 45, 39, 32, 32, 3, 3, 1, 0, 0),    # 2a-like: 32-wide column tile
     (2, 35, 35, 192, 80, 3, 3, 1, 0, 0),   # Cout=80 (three 32-wide column tiles, the last half empty), six input slices
+    # Inception-ResNet-v2 layer shapes (widths 48, 160, 224, 288, 320, 1088, 2080: 2080 is 32.5 k steps of 64, 16.25 column tiles of 128)
+    (2, 17, 17, 48, 64, 5, 5, 1, 2, 2),    # Mixed_5a 5x5 same
+    (2, 17, 17, 32, 48, 3, 3, 1, 1, 1),    # block35 0b 3x3 (Cout=48)
+    (2, 17, 17, 48, 64, 3, 3, 1, 1, 1),    # block35 0c 3x3 (Cin=48)
+    (2, 17, 17, 128, 320, 1, 1, 1, 0, 0),  # block35 up
+    (2, 17, 17, 320, 32, 1, 1, 1, 0, 0),   # block35 in
+    (2, 17, 17, 320, 384, 3, 3, 2, 0, 0),  # Mixed_6a stride-2
+    (3, 8, 8, 1088, 192, 1, 1, 1, 0, 0),   # block17 in
+    (3, 8, 8, 128, 160, 1, 7, 1, 0, 3),    # block17 1x7 (Cout=160)
+    (3, 8, 8, 160, 192, 7, 1, 1, 3, 0),    # block17 7x1 (Cin=160)
+    (3, 8, 8, 384, 1088, 1, 1, 1, 0, 0),   # block17 up
+    (3, 8, 8, 256, 288, 3, 3, 2, 0, 0),    # Mixed_7a stride-2 (Cout=288)
+    (3, 8, 8, 288, 320, 3, 3, 2, 0, 0),    # Mixed_7a stride-2 (Cin=288)
+    (5, 3, 3, 2080, 192, 1, 1, 1, 0, 0),   # block8 in
+    (5, 3, 3, 192, 224, 1, 3, 1, 0, 1),    # block8 1x3 (Cout=224)
+    (5, 3, 3, 224, 256, 3, 1, 1, 1, 0),    # block8 3x1 (Cin=224)
+    (5, 3, 3, 448, 2080, 1, 1, 1, 0, 0),   # block8 up
+    (5, 3, 3, 2080, 1536, 1, 1, 1, 0, 0),  # Conv2d_7b
+    (7, 1, 1, 1536, 128, 1, 1, 1, 0, 0),   # Bottleneck 1536 -> E
+    (1, 35, 35, 32, 48, 3, 3, 1, 1, 1),    # block35 0b 3x3 at 299 pixels: the library itself picks the halo-tile kernel (no request)
 ]
-HALO_CASES = CASES[-4:]
+HALO_CASES = CASES[13:17]
 HALO = 9000000      # fn_conv_desc.tile_*: ask for the halo-tile kernel (production picks it only for <= 64 source channels, where it wins)
 
 
@@ -1060,7 +1081,11 @@ def test_conv_split_k_variants(lib, bm, bn, ks, c, dt):
 # fn_conv2d_variant(d, 0) / (d, 1) of CASES under the library heuristic (HALO_CASES: with the halo-tile kernel requested)
 CASE_VARIANTS = [(32032, 32032), (32032, 2032032), (32032, 32032), (2032032, 4032032), (32032, 32032), (32032, 32032), (4032032, 2032032),
                  (2032032, 2032032), (2032032, 2032032), (2032032, 2032032), (2032032, 2032032), (32032, 4032032), (4032032, 32032),
-                 (9000064, 9000032), (9000064, 9000032), (9000032, 9000032), (9000032, 9000064)]
+                 (9000064, 9000032), (9000064, 9000032), (9000032, 9000032), (9000032, 9000064),
+                 (4032032, 4032032), (32032, 32032), (32032, 2032032), (32032, 32032), (32032, 32032), (4032032, 32032),      # v2: Mixed_5a .. Mixed_6a
+                 (4032032, 32032), (2032032, 4032032), (4032032, 4032032), (32032, 2032032), (4032032, 4032032), (4032032, 4032032),   # block17, Mixed_7a
+                 (4032032, 32032), (2032032, 2032032), (2032032, 2032032), (32032, 4032032), (2032032, 32032), (4032032, 32032),      # block8 .. Bottleneck
+                 (9000032, 9000032)]                                                                                                   # halo at 299, unrequested
 NINE_TILES = [128128, 128064, 128032, 64128, 64064, 64032, 32128, 32064, 32032]
 
 
@@ -1079,7 +1104,8 @@ def _launch_checked(lib, L, what):
 def test_conv_single_launches_elementwise(lib, case, dt):
     """Every layer of CASES as a single launch against fp64, element by element: forward with BatchNorm statistics over four
     replicas, the data gradient plain and accumulated onto a base; the four HALO_CASES on conv_halo_kernel (tile 9000000), where
-    one wrong border pixel of one tile fails."""
+    one wrong border pixel of one tile fails.  The Block35 3x3 layer of the 299-pixel geometry (1, 35, 35, 32, 48) asks for no
+    tile: CASE_VARIANTS holds the library to choosing the halo-tile kernel for it, forward and data gradient."""
     N, H, W, Cin, Cout, kh, kw, s, ph, pw, OH, OW = _geo(case)
     tile = HALO if case in HALO_CASES else 0
     want = CASE_VARIANTS[CASES.index(case)]

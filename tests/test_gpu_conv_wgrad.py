@@ -66,7 +66,32 @@ TAPS_GEOS = [
 ]
 NOT_TAPS_GEO = (1, 3, 9, 64, 64, 3, 3, 1, 1, 1)     # 27 output pixels: stays on the general kernel
 
-ALL_WGRAD_CASES = [g for _, g in TILE_PARAMS] + [g for g, _ in REDUCE_CASES] + [g for g, _ in NORM_CASES] + TAPS_GEOS + [NOT_TAPS_GEO]
+# the layer shapes of Inception-ResNet-v2 under the library's own variant: (case, fn_conv2d_variant(d, 2))
+V2_CASES = [
+    ((2, 17, 17, 48, 64, 5, 5, 1, 2, 2), 64064),        # Mixed_5a 5x5: 25 taps, not a layer of the tap-sharing kernel
+    ((2, 17, 17, 32, 48, 3, 3, 1, 1, 1), TAPS),         # block35 0b (Cout = 48: a cout tile three quarters full)
+    ((2, 17, 17, 48, 64, 3, 3, 1, 1, 1), TAPS),         # block35 0c (Cin = 48: the second 32-channel slice half empty)
+    ((2, 17, 17, 128, 320, 1, 1, 1, 0, 0), 64064),      # block35 up
+    ((2, 17, 17, 320, 32, 1, 1, 1, 0, 0), 32064),       # block35 in
+    ((2, 17, 17, 320, 384, 3, 3, 2, 0, 0), TAPS),       # Mixed_6a stride 2
+    ((3, 8, 8, 1088, 192, 1, 1, 1, 0, 0), 64064),       # block17 in
+    ((3, 8, 8, 128, 160, 1, 7, 1, 0, 3), TAPS),         # block17 1x7 (Cout = 160)
+    ((3, 8, 8, 160, 192, 7, 1, 1, 3, 0), TAPS),         # block17 7x1 (Cin = 160)
+    ((3, 8, 8, 384, 1088, 1, 1, 1, 0, 0), 64064),       # block17 up
+    ((3, 8, 8, 256, 288, 3, 3, 2, 0, 0), 64128),        # Mixed_7a stride 2 (27 output pixels: the general kernel)
+    ((3, 8, 8, 288, 320, 3, 3, 2, 0, 0), 64064),
+    ((5, 3, 3, 2080, 192, 1, 1, 1, 0, 0), 64064),       # block8 in: K = 2080 = 32.5 column tiles of 64
+    ((5, 3, 3, 192, 224, 1, 3, 1, 0, 1), 64064),        # block8 1x3 (Cout = 224)
+    ((5, 3, 3, 224, 256, 3, 1, 1, 1, 0), 64064),        # block8 3x1 (Cin = 224)
+    ((5, 3, 3, 448, 2080, 1, 1, 1, 0, 0), 64064),       # block8 up: 32.5 cout tiles
+    ((5, 3, 3, 2080, 1536, 1, 1, 1, 0, 0), 128064),     # Conv2d_7b
+    ((7, 1, 1, 1536, 128, 1, 1, 1, 0, 0), 64064),       # Bottleneck
+    ((1, 35, 35, 32, 48, 3, 3, 1, 1, 1), TAPS),         # block35 0b at 299 pixels: M = 1225, the one case here above M = 578 (the
+    #                                                     layer is listed for the forward's halo kernel; its dW is held too, M <= WGRAD_MAX_M)
+]
+
+ALL_WGRAD_CASES = ([g for _, g in TILE_PARAMS] + [g for g, _ in REDUCE_CASES] + [g for g, _ in NORM_CASES] + TAPS_GEOS + [NOT_TAPS_GEO]
+                   + [g for g, _ in V2_CASES])
 assert all(wgrad_pixels(g) <= WGRAD_MAX_M for g in ALL_WGRAD_CASES)
 
 
@@ -358,3 +383,25 @@ def test_wgrad_map_below_32_pixels_stays_on_the_general_kernel(lib, dt):
     with pytest.raises(ValueError):
         _Group(lib, [d], TAPS, dt)
     _run_grouped_twice(lib, d, variant, dt, dw, ref, aref, wgrad_pixels(case), f"{case} grouped", want_slabs=0)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("case,variant", V2_CASES)
+def test_wgrad_v2_layer_shapes_against_fp64(lib, case, variant, dt):
+    """Every layer shape of Inception-ResNet-v2 on the kernel the library itself chooses for it (asserted): the single launch
+    with the library's split, then the grouped launch of that variant unsplit (direct stores into a NaN-filled dW) and with the
+    library's split, twice with the same bits; x and dy are channel slices between NaN channels."""
+    N, H, W, Cin, Cout, kh, kw, s, ph, pw = case
+    M = wgrad_pixels(case)
+    x, dy, ref, aref = _reference(case, dt, 770)
+    (xb, x0), (dyb, y0) = _place(x, True), _place(dy, True)
+    dw = torch.zeros(Cout, kh, kw, Cin, dtype=torch.float32, device="cuda")
+    d = _desc(case, dt, xb, x0, dyb, y0, dw)
+    assert lib.fn_conv2d_variant(C.byref(d), 2) == variant
+    _lib.check(lib.fn_conv2d_wgrad(C.byref(d), stream()))
+    torch.cuda.synchronize()
+    assert_elementwise(dw, ref, aref, wgrad_k(M, _cdiv(M, 64)), dt, f"v2 {case}, single launch", out_f32=True)
+    d.splits = 1
+    _run_grouped_twice(lib, d, variant, dt, dw, ref, aref, M, f"v2 {case}, grouped, unsplit", want_slabs=0)
+    d.splits = 0
+    _run_grouped_twice(lib, d, variant, dt, dw, ref, aref, M, f"v2 {case}, grouped, library split")
