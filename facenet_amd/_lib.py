@@ -105,6 +105,7 @@ _SIGNATURES = {
     "fn_bn_finalize": [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _p],
     "fn_crop_or_pad_u8": [_p, _p, _p, _p, _i, _i, _p],
     "fn_augment_u8": [_p, _p, _p, _p, _p, _i, _i, _p],
+    "fn_resident_batch_u8": [_p, _p, _p, C.c_longlong, _p, _p, _p, _i, _i, _p],
     "fn_gather_images": [_p, _p, _p, _i, _i, _p],
     "fn_face_crop_workspace": [_p, _i, _i, C.POINTER(C.c_longlong)],
     "fn_face_crop_resize_u8": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, C.c_longlong, _p],

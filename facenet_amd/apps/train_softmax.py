@@ -126,17 +126,22 @@ def train_softmax(cfg, nrof_classes: int, batches=None, embedding_size: int = 51
 
 def dataset_batches(cfg, rank: int = 0, world: int = 1, log=print, **kw):
     """apps/train_softmax.py:28-47: (Database of cfg.dataset.path, this rank's endless shuffled batch pipeline).  The image.random_*
-    keys (train_softmax.yaml:85-91) augment the batches, drawn from a generator seeded by seed + rank; rank 0 logs them once."""
+    keys (train_softmax.yaml:85-91) augment the batches, drawn from a generator seeded by seed + rank; rank 0 logs them once.
+    dataset.resident (with resident_cache, resident_bytes): the same batches from a decoded copy of the set in device memory."""
     from facenet_amd import dataset
     loader = dataset.ImageLoader(config=cfg.image)
     train_dbase = dataset.Database(cfg.dataset)
     augment = dataset.Augmentation.from_config(cfg.image, cfg.seed + rank)
     if augment is not None and rank == 0:
         log(f"augmentation: {augment}")
+    store = None
+    if cfg.dataset.resident:                                      # the decoded set in device memory (DESIGN.md section 33); every
+        from facenet_amd import resident                          # rank holds all of it, since every rank walks all of it
+        store = resident.from_config(cfg.dataset, train_dbase, device=kw.get("device", "cuda"), rank=rank, log=log)
     np.random.seed(cfg.seed + rank)                               # every replica walks its own permutation of the data set
     kw.setdefault("processes", True)
     batches = train_dbase.tf_dataset_api(loader=loader, batch_size=cfg.batch_size // world, repeat=True, buffer_size=10,
-                                         augment=augment, **kw)
+                                         augment=augment, resident=store, **kw)
     return train_dbase, batches
 
 

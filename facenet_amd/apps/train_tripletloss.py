@@ -168,15 +168,20 @@ def train_tripletloss(cfg, people_per_batch: int = 45, images_per_person: int = 
 
 def dataset_pools(cfg, log=print, **kw):
     """P x K batches from cfg.dataset.path: the reference's equal-batches sampler (dataset.py:46-101), 20 classes x 5 images.
-    The image.random_* keys (train_softmax.yaml:85-91) augment them, drawn from a generator seeded by cfg.seed; logged once."""
+    The image.random_* keys (train_softmax.yaml:85-91) augment them, drawn from a generator seeded by cfg.seed; logged once.
+    dataset.resident (with resident_cache, resident_bytes): the same batches from a decoded copy of the set in device memory."""
     from facenet_amd import dataset
     loader = dataset.ImageLoader(config=cfg.image)
     dbase = dataset.Database(cfg.dataset)
     augment = dataset.Augmentation.from_config(cfg.image, cfg.seed)
     if augment is not None:
         log(f"augmentation: {augment}")
+    store = None
+    if cfg.dataset.resident:                                      # the decoded set in device memory (DESIGN.md section 33)
+        from facenet_amd import resident
+        store = resident.from_config(cfg.dataset, dbase, device=kw.get("device", "cuda"), log=log)
     kw.setdefault("processes", True)
-    return dataset.pipeline_with_equal_batches(loader, dbase.classes, cfg, augment=augment, **kw)
+    return dataset.pipeline_with_equal_batches(loader, dbase.classes, cfg, augment=augment, resident=store, **kw)
 
 
 @click.command()

@@ -7,6 +7,8 @@ into pinned host memory, copied on a side stream and centre-cropped / zero-padde
 (`fn_crop_or_pad_u8` = tf.image.resize_with_crop_or_pad) -- or, for training with an `Augmentation`, randomly rotated,
 cropped and flipped in the same single launch (`fn_augment_u8`) -- so what reaches the step is the
 uint8 NHWC batch its first kernel (`fn_image_normalize`) reads.  Batches are prefetched `prefetch` deep; the consumer's stream waits on an event.
+With a `resident` store (facenet_amd.resident) the decoded set already lives on the device and
+`ResidentPipeline` builds the same batches from it by row number, with no decode and no pixel copy per batch.
 
 Not carried over: the `h5file` validity filter (h5py is not in this image: a config that
 sets it raises) and tqdm/loguru progress output.
@@ -248,8 +250,9 @@ class Database:
     def nrof_images_per_class(self):
         return [cls.nrof_images for cls in self.classes]
 
-    def tf_dataset_api(self, loader, batch_size, buffer_size=None, repeat=False, augment=None, **kw):
-        return tf_dataset_api(self.files, self.labels, loader, batch_size, buffer_size=buffer_size, repeat=repeat, augment=augment, **kw)
+    def tf_dataset_api(self, loader, batch_size, buffer_size=None, repeat=False, augment=None, resident=None, **kw):
+        return tf_dataset_api(self.files, self.labels, loader, batch_size, buffer_size=buffer_size, repeat=repeat, augment=augment,
+                              resident=resident, **kw)
 
 
 class BatchPipeline:
@@ -460,12 +463,83 @@ class BatchPipeline:
                     f.cancel()
 
 
-def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=False, augment=None, **kw):
+class ResidentPipeline:
+    """BatchPipeline's protocol over a facenet_amd.resident.ResidentDataset: the same `plan()` callables,
+    the same (uint8 [B,size,size,3], int64 [B]) device tensors, `cardinality()`, `__len__`, `close()` -- and no decode.  Per
+    batch the plan is pulled and the augmentation draws are taken at that moment, in plan order and `prefetch` plans ahead as
+    BatchPipeline does, so for the same seeds of `random`, `np.random` and the Augmentation the batches are BatchPipeline's bit
+    for bit.  Files become rows, the draws are resolved against the store's host (h, w), and labels, records and rows go into
+    one slot of a small pinned ring: one asynchronous H2D copy and one fn_resident_batch_u8 launch on the consumer's current
+    stream.  The host waits only for a slot's event when the ring wraps."""
+
+    RING = 4
+
+    def __init__(self, plan, loader: ImageLoader, cardinality=None, resident=None, augment: Augmentation = None, prefetch=2):
+        if resident is None:
+            raise ValueError("ResidentPipeline needs a ResidentDataset")
+        self._plan, self.loader, self._card, self.resident, self.augment = plan, loader, cardinality, resident, augment
+        self.prefetch, self.device = max(1, prefetch), resident.device
+
+    def close(self):
+        pass
+
+    def cardinality(self):
+        return self._card
+
+    def __len__(self):
+        if self._card is None:
+            raise TypeError("infinite pipeline")
+        return self._card
+
+    def __iter__(self):
+        store, size = self.resident, self.loader.height
+        rec = 8 + AUGMENT_PARAM.itemsize + 4          # per image: int64 label, augmentation record, int32 row
+        ring = [{"host": None, "event": None} for _ in range(self.RING)]
+        pending, turn = deque(), 0
+        plan = iter(self._plan())
+
+        def submit():
+            try:
+                files, labels = next(plan)
+            except StopIteration:
+                return False
+            pending.append((files, labels, self.augment.draw(len(files)) if self.augment is not None else None))
+            return True
+
+        for _ in range(self.prefetch):
+            if not submit():
+                break
+        while pending:
+            files, labels, draws = pending.popleft()
+            submit()
+            n = len(files)
+            rows = store.rows_of(files)                # KeyError before anything is launched
+            slot, turn = ring[turn % self.RING], turn + 1
+            if slot["event"] is not None:
+                slot["event"].synchronize()            # the ring wrapped: this slot's copy must have left the host
+            if slot["host"] is None or slot["host"].numel() < rec * n:
+                slot["host"] = torch.empty(rec * max(n, 256), dtype=torch.uint8).pin_memory()
+            host = slot["host"].numpy()
+            host[:8 * n] = np.asarray(labels, np.int64).view(np.uint8)
+            if draws is not None:
+                host[8 * n:28 * n] = augment_params(draws, store.host_hw[rows], size).view(np.uint8)
+            host[28 * n:32 * n] = rows.view(np.uint8)
+            st = torch.cuda.current_stream(self.device)
+            dev = slot["host"][:rec * n].to(self.device, non_blocking=True)
+            slot["event"] = torch.cuda.Event()
+            slot["event"].record(st)
+            images = torch.empty(n, size, size, 3, dtype=torch.uint8, device=self.device)
+            store.launch(dev.data_ptr() + 28 * n, dev.data_ptr() + 8 * n if draws is not None else 0, images, n, size, st)
+            yield images, dev[:8 * n].view(torch.int64)
+
+
+def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=False, augment=None, resident=None, **kw):
     """dataset.py:15-43: zip(files, labels) -> optional shuffle -> optional repeat -> batch -> prefetch.  With a
     `buffer_size` the reference shuffles once globally and then through a buffer_size*batch_size window, reshuffled
     every iteration; here every epoch is a fresh full permutation (the window's limit case).  `repeat` comes before
     `batch` as in the reference, so a repeating stream has full batches that span epochs and only a finite one ends short.
-    `augment`: an Augmentation for training batches (BatchPipeline), None for the plain centre crop / pad."""
+    `augment`: an Augmentation for training batches (BatchPipeline), None for the plain centre crop / pad.
+    `resident`: a ResidentDataset holding `files` -> a ResidentPipeline over the same plan (`workers` / `processes` are ignored)."""
     files, labels = list(files), list(np.asarray(labels).tolist())
     if len(files) != len(labels):
         raise ValueError("files and labels differ in length")
@@ -487,13 +561,15 @@ def tf_dataset_api(files, labels, loader, batch_size, buffer_size=None, repeat=F
                 return
 
     card = None if repeat else (n + batch_size - 1) // batch_size
+    if resident is not None:
+        return ResidentPipeline(plan, loader, card, resident, augment=augment, prefetch=kw.get("prefetch", 2))
     return BatchPipeline(plan, loader, card, augment=augment, **kw)
 
 
-def pipeline_with_equal_batches(loader, classes, config, augment=None, **kw):
+def pipeline_with_equal_batches(loader, classes, config, augment=None, resident=None, **kw):
     """dataset.py:46-101: endless P x K batches, 20 random classes x 5 random files each (the reference overwrites the
     two config values the same way, :61-62); labels are class indexes.  Raises ValueError (from random.sample) when there
-    are fewer classes / files than asked for, as the reference's generator does.  `augment` as for tf_dataset_api."""
+    are fewer classes / files than asked for, as the reference's generator does.  `augment` and `resident` as for tf_dataset_api."""
     config.nrof_classes_per_batch = 20
     config.nrof_examples_per_class = 5
     for idx, _class in enumerate(classes):
@@ -507,4 +583,6 @@ def pipeline_with_equal_batches(loader, classes, config, augment=None, **kw):
                 _indexes += [cls.index] * config.nrof_examples_per_class
             yield _files, _indexes
 
+    if resident is not None:
+        return ResidentPipeline(plan, loader, None, resident, augment=augment, prefetch=kw.get("prefetch", 2))
     return BatchPipeline(plan, loader, None, augment=augment, **kw)

@@ -205,6 +205,15 @@ typedef struct fn_augment_param {
  * one launch; S must be even.  Sizes are not checked against the src allocation: the caller owns the packing. */
 int fn_augment_u8(const uint8_t* src, const long long* offsets, const int32_t* hw, const fn_augment_param* params, uint8_t* dst, int N,
                   int S, void* stream);
+/* A batch from a data set whose decoded pixels live in device memory: `pool`, `offsets` (byte offsets, 64-bit,
+ * any alignment) and `hw` are the tables of the whole set of M images, and image n of the batch is row rows[n] of them, so no
+ * per-batch table is gathered.  With `params` (one record per batch image) dst is what fn_augment_u8 writes for the same images and
+ * records, byte for byte; with params == NULL every image gets the centre crop / pad of fn_crop_or_pad_u8, computed from hw.
+ * A row outside [0, M) is defined: neither the tables nor the pool are read for it, its output image is all zero and the other
+ * images of the batch are unaffected.  N <= 65535, S even.  Rows inside [0, M) are not checked against the pool allocation: the
+ * caller owns the tables. */
+int fn_resident_batch_u8(const uint8_t* pool, const long long* offsets, const int32_t* hw, long long M, const int32_t* rows,
+                         const fn_augment_param* params, uint8_t* dst, int N, int S, void* stream);
 /* PIL's `frame.crop(window).resize((side, side), LANCZOS)` for 8-bit RGB, bit for bit, for F windows over
  * one HWC u8 frame [H,W,3] in device memory.  `windows` is HOST memory, F x (left, top, right, bottom) with exclusive right /
  * bottom; a window may reach outside the frame on any side (those pixels of the crop are 0).  dst u8 [F,S,S,3] holds rows / columns
